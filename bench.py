@@ -31,6 +31,13 @@ exchange, BASELINE north_star).
   4  8 streams, fp8 (e4m3fn) KV cache + fp8 codec weights, KV reset every --reset-every chunks
      (a new sentence), 256-token chunks (configs[4])
 
+A plain run sets up, warms up, times --steps steps and prints the line. --full measures the rest
+after the timed steps, each in runs of its own: the first-chunk latencies (idle and joining a busy
+scheduler), the per-kernel and codec rooflines, the fp32 parity line and the CPU baseline (null in
+a plain line). --dump-outputs DIR writes what the last timed step delivered (every stream's speech
+tokens and PCM) as float32 DIR/<name>.npy; the inputs are seeded, so two builds can be compared
+output for output.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -381,6 +388,7 @@ def run_config3(args, eng, world, rank, local, dist):
                            tail=int(so.get("tail", 8)), codec_stream=so.get("cs", "1") != "0")
     rng = np.random.default_rng(1234)  # rank 0 draws every rank's request texts
     pcm_bytes = [0]
+    last = {}
 
     class FirstBytes:  # a stream's sink: when its first PCM bytes were delivered
         t = None
@@ -420,6 +428,11 @@ def run_config3(args, eng, world, rank, local, dist):
         if rank == 0:
             pcm_bytes[0] += sum(len(x) for r in got for x in r)
         n_tok = sum(len(st.tokens) for st in streams)
+        if args.dump_outputs:  # (--dump-outputs: the last utterance's tokens and f32le bytes per stream)
+            last.clear()
+            for s, st in enumerate(streams):
+                last[f"tokens_s{s}"] = np.asarray(st.tokens)
+                last[f"pcm_s{s}"] = np.frombuffer(out[s], dtype="<f4")
         for st in streams:
             sched.close_stream(st)
         return n_tok, first
@@ -450,6 +463,8 @@ def run_config3(args, eng, world, rank, local, dist):
         dt, toks = float(t_dt.item()), int(t_tok.item())
     value = toks / dt
     sched.close()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     kern, rl = None, None
     if not args.no_probe:
@@ -1011,9 +1026,19 @@ def main():
                     help="library options for A/B runs, name=value[,name=value] (lvx_set_option; default: production)")
     ap.add_argument("--rehearse", action="store_true",
                     help="CPU-only rehearsal of the multi-rank skeleton (gloo; tests/test_bench_launcher.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: first-chunk latencies, "
+                         "the per-kernel and codec rooflines, the fp32 parity line and the CPU baseline (each can "
+                         "still be dropped with its --no-... option); without it a run sets up, warms up, times "
+                         "--steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step delivered as DIR/<name>.npy (float32): "
+                         "rank 0's speech tokens and PCM of every stream")
     ap.set_defaults(dist_world1=True)
     args = ap.parse_args()
     args.codec_overlap = not args.serial_codec
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_probe = args.no_parity_line = args.no_loaded_latency = True
     if args.streams == 0:
         args.streams = {1: 1, 2: 32, 3: 1, 4: 8}[args.config]
     if args.config == 4:
@@ -1064,8 +1089,12 @@ def main():
 
     from llmvox_amd.engine import build_engine
     S, chunk, K, Wm = args.streams, args.chunk, args.steps, args.warmup
-    if max(K, Wm) * chunk > 8192:
-        raise SystemExit("steps * chunk must stay within block_size 8192 positions")
+    # positions one utterance spans: --utterance tokens (the KV slots are reset at every utterance
+    # start, so --steps is free), else the whole run (configs[3]: --utt-tokens, one utterance a step)
+    span = args.utt_tokens if args.config == 3 else (args.utterance or max(K, Wm) * chunk)
+    if K < 1 or span > 8192:
+        raise SystemExit("--steps must be >= 1 and an utterance (--utterance / --utt-tokens; with --utterance 0: "
+                         "steps * chunk) must stay within block_size 8192 positions")
     kvd = args.kv_dtype or args.dtype
     eng = build_engine(local, args.dtype, kvd, max_streams=max(S, 1), max_positions=8192,
                        max_codec_frames=max(S * chunk, 1280 * S if args.config == 3 else 0),
@@ -1104,6 +1133,8 @@ def main():
         if not reset_every:
             raise SystemExit("--seconds needs utterances (--utterance > 0): a KV reset per sentence")
         n_utt = max(n_utt, 16)  # a pool of 16 sentences per stream, cycled
+    elif reset_every:
+        n_utt = min(n_utt, 16)  # (more than 64 steps: the same pool, cycled by run_chunks)
     n_pos = n_utt * utt
     plans = np.zeros((world * S, n_pos), dtype=np.int32)
     rng = np.random.default_rng(1234)
@@ -1127,8 +1158,11 @@ def main():
     total_tokens = world * S * K * chunk
     value = total_tokens / dt
     toks_rank0 = last_tok[0].cpu().numpy()
+    if rank == 0 and args.dump_outputs:  # the last timed step: every stream's tokens and PCM
+        dump_outputs(args.dump_outputs, {"tokens": last_tok.cpu().numpy(),
+                                         "pcm": pcm_bufs[(K - 1) & 1].cpu().numpy()})
 
-    p50 = first_chunk_latency(eng, overlap=args.codec_overlap)
+    p50 = first_chunk_latency(eng, overlap=args.codec_overlap) if args.full else None
     p50_loaded = None
     if args.config in (1, 2, 4) and not args.no_loaded_latency:
         eng.check_errors()
@@ -1165,34 +1199,36 @@ def main():
 
     # ---- codec: one batched decode of a chunk (S streams x chunk frames), HIP events on the
     # stream it runs on; algorithmic FLOPs per SURVEY 8(d): 125,566,976 + 3,072 L per frame
-    torch.cuda.synchronize()
-    with torch.cuda.stream(codec_stream):
-        eng.decode_codes(tok_bufs[0], 0, out=pcm_bufs[0])
-        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        c0.record(codec_stream)
-        for _ in range(5):
+    codec = None
+    if args.full:
+        torch.cuda.synchronize()
+        with torch.cuda.stream(codec_stream):
             eng.decode_codes(tok_bufs[0], 0, out=pcm_bufs[0])
-        c1.record(codec_stream)
-    c1.synchronize()
-    codec_ms = c0.elapsed_time(c1) / 5
-    codec_flops = S * chunk * (125_566_976 + 3_072 * chunk)
-    codec_peak = 2500.0 if args.dtype == "bf16" else 157.3  # dense bf16 MFMA / exact-f32 MFMA, TFLOP/s
-    peak_note = None
-    if args.codec_dtype == "fp8":
-        # pwconv1 (12 x 2 x 768 x 2,304 = 42,467,328 FLOPs per frame, 33.8 % of the codec) runs W8A8 on
-        # the fp8 MFMA (dense 5,000 TFLOP/s); every other FLOP on bf16 MFMA (2,500): the peak is the
-        # rate at which the decode's FLOP mix would run with each part at its own peak
-        f_pw1 = S * chunk * 42_467_328
-        codec_peak = codec_flops / (f_pw1 / 5000.0 + (codec_flops - f_pw1) / 2500.0)
-        peak_note = ("FLOP-weighted: pwconv1 at the dense fp8 MFMA peak 5,000 TFLOP/s, the rest at the dense "
-                     "bf16 peak 2,500")
-    ckey = f"{args.codec_dtype or args.dtype}/F{S * chunk}/L{chunk}"
-    codec = {"frames": S * chunk, "avg_ms": round(codec_ms, 3),
-             "achieved": round(codec_flops / (codec_ms * 1e-3) / 1e12, 2), "peak": round(codec_peak, 1),
-             "unit": "TFLOP/s", "frac": round(codec_flops / (codec_ms * 1e-3) / 1e12 / codec_peak, 4),
-             "gemm_mfma_busy": pmc_codec(ckey), "pmc_key": ckey}
-    if peak_note:
-        codec["peak_note"] = peak_note
+            c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            c0.record(codec_stream)
+            for _ in range(5):
+                eng.decode_codes(tok_bufs[0], 0, out=pcm_bufs[0])
+            c1.record(codec_stream)
+        c1.synchronize()
+        codec_ms = c0.elapsed_time(c1) / 5
+        codec_flops = S * chunk * (125_566_976 + 3_072 * chunk)
+        codec_peak = 2500.0 if args.dtype == "bf16" else 157.3  # dense bf16 MFMA / exact-f32 MFMA, TFLOP/s
+        peak_note = None
+        if args.codec_dtype == "fp8":
+            # pwconv1 (12 x 2 x 768 x 2,304 = 42,467,328 FLOPs per frame, 33.8 % of the codec) runs W8A8 on
+            # the fp8 MFMA (dense 5,000 TFLOP/s); every other FLOP on bf16 MFMA (2,500): the peak is the
+            # rate at which the decode's FLOP mix would run with each part at its own peak
+            f_pw1 = S * chunk * 42_467_328
+            codec_peak = codec_flops / (f_pw1 / 5000.0 + (codec_flops - f_pw1) / 2500.0)
+            peak_note = ("FLOP-weighted: pwconv1 at the dense fp8 MFMA peak 5,000 TFLOP/s, the rest at the dense "
+                         "bf16 peak 2,500")
+        ckey = f"{args.codec_dtype or args.dtype}/F{S * chunk}/L{chunk}"
+        codec = {"frames": S * chunk, "avg_ms": round(codec_ms, 3),
+                 "achieved": round(codec_flops / (codec_ms * 1e-3) / 1e12, 2), "peak": round(codec_peak, 1),
+                 "unit": "TFLOP/s", "frac": round(codec_flops / (codec_ms * 1e-3) / 1e12 / codec_peak, 4),
+                 "gemm_mfma_busy": pmc_codec(ckey), "pmc_key": ckey}
+        if peak_note:
+            codec["peak_note"] = peak_note
 
     # whole decode step against HBM: algorithmic bytes of every step of the timed chunks (their KV
     # positions) over the measured AR time of those chunks (events around ar_steps in the timed loop)
@@ -1255,7 +1291,7 @@ def main():
             "dist": dist_info or {"backend": None, "world_size": 1},
             "audio_samples_per_s": round(320 * value, 1),
             "realtime_factor_per_stream": round(value / (world * S) / 75.0, 1),
-            "p50_first_chunk_latency_ms": round(p50, 3),
+            "p50_first_chunk_latency_ms": round(p50, 3) if p50 is not None else None,
             "p50_first_chunk_latency_loaded_ms": round(p50_loaded[0], 3) if p50_loaded else None,
             "first_chunk_latency_loaded": ({"p50_ms": round(p50_loaded[0], 3), "p90_ms": round(p50_loaded[1], 3),
                                             "max_ms": round(p50_loaded[2], 3), "joins": p50_loaded[3],
@@ -1285,6 +1321,19 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     _release(eng)
+
+
+def dump_outputs(d, arrays, budget=60_000_000):
+    """--dump-outputs: each array as d/<name>.npy in float32 (token ids < 4096 are exact in it), at most
+    `budget` bytes in all: an array over its share of the budget is cut to a fixed sample of its
+    flattened elements (indices drawn with seed 0, sorted), the same from run to run."""
+    os.makedirs(d, exist_ok=True)
+    share = budget // max(1, len(arrays)) // 4  # elements per array
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _release(eng):

@@ -12,7 +12,7 @@ timeout -k 10 200 python tools/step_sweep.py 2 384 'l0q=0' '' >> $O 2>&1 || exit
 timeout -k 10 300 python tools/l0q_accuracy.py bf16 1 'l0q=0' 'l0q=1' >> $O 2>&1 || exit 1
 timeout -k 10 300 python tools/l0q_accuracy.py bf16 2 'l0q=0' 'l0q=1' >> $O 2>&1 || exit 1
 for o in "l0q=0" "l0q=1"; do
-timeout -k 10 300 python bench.py --config 1 --steps 8 --no-cpu-baseline --no-parity-line --opt $o > gpurun_out/b1_cfg1_$o.jsonl 2> gpurun_out/b1_cfg1.err || { tail -5 gpurun_out/b1_cfg1.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 1 --steps 8 --no-cpu-baseline --no-parity-line --opt $o > $(dirname $O)/b1_cfg1_$o.jsonl 2> $(dirname $O)/b1_cfg1.err || { tail -5 $(dirname $O)/b1_cfg1.err; exit 1; }
 python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('configs[1] $o', d['value'], d['ms_per_step'], d['p50_first_chunk_latency_ms'], d['step_roofline']['us_per_step'])" gpurun_out/b1_cfg1_$o.jsonl >> $O
 done
 grep -v amdgpu.ids $O

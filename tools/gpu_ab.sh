@@ -4,7 +4,7 @@
 set -o pipefail
 export PYTHONPATH=.
 O=gpurun_out/${OUT:-ab}; mkdir -p $O
-COMMON=${COMMON:-"--steps 8 --no-cpu-baseline --no-parity-line --no-probe --no-loaded-latency"}
+COMMON=${COMMON:-"--full --steps 8 --no-cpu-baseline --no-parity-line --no-probe --no-loaded-latency"}
 for p in $(seq 1 ${PAIRS:-3}); do
   for v in A B; do
     eval args=\$${v}_ARGS

@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export PYTHONPATH=.
-TAG=r06c4 ARGS="--config 4 --steps 20 --warmup 0 --no-cpu-baseline --no-parity-line" KEY=bf16/kvfp8/B8/P512 \
-  CKEY=fp8/F2048/L256 BENCH_ARGS="--config 4 --steps 20 --warmup 5 --no-cpu-baseline" bash tools/prof_round.sh || exit 1
+TAG=r06c4 ARGS="--full --config 4 --steps 20 --warmup 0 --no-cpu-baseline --no-parity-line" KEY=bf16/kvfp8/B8/P512 \
+  CKEY=fp8/F2048/L256 BENCH_ARGS="--full --config 4 --steps 20 --warmup 5 --no-cpu-baseline" bash tools/prof_round.sh || exit 1
 bash tools/gpu_round_lines.sh || exit 1
 echo PART2_OK

@@ -14,7 +14,7 @@ O=gpurun_out/$TAG; mkdir -p $O
 # PMC passes launch the steps one by one on the null stream (--null-stream): with the default
 # side-stream HIP-graph replay, rocprofv3 --pmc segfaults in its own thread (profiles/r03/pmc_segv_graph_replay.log);
 # per-dispatch counters do not depend on how the dispatch was submitted
-ARGS=${ARGS:-"--steps 20 --warmup 0 --no-cpu-baseline --no-parity-line"}
+ARGS=${ARGS:-"--full --steps 20 --warmup 0 --no-cpu-baseline --no-parity-line"}
 PARGS=${PARGS:-"$ARGS --null-stream --no-dist-world1"}
 KEY=${KEY:-bf16/kvbf16/B32/P512}
 CKEY=${CKEY:-bf16/F8192/L256}
@@ -36,6 +36,6 @@ find $O/kt -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \;
 python3 tools/probe_trace.py $(find $O/kt -name "*kernel_trace.csv" | head -1) > $O/probe_trace.txt || exit 1
 cat $O/probe_trace.txt
 rm -rf $O/kt
-timeout -k 10 400 python bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5} > $O/bench.jsonl 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py ${BENCH_ARGS:---gpus 1 --full --steps 20 --warmup 5} > $O/bench.jsonl 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
 tail -c 600 $O/bench.jsonl
 echo PROF_OK

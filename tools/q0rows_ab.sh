@@ -15,7 +15,7 @@ LVX_SWEEP_KV=fp8 timeout -k 10 200 python tools/step_sweep.py 8 384 'exp=2' '' '
 timeout -k 10 200 python tools/step_sweep.py 4 384 'exp=2' '' >> $O 2>&1 || exit 1
 timeout -k 10 300 python tools/l0q_accuracy.py bf16 32 'l0q=0' 'l0q=1' >> $O 2>&1 || exit 1
 timeout -k 10 300 python tools/l0q_accuracy.py fp8 8 'l0q=0' 'l0q=1' >> $O 2>&1 || exit 1
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity-line > gpurun_out/q0rows_c2.jsonl 2> gpurun_out/q0rows_c2.err || { tail -5 gpurun_out/q0rows_c2.err; exit 1; }
-timeout -k 10 300 python bench.py --config 4 --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/q0rows_c4.jsonl 2> gpurun_out/q0rows_c4.err || { tail -5 gpurun_out/q0rows_c4.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity-line > $(dirname $O)/q0rows_c2.jsonl 2> $(dirname $O)/q0rows_c2.err || { tail -5 $(dirname $O)/q0rows_c2.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config 4 --steps 20 --warmup 5 --no-cpu-baseline > $(dirname $O)/q0rows_c4.jsonl 2> $(dirname $O)/q0rows_c4.err || { tail -5 $(dirname $O)/q0rows_c4.err; exit 1; }
 for f in c2 c4; do python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('$f', d['value'], d['ms_per_step'], d['p50_first_chunk_latency_ms'], d['step_roofline']['us_per_step'], d['tokens_head'])" gpurun_out/q0rows_$f.jsonl >> $O; done
 grep -v amdgpu.ids $O
