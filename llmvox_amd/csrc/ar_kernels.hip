@@ -15,7 +15,7 @@
 // prologue of c_proj, residual adds / GELU / KV-append are GEMV epilogues. The weight
 // stream is the HBM-bound part: 62.9 MB (bf16) or 125.8 MB (fp32) per step, shared by the
 // B streams of the step.
-#include "lvx_internal.h"
+#include "ar_plan.h"
 
 // No implicit a*b+c contraction in this file: the compiler would choose per unrolled copy, so a
 // batch row's rounding could depend on which copy (batch position) computed it. Fused
@@ -51,17 +51,11 @@ __device__ uint64_t g_lvx_ts[16 * 4 * TS_BLOCKS * 4];
 
 // ---------------------------------------------------------------------------------
 // GEMV family: out[b][n] = sum_k W[n][k] * in[b][k]   (W row-major [N][K], TW in {f32,bf16})
-//   IN  0: in = LayerNorm(x[b]) * ln_w            (eps 1e-5, no bias; src/model.py:37-38)
-//   IN  1: in = h[b] (fp32, K = 3072)
-//   IN  2: in = merge of the split-KV attention partials (flash-decoding combine)
-//   IN  4: in = LayerNorm(x[b] + sum_c yacc[b][c]) (the fused MLP's pending output)
-//   IN  3: layer-0 c_attn: builds x[b] first (a2-a4: text row, codebook row of the previous
-//          token or 0 at position 0, L2-normalise eps 1e-8, + wpe[pos]; or, for the drop-in
-//          row forward, the caller's row + wpe[pos]), block 0 stores it, then LayerNorm.
-//   OUT 0: c_attn: q -> st.q, k/v -> KV cache at the slot's position
-//   OUT 1: residual: x[b][n] += out
-//   OUT 2: h[b][n] = gelu_tanh(out)
-//   OUT 3: logits: dst[b][n] = out
+// IN / OUT: the GIN_ / GOUT_ codes of ar_plan.h, where the mode codes of every kernel family of this
+// file are listed once. The LayerNorm is eps 1e-5, no bias (src/model.py:37-38); GIN_EMBED builds
+// x[b] first (a2-a4: text row, codebook row of the previous token or 0 at position 0, L2-normalise
+// eps 1e-8, + wpe[pos]; or, for the drop-in row forward, the caller's row + wpe[pos]), block 0
+// stores it, then LayerNorm. GOUT_QKV: q -> st.q, k/v -> KV cache at the slot's position.
 // A block is 4 waves; KW waves share the K range of the same RPW rows (KW in {1,4}). Each
 // lane owns 4-element K chunks. All weight loads of the wave are issued before the input
 // prologue (they do not depend on it), so the HBM/MALL latency overlaps the LN / merge /
@@ -86,7 +80,7 @@ struct GemvArgs {
   const float* ln_w;
   float* dst;
   int kv_dtype;          // LVX_DTYPE_F32 / BF16 / FP8
-  // IN 3 inputs
+  // GIN_EMBED inputs
   const float* text_table;
   const float* codebook;
   const float* wpe;
@@ -95,11 +89,10 @@ struct GemvArgs {
   float* yacc;           // batched steps: the mlp c_proj K-slice partials (fp32, plain stores)
   unsigned long long* yfx;  // B <= 2 fused MLP (non-null when the step runs it): its output as YCOPIES
                             // accumulators in 2^-32 fixed point (int64 atomics: order-independent sums)
-  const float* gsum;     // batched c_fc (ar_mfma2_kernel XM 1): ArWeights::fc_gsum of the layer
+  const float* gsum;     // batched c_fc (ar_mfma2_kernel M2X_LN_AFTER): ArWeights::fc_gsum of the layer
   int add_y;             // c_proj: fold the accumulators into x (layers >= 1; 0 at layer 0 = just clear)
-  int defer_sel;         // deferred greedy select (option "defer_select"). 1: B <= 2 GEMV step, lm_head
-                         // publishes per-block granules, the next step's c_attn layer 0 reduces them;
-                         // 2: batched step, the next step's embedding rows kernel reduces the logits
+  int defer_sel;         // the step's select form, an ArSelect (ar_plan.h): SEL_ARGMAX 0, SEL_GRAN 1, SEL_EMBED 2,
+                         // SEL_LN_GRAN 3, SEL_Q0_ROWS 4
   int xmap;              // ar_mfma2_kernel launched as a 1-D grid with the XCD-aligned tile order:
                          // 1 = mlp c_proj (K slice = XCD mod 4), 2 = c_proj batch tiles (tile = XCD mod 2)
   // layer 0's c_attn as table rows (ArWeights q0_*; ar_embed_select_kernel QKV)
@@ -199,8 +192,8 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned gu32;
 typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 
-// Deferred select: lm_head (OUT 9) leaves one 16-byte granule {index << 32 | top1 bits, top2 bits}
-// per (block, row) in st.lmbest; the next step's c_attn layer 0 (IN 5) or ar_select_final_kernel
+// Deferred select: lm_head (GOUT_LOGITS_GRAN) leaves one 16-byte granule {index << 32 | top1 bits, top2 bits}
+// per (block, row) in st.lmbest; the next step's c_attn layer 0 (GIN_EMBED_SELECT) or ar_select_final_kernel
 // reduces a row's 512 granules with one wave: every load in flight at once, then a shuffle tree.
 static_assert(NSPLIT == 16, "the split merges reduce one head's splits as one 16-lane DPP row");
 constexpr int LM_SEL_BLOCKS = VOCAB / 8;  // lm_head blocks on the B <= 2 GEMV path (8 rows each)
@@ -221,10 +214,10 @@ __device__ __forceinline__ Best lmg_reduce(const LmGran& q) {
   return best_wave(r);
 }
 
-// Batched deferred select at 4 <= B <= 8 (defer_sel 3): lm_head (ar_mfma_ln_kernel OUT 3, 16 vocabulary
+// Batched deferred select at 4 <= B <= 8 (SEL_LN_GRAN): lm_head (ar_mfma_ln_kernel MLOUT_LOGITS, 16 vocabulary
 // rows per block) leaves one granule per (block, row) in st.lmbest laid out [256 blocks][8 rows]; the
-// next step's c_attn layer 0 (ar_mfma_ln_kernel MODE 7) reduces a row's 256 granules with one wave
-constexpr int LM8_BLOCKS = VOCAB / 16, LM8_ROWS = 8;
+// next step's c_attn layer 0 (ar_mfma_ln_kernel MLMODE_EMBED_SELECT) reduces a row's 256 granules with one wave
+constexpr int LM8_BLOCKS = VOCAB / 16;  // (LM8_ROWS: ar_plan.h)
 struct LmGran8 {
   u64x2_t g[LM8_BLOCKS / 64];
 };
@@ -300,7 +293,7 @@ __device__ __forceinline__ void wave_ln_to_lds(float4 (&v)[3], const float4 (&ga
   }
 }
 
-// x[b] (IN 0) or x[b] + sum_c yacc[b][c] (IN 4) in the lane layout k = j * 256 + lane * 4: the
+// x[b] (GIN_LN) or x[b] + sum_c yacc[b][c] (GIN_LN_Y) in the lane layout k = j * 256 + lane * 4: the
 // loads are issued by xrow_issue and summed by xrow_sum, so a prefetch does not wait on them
 // The fused MLP's fixed point (B <= 2): partial t -> round(t * 2^32) as int64, added with 64-bit
 // integer atomics (exact, so the sum does not depend on the order the 192 blocks arrive in: the
@@ -322,20 +315,20 @@ __device__ __forceinline__ float yfx_to_f(unsigned long long s) {
   return __ll2float_rn((long long)s) * 2.3283064365386963e-10f;
 }
 
-// FX = false: the batched steps' fp32 K-slice partials (ar_rows_kernel<4>); FX = true: the B <= 2
-// fused MLP's fixed-point copies (GEMV IN 4)
+// FX = false: the batched steps' fp32 K-slice partials (ar_rows_kernel<RMODE_LN_Y>); FX = true: the B <= 2
+// fused MLP's fixed-point copies (GEMV GIN_LN_Y)
 template <int IN, bool FX = false>
 struct XRow {
   float4 x[3];
-  float4 y[(IN == 4 && !FX) ? YCOPIES : 1][3];
-  u64x2n yf[(IN == 4 && FX) ? YCOPIES : 1][3][2];
+  float4 y[(IN == GIN_LN_Y && !FX) ? YCOPIES : 1][3];
+  u64x2n yf[(IN == GIN_LN_Y && FX) ? YCOPIES : 1][3][2];
 };
 template <int IN, bool FX = false>
 __device__ __forceinline__ void xrow_issue(const GemvArgs& a, int b, int lane, XRow<IN, FX>& r) {
   const float* xr = a.st.x + (size_t)b * D;
 #pragma unroll
   for (int j = 0; j < 3; ++j) r.x[j] = *reinterpret_cast<const float4*>(xr + j * 256 + lane * 4);
-  if constexpr (IN == 4 && FX) {
+  if constexpr (IN == GIN_LN_Y && FX) {
 #pragma unroll
     for (int c = 0; c < YCOPIES; ++c)
 #pragma unroll
@@ -344,7 +337,7 @@ __device__ __forceinline__ void xrow_issue(const GemvArgs& a, int b, int lane, X
         r.yf[c][j][0] = yp[0];
         r.yf[c][j][1] = yp[1];
       }
-  } else if constexpr (IN == 4) {
+  } else if constexpr (IN == GIN_LN_Y) {
 #pragma unroll
     for (int c = 0; c < YCOPIES; ++c)
 #pragma unroll
@@ -357,12 +350,12 @@ __device__ __forceinline__ void xrow_sum(const XRow<IN, FX>& r, float4 (&v)[3]) 
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
     float4 t = r.x[j];
-    if constexpr (IN == 4 && FX) {
+    if constexpr (IN == GIN_LN_Y && FX) {
       u64x2n s0 = r.yf[0][j][0], s1 = r.yf[0][j][1];
 #pragma unroll
       for (int c = 1; c < YCOPIES; ++c) { s0 += r.yf[c][j][0]; s1 += r.yf[c][j][1]; }
       t.x += yfx_to_f(s0.x); t.y += yfx_to_f(s0.y); t.z += yfx_to_f(s1.x); t.w += yfx_to_f(s1.y);
-    } else if constexpr (IN == 4) {
+    } else if constexpr (IN == GIN_LN_Y) {
 #pragma unroll
       for (int c = 0; c < YCOPIES; ++c) { t.x += r.y[c][j].x; t.y += r.y[c][j].y; t.z += r.y[c][j].z; t.w += r.y[c][j].w; }
     }
@@ -386,18 +379,18 @@ __device__ __forceinline__ void xrow_sum(const XRow<IN, FX>& r, float4 (&v)[3]) 
 
 template <int K, int IN, int BG = 0>
 __device__ __forceinline__ void gemv_stage_input(const GemvArgs& a, float* xs, float* aux, const float4 (&gam)[3], int g0, int bg,
-                                                 const XRow<IN == 4 ? 4 : 0, true>& xpre, int4 ripre, bool prefetched) {
+                                                 const XRow<IN == GIN_LN_Y ? GIN_LN_Y : GIN_LN, true>& xpre, int4 ripre, bool prefetched) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  if (IN == 0 || IN == 3 || IN == 4 || IN == 5) {
+  if (IN == GIN_LN || IN == GIN_EMBED || IN == GIN_LN_Y || IN == GIN_EMBED_SELECT) {
     for (int bb = wave; bb < bg; bb += 4) {  // one wave per row
       const int b = g0 + bb;
       const bool pre = prefetched && g0 == 0 && bb == wave;  // this row was prefetched before the weights
       float4 v[3];
-      if (IN == 0 || IN == 4) {
+      if (IN == GIN_LN || IN == GIN_LN_Y) {
         if (pre) {
           xrow_sum(xpre, v);
         } else {
-          XRow<IN == 4 ? 4 : 0, true> xr;
+          XRow<IN == GIN_LN_Y ? GIN_LN_Y : GIN_LN, true> xr;
           xrow_issue(a, b, lane, xr);
           xrow_sum(xr, v);
         }
@@ -454,7 +447,7 @@ __device__ __forceinline__ void gemv_stage_input(const GemvArgs& a, float* xs, f
       }
       wave_ln_to_lds(v, gam, xs + bb * K, lane);
     }
-  } else if (IN == 1) {
+  } else if (IN == GIN_H) {
     for (int e = tid * 4; e < bg * K; e += 256 * 4)
       *reinterpret_cast<float4*>(xs + e) = *reinterpret_cast<const float4*>(a.st.h + (size_t)g0 * K + e);
   } else {
@@ -538,48 +531,48 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
   constexpr int WROWS = 4 / KW;  // row groups per block
   __shared__ __attribute__((aligned(16))) float xs[BG * K];
   __shared__ float part[4][RPW][BG];
-  __shared__ float aux[IN == 2 ? BG * N_HEAD * NSPLIT : 1];
-  __shared__ int4 ri_s[IN == 5 ? BG : 1];  // IN 5: the rows' new control records for the KV epilogue
+  __shared__ float aux[IN == GIN_MERGE ? BG * N_HEAD * NSPLIT : 1];
+  __shared__ int4 ri_s[IN == GIN_EMBED_SELECT ? BG : 1];  // GIN_EMBED_SELECT: the rows' new control records for the KV epilogue
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int rg = wave / KW, kp = wave % KW;
   const int row0 = (blockIdx.x * WROWS + rg) * RPW;
   // inputs of the first batch group first (vmcnt retires in issue order): the LayerNorm /
   // embedding math then overlaps the weight stream instead of waiting behind it
-  XRow<IN == 4 ? 4 : 0, true> xpre;
+  XRow<IN == GIN_LN_Y ? GIN_LN_Y : GIN_LN, true> xpre;
   int4 ripre = make_int4(-1, 0, 0, 0);
   const bool prefetched = wave < min(BG, a.B);
   // control record of this lane's epilogue row in the first batch group (bb = lane % BG): the
   // KV append needs (slot, pos); loading it here keeps it off the epilogue's critical path
   int4 riep = make_int4(-1, 0, 0, 0);
-  if (OUT == 0 && IN != 5) riep = a.st.rowinfo[min(lane % BG, a.B - 1)];
-  // residual epilogue (OUT 1): this lane's (row, batch row) of the first group is (row0 + lane / BG,
+  if (OUT == GOUT_QKV && IN != GIN_EMBED_SELECT) riep = a.st.rowinfo[min(lane % BG, a.B - 1)];
+  // residual epilogue (GOUT_RESID): this lane's (row, batch row) of the first group is (row0 + lane / BG,
   // lane % BG); its x element (and, for c_proj after a fused MLP, the pending accumulators) is
   // loaded now instead of behind the dot products
   float xep = 0.f;
   unsigned long long yep[YCOPIES];
-  if constexpr (OUT == 1) {
+  if constexpr (OUT == GOUT_RESID) {
     const int n = row0 + lane / BG, b = lane % BG;
     if (lane < RPW * BG && n < a.N && b < a.B) {
       xep = a.st.x[(size_t)b * D + n];
-      if (IN == 2 && a.yfx)
+      if (IN == GIN_MERGE && a.yfx)
 #pragma unroll
         for (int c = 0; c < YCOPIES; ++c) yep[c] = a.yfx[((size_t)b * YCOPIES + c) * D + n];
     }
   }
-  if ((IN == 0 || IN == 3 || IN == 4) && prefetched) {
-    if (IN == 0 || IN == 4) {
+  if ((IN == GIN_LN || IN == GIN_EMBED || IN == GIN_LN_Y) && prefetched) {
+    if (IN == GIN_LN || IN == GIN_LN_Y) {
       xrow_issue(a, wave, lane, xpre);
     } else {
       ripre = a.st.rowinfo[wave];
     }
   }
-  // IN 5 (deferred select, every row prefetched by its own wave): the previous step's lm_head
+  // GIN_EMBED_SELECT (deferred select, every row prefetched by its own wave): the previous step's lm_head
   // granules, the pending flag and the row's {step, next text id} come in the same round trip
   // as the control record
   LmGran lmg;
   int2 rxp = make_int2(0, 0);
   unsigned selpend = 0u;
-  if constexpr (IN == 5) {  // every wave, clamped row (no loads under a branch); used by waves < B
+  if constexpr (IN == GIN_EMBED_SELECT) {  // every wave, clamped row (no loads under a branch); used by waves < B
     const int rb = min(wave, a.B - 1);
     ripre = a.st.rowinfo[rb];
     rxp = a.st.rowx[rb];
@@ -587,7 +580,7 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
     lmg_issue(a.st, rb, lane, lmg);
   }
   float4 gam[3];  // LayerNorm gamma of the LN input modes, ahead of the weights
-  if constexpr (IN == 0 || IN == 3 || IN == 4 || IN == 5) {
+  if constexpr (IN == GIN_LN || IN == GIN_EMBED || IN == GIN_LN_Y || IN == GIN_EMBED_SELECT) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) gam[j] = *reinterpret_cast<const float4*>(a.ln_w + j * 256 + lane * 4);
   }
@@ -603,7 +596,7 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
       // are never stored
       wr[r][it] = WReg<TW>::load(W + (size_t)min(n, a.N - 1) * K + kp * KC + it * 256 + lane * 4);
   }
-  if constexpr (IN == 5) {
+  if constexpr (IN == GIN_EMBED_SELECT) {
     // commit the previous step's greedy select (argmax_commit's state advance; block 0 writes
     // the shadow records, attention layer 0 copies them back) and build this step's record. The
     // reduction and the record select run unconditionally so that the granule loads stay in the
@@ -691,23 +684,23 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
         if (bb >= bg || n >= a.N || lane != ((r * BG + bb) & 63)) continue;
         const float v = acc[r][bb];
         const int b = g0 + bb;
-        if (OUT == 0) {
+        if (OUT == GOUT_QKV) {
           if (n < D) {
             a.st.q[(size_t)b * D + n] = v;
           } else {
             const int c = (n - D) % D, which = (n - D) / D;
             const int head = c / HD, d = c - head * HD;
-            const int4 ri = IN == 5 ? ri_s[bb] : g0 == 0 ? riep : a.st.rowinfo[b];
+            const int4 ri = IN == GIN_EMBED_SELECT ? ri_s[bb] : g0 == 0 ? riep : a.st.rowinfo[b];
             const int s = ri.x, p = ri.y;
             if (s < 0) continue;
             const size_t idx =
                 kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, s, head, p) + d;
             store_kv(a, which, idx, v);
           }
-        } else if (OUT == 1) {
+        } else if (OUT == GOUT_RESID) {
           float* xp = a.st.x + (size_t)b * D + n;
           float t = g0 == 0 ? xep : *xp;
-          if (IN == 2 && a.yfx) {  // c_proj: fold the fused MLP's accumulators into x and clear them
+          if (IN == GIN_MERGE && a.yfx) {  // c_proj: fold the fused MLP's accumulators into x and clear them
             unsigned long long ys = 0;
 #pragma unroll
             for (int c = 0; c < YCOPIES; ++c) {
@@ -718,16 +711,16 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
             if (a.add_y) t += yfx_to_f(ys);
           }
           *xp = t + v;
-        } else if (OUT == 2) {
+        } else if (OUT == GOUT_GELU) {
           a.st.h[(size_t)b * DFF + n] = gelu_tanh(v);
         } else {
           a.dst[(size_t)b * a.N + n] = v;
-          if (OUT == 9) part[wave][r][bb] = v;
+          if (OUT == GOUT_LOGITS_GRAN) part[wave][r][bb] = v;
         }
       }
     }
   }
-  if constexpr (OUT == 9) {
+  if constexpr (OUT == GOUT_LOGITS_GRAN) {
     // deferred select: this block's top1/top2 per row as one granule (plain store; the next
     // kernel boundary publishes it) and the pending flag
     __syncthreads();
@@ -752,7 +745,7 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
 // GEMV / batched-GEMM epilogue store of output n of batch row b
 template <int OUT>
 __device__ __forceinline__ void gemv_store(const GemvArgs& a, int n, int b, float v) {
-  if (OUT == 0) {
+  if (OUT == GOUT_QKV) {
     if (n < D) {
       a.st.q[(size_t)b * D + n] = v;
     } else {
@@ -763,16 +756,16 @@ __device__ __forceinline__ void gemv_store(const GemvArgs& a, int n, int b, floa
       const size_t idx = kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, ri.x, head, ri.y) + d;
       store_kv(a, which, idx, v);
     }
-  } else if (OUT == 1) {
+  } else if (OUT == GOUT_RESID) {
     float* xp = a.st.x + (size_t)b * D + n;
     float t = *xp;
     if (a.yacc && a.add_y)  // c_proj: fold the pending split-K partials of the previous mlp c_proj
 #pragma unroll
       for (int c = 0; c < YCOPIES; ++c) t += a.yacc[((size_t)b * YCOPIES + c) * D + n];
     *xp = t + v;
-  } else if (OUT == 2) {
+  } else if (OUT == GOUT_GELU) {
     a.st.h[(size_t)b * DFF + n] = gelu_tanh(v);
-  } else if (OUT == 6) {  // split-K partial of mlp c_proj (K slice blockIdx.y) -> pending copy
+  } else if (OUT == GOUT_SPLITK) {  // split-K partial of mlp c_proj (K slice blockIdx.y) -> pending copy
     a.yacc[((size_t)b * YCOPIES + blockIdx.y) * D + n] = v;
   } else {
     a.dst[(size_t)b * a.N + n] = v;
@@ -1057,7 +1050,7 @@ template <> struct KvPiece<fp8_t> {
 // V pieces (48 B bf16 each) load straight to registers, the score needs two quad shuffles, and
 // every wave keeps its own online-softmax state (m, l, o[24] per lane) so the loop has no
 // barrier. The 4 wave states are merged once at the end through LDS.
-// direct = 1 (batched path with one split per (row, head)): the normalised head output goes
+// direct (ATTN_*, ar_plan.h) = ATTN_XN (batched path with one split per (row, head)): the normalised head output goes
 // straight to the bf16 operand row xn, as the merge kernel would write it (o * (1 / l)), and the
 // merge kernel is skipped.
 // QKV (fp32 KV: the parity mode, 3 <= B <= 32): c_attn left its output as four K-slice partials
@@ -1216,7 +1209,7 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
   if (s < 0) {
     copy_tail();
     // an idle row's fp32 operand is 0, as the merge would give it
-    if (direct == 3 && sp == 0 && tid < HD) st.part_o[(size_t)(b * N_HEAD + head) * NSPLIT * HD + tid] = 0.f;
+    if (direct == ATTN_F32_ROWS && sp == 0 && tid < HD) st.part_o[(size_t)(b * N_HEAD + head) * NSPLIT * HD + tid] = 0.f;
     return;
   }
   const int t = ri.y + 1;
@@ -1406,12 +1399,12 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
       ov += f * ((wo_s[w][0][tid] + wo_s[w][1][tid]) + (wo_s[w][2][tid] + wo_s[w][3][tid]));
       lv += f * wl_s[w];
     }
-    if (direct == 3) {  // fp32 parity mode, one split: the normalised head output in split 0's slot
+    if (direct == ATTN_F32_ROWS) {  // fp32 parity mode, one split: the normalised head output in split 0's slot
       st.part_o[(size_t)(b * N_HEAD + head) * NSPLIT * HD + tid] = ov * (1.0f / lv);
       return;
     }
     if (direct) {
-      st.xn[direct == 2 ? xfrag(b, head * HD + tid, D) : (size_t)b * D + head * HD + tid] = f32_to_bf16(ov * (1.0f / lv));
+      st.xn[direct == ATTN_XN_PACKED ? xfrag(b, head * HD + tid, D) : (size_t)b * D + head * HD + tid] = f32_to_bf16(ov * (1.0f / lv));
       return;
     }
     st.part_o[((size_t)(b * N_HEAD + head) * NSPLIT + sp) * HD + tid] = ov;
@@ -1461,9 +1454,13 @@ __global__ __launch_bounds__(256) void ar_argmax_kernel(ArState st) {
 // ---------------------------------------------------------------------------------
 // Kernel-variant switches kept for cross-checks (lvx_set_option): each selects between two correct
 // implementations of the same step that tests/ compare (defaults are the measured-faster ones).
+// What a step runs under them is decided in one place, ar_plan_step (ar_plan.h).
 // option defer_select (default 1, Opts in lvx_internal.h): 1: greedy select deferred into the next
-//   step's first kernel (B <= 2: c_attn layer 0 reduces lm_head's granules; B >= 4: ar_embed_select);
-//   0: ar_argmax_kernel
+//   step's first kernel, in the form its path can run (ArSelect: B <= 2 GEMV: c_attn layer 0 reduces
+//   lm_head's granules, or ar_q0_gran_kernel with the q0 tables; bf16 4 <= B <= 32 with the tables:
+//   ar_q0_rows_kernel; else 4 <= B <= 8: the prologue of c_attn layer 0 reduces lm_head's granules;
+//   other batched B >= 4: ar_embed_select_kernel; B = 3 keeps ar_argmax_kernel); 2: as 1 without the
+//   prologue-granule form; 0: ar_argmax_kernel
 // option fuse_mlp (default 1, Opts in lvx_internal.h): bf16, B <= 2: c_fc + gelu + mlp c_proj in one
 //   kernel, its 192 blocks' c_proj partials added as 2^-32 fixed-point int64 (exact integer sums in any
 //   arrival order: reproducible); 0: two GEMV kernels (another summation order)
@@ -1473,12 +1470,12 @@ static void launch_gemv(const GemvArgs& a, hipStream_t s) {
   const int rows_per_block = (4 / KW) * RPW;
   dim3 grid((a.N + rows_per_block - 1) / rows_per_block);
   constexpr int BGMAX = (K == 768) ? 16 : 4;
-  if constexpr (OUT == 9 || IN == 5) {  // select variants: one batch group of <= 4 rows (launch_op checks)
+  if constexpr (OUT == GOUT_LOGITS_GRAN || IN == GIN_EMBED_SELECT) {  // select variants: one batch group of <= 4 rows (SEL_GRAN: B <= 2)
     if (a.B <= 1) hipLaunchKernelGGL((ar_gemv_kernel<TW, K, KW, RPW, 1, IN, OUT>), grid, dim3(256), 0, s, a);
     else if (a.B <= 2) hipLaunchKernelGGL((ar_gemv_kernel<TW, K, KW, RPW, 2, IN, OUT>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((ar_gemv_kernel<TW, K, KW, RPW, 4, IN, OUT>), grid, dim3(256), 0, s, a);
   } else {
-    if constexpr (IN == 2 && OUT == 1 && K == 768 && KW == 1) {
+    if constexpr (IN == GIN_MERGE && OUT == GOUT_RESID && K == 768 && KW == 1) {
       if (a.B == 1) {  // B = 1 c_proj: the split merge once per block, 16 splits
         hipLaunchKernelGGL((ar_cproj_b1_kernel<TW, RPW, NSPLIT>), grid, dim3(256), 0, s, a);
         return;
@@ -1509,12 +1506,6 @@ __device__ __forceinline__ uint2 pack4_bf16(float4 v) {
 // the LVX_YCS=4 build: B = 8 fp8 KV 94.8 / 95.1 -> 94.3 / 93.6 us per step, bf16 97.2 -> 96.7, B = 4
 // 90.9 -> 90.5; configs[4] 82.0k -> 82.7k). B > ln_max keeps 4 slices (YCOPIES) for the rows kernel.
 constexpr int YCS = LVX_YCS;
-constexpr int MFMA_BATCH_MIN = 3;  // smallest B on the batched MFMA path (measured B = 3: 117 vs 154 us, B = 2: 119 vs 114)
-// batched path: LayerNorm / embedding fused into the MFMA GEMM prologue for B <= this value
-// (measured: B = 8 147 vs 156 us/step; B = 32 slower, every block re-normalising 32 rows)
-// (runtime value: option "ln_max", for A/B of the two batched structures at small B)
-// option ln_max (default 8, Opts in lvx_internal.h):
-#define MFMA_LN_MAX (opts().ln_max)
 
 // ---------------------------------------------------------------------------------
 // Batched path v2 (bf16 weights, 4 < B <= 32): every per-row prologue runs ONCE per row into a
@@ -1560,10 +1551,9 @@ __device__ __forceinline__ void embed_row(const GemvArgs& a, int4 ri, int lane, 
 }
 
 
-// 0: LayerNorm(x)  4: LayerNorm(x + pending copies)  3: embedding (+ stores x) then LayerNorm
-// 5: as 4 with fp32 output rows in st.h ([B][768]; the batched fp32 parity mode's c_attn / lm_head
-// operand, ar_qkv_ksplit_f32_kernel / ar_f32b_kernel IN 6: h is free between mlp c_proj and the next
-// c_fc)  6: as 3 with the fp32 output rows of 5
+// MODE: RMODE_* (ar_plan.h). The fp32 output rows of the _F32 modes go to st.h ([B][768]; the batched
+// fp32 parity mode's c_attn / lm_head operand, ar_qkv_ksplit_f32_kernel / ar_f32b_kernel FIN_LN_ROWS:
+// h is free between mlp c_proj and the next c_fc)
 template <int MODE>
 __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_rows_kernel(GemvArgs a) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1574,13 +1564,13 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_rows_kernel(GemvArgs a
   float4 g[3], v[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) g[j] = *reinterpret_cast<const float4*>(a.ln_w + j * 256 + lane * 4);
-  if (MODE == 0 || MODE == 4 || MODE == 5) {
-    XRow<MODE == 5 ? 4 : MODE> r;
+  if (MODE == RMODE_LN || MODE == RMODE_LN_Y || MODE == RMODE_LN_Y_F32) {
+    XRow<MODE == RMODE_LN_Y_F32 ? GIN_LN_Y : MODE> r;
     xrow_issue(a, b, lane, r);
     __builtin_amdgcn_sched_barrier(0);  // gamma and the rows issued up front (the scheduler sank a
                                         // gamma load behind the variance: one more round trip)
     xrow_sum(r, v);
-    if (MODE == 4 || MODE == 5)  // fold the pending copies into x here (one wave owns the row): the next c_proj
+    if (MODE == RMODE_LN_Y || MODE == RMODE_LN_Y_F32)  // fold the pending copies into x here (one wave owns the row): the next c_proj
 #pragma unroll      // then adds its output to a final x instead of re-reading the copies
       for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = v[j];
   } else {
@@ -1591,7 +1581,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_rows_kernel(GemvArgs a
   }
   TS_MARK(1);
   wave_ln_regs(v, g);
-  if constexpr (MODE == 5 || MODE == 6) {
+  if constexpr (MODE == RMODE_LN_Y_F32 || MODE == RMODE_EMBED_F32) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.h + (size_t)b * D + j * 256 + lane * 4) = v[j];
     return;
@@ -1605,11 +1595,11 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_rows_kernel(GemvArgs a
   TS_SAVE(a.N == VOCAB ? 8 : 0, a.layer, blockIdx.x);
 }
 
-// Batched deferred select (defer_sel 2): the previous step's greedy select of row b (the
+// Batched deferred select (SEL_EMBED): the previous step's greedy select of row b (the
 // ar_argmax_kernel commit, streaming_server.py:342-347) and then the embedding + LayerNorm of the
-// token it picked (ar_rows_kernel<3>). Four waves split the 4096 logits (one round trip with the
+// token it picked (ar_rows_kernel<RMODE_EMBED>). Four waves split the 4096 logits (one round trip with the
 // row's control records), wave 0 commits and builds the operand row.
-// F32OUT (the batched fp32 parity mode): the LayerNorm'd row in fp32 into st.h (ar_rows_kernel<6>'s
+// F32OUT (the batched fp32 parity mode): the LayerNorm'd row in fp32 into st.h (ar_rows_kernel<RMODE_EMBED_F32>'s
 // output, read by ar_qkv_ksplit_f32_kernel)
 // (With bf16 weights and option l0q the select runs in ar_q0_rows_kernel instead, which also computes
 // layer 0's q / k / v from the q0 tables; round 6's first form of that, one block per row inside this
@@ -1688,10 +1678,10 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_embed_select_kernel(Ge
   TS_SAVE(7, 0, b);
 }
 
-// B <= 2 GEMV steps with the deferred granule select (defer_sel 1) and option l0q (bf16): layer 0's
+// B <= 2 GEMV steps with the deferred granule select (SEL_GRAN) and option l0q (bf16): layer 0's
 // c_attn from the q0 tables, as ar_embed_select_kernel<false, true> computes it, over 9 blocks of 256
 // outputs instead of one block per row: every block reduces the rows' lm_head granules (as the GEMV's
-// IN 5 prologue does; block 0 commits the select and leaves the new records in the shadow arrays that
+// GIN_EMBED_SELECT prologue does; block 0 commits the select and leaves the new records in the shadow arrays that
 // attention layer 0 copies back), loads its 256-column slices of Tt[t], Tp[p], G and Tc[c], and one
 // wave per row builds the embedding row for (den, mean, rstd) (block 0 also stores x). Round 6: the
 // single-block form cost the B = 1 step 6.6 us per launch (kernel trace) against 4.6-4.8 for its
@@ -1705,7 +1695,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_gran_kernel(GemvArg
   const int B = a.B;
   TS_DECL;
   TS_MARK(0);
-  // every wave (row clamped: no load under a branch), as the IN 5 prologue: the record, the
+  // every wave (row clamped: no load under a branch), as the GIN_EMBED_SELECT prologue: the record, the
   // {step, next text id}, the pending flag and the row's granules
   const int rb = min(wave, B - 1);
   const int4 ri = a.st.rowinfo[rb];
@@ -1798,7 +1788,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_gran_kernel(GemvArg
   TS_SAVE(7, 0, blockIdx.x);
 }
 
-// Batched steps (4 <= B <= 32, bf16, option l0q; defer_sel 4): the previous step's greedy select and
+// Batched steps (4 <= B <= 32, bf16, option l0q; SEL_Q0_ROWS): the previous step's greedy select and
 // layer 0's c_attn from the q0 tables (as ar_embed_select_kernel<false, true> computes them) over a grid
 // of 9 column slices x B rows: every block reduces its row's 4,096 logits (four waves, as
 // ar_embed_select_kernel), loads 256-column slices of Tt[t], Tp[p], G and Tc[c] and builds the
@@ -1947,22 +1937,22 @@ static void launch_merge_bf16(const ArState& st, int B, int nsm, hipStream_t s, 
   else hipLaunchKernelGGL(ar_merge_bf16_kernel<NSPLIT>, dim3(B), dim3(256), 0, s, st, nsm, xpk);
 }
 
-// OUT as gemv_store, plus OUT 5: h (bf16) = gelu_tanh(v) for the batched mlp c_proj. A block
-// covers K columns starting at blockIdx.y * K of rows of length KTOT (KTOT > K: split K, OUT 6).
-// XM 1 (c_fc): LayerNorm applied after the GEMM. The operand is the bf16 copy of x * ln_2.weight
-// the previous c_proj (OUT 7) left, multiplied as it is; the epilogue centres and scales:
+// OUT: M2OUT_*, XM: M2X_* (ar_plan.h). A block covers K columns starting at blockIdx.y * K of rows
+// of length KTOT (KTOT > K: split K, M2OUT_SPLITK).
+// M2X_LN_AFTER (c_fc): LayerNorm applied after the GEMM. The operand is the bf16 copy of x * ln_2.weight
+// the previous c_proj (M2OUT_RESID_STATS) left, multiplied as it is; the epilogue centres and scales:
 // LN2(x) . W^T = rstd * ((x * g) . W^T - mean * G[n]), G = ArWeights::fc_gsum, with (mean, rstd)
 // from the per-row statistics c_proj left in 48 column-block partials (mean, M2 over 16 columns
 // each, combined here with Chan's formula while the operands load): no rows kernel and no
 // per-element normalisation on the operand path (round 2: 4.1 -> ~2.7 us from entry to MFMA).
-// OUT 7 (c_proj): x += v, plus that bf16 copy (x * ln_2.weight) and this block's (mean, M2) of its
-// 16 columns.
+// M2OUT_RESID_STATS (c_proj): x += v, plus that bf16 copy (x * ln_2.weight) and this block's (mean, M2)
+// of its 16 columns.
 template <int K, int NT, int OUT, int KTOT = K, int XM = 0>
 __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
   constexpr int NW = K / 192;  // waves per block, each a 192-wide K slice (6 MFMA k-steps)
   __shared__ float red[NW][NT * 256];
-  __shared__ float xo[OUT == 7 ? 16 * NT * 16 : 1];
-  __shared__ float2 rs[XM == 1 ? NT * 16 : 1];
+  __shared__ float xo[OUT == M2OUT_RESID_STATS ? 16 * NT * 16 : 1];
+  __shared__ float2 rs[XM == M2X_LN_AFTER ? NT * 16 : 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // XCD-aligned tile order (a.xmap, 1-D grid): workgroups are dealt to the 8 XCDs round robin, so
   // with this order XCD x runs only the tiles of K slice x mod 4 (mlp c_proj: its L2 fetches only
@@ -1988,19 +1978,19 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
   const int B = a.B;
   TS_DECL;
   TS_MARK(0);
-  const bf16_t* __restrict__ X = XM == 1 ? a.st.xb : ((KTOT == 768) ? a.st.xn : a.st.hb);
+  const bf16_t* __restrict__ X = XM == M2X_LN_AFTER ? a.st.xb : ((KTOT == 768) ? a.st.xn : a.st.hb);
   const int k0 = by * K + wave * 192 + 8 * (lane >> 4);
   // epilogue operands first (a load in the epilogue is one more dependent round trip): thread tid
   // stores elements e = tid + k * NW * 64, all of batch row tid % (NT * 16) (NW * 64 is a multiple
-  // of NT * 16): its control record (OUT 0, KV append) or its x values (OUT 7, residual)
+  // of NT * 16): its control record (M2OUT_QKV, KV append) or its x values (M2OUT_RESID_STATS, residual)
   constexpr int EPT = (16 * NT * 16 + NW * 64 - 1) / (NW * 64);
   static_assert((NW * 64) % (NT * 16) == 0, "one batch row per thread in the epilogue");
   int4 ripre = make_int4(-1, 0, 0, 0);
-  float xpre[(OUT == 7 || OUT == 1) ? EPT : 1];
-  float gpre[(OUT == 7 || XM == 1) ? EPT : 1];  // OUT 7: ln_2.weight[n]; XM 1: G[n]
-  if constexpr (OUT == 0) ripre = a.st.rowinfo[min(r0 + tid % (NT * 16), B - 1)];
-  if constexpr (OUT == 1) {
-    // (B <= 8 c_proj) x and the MLP's pending copies up front, summed in gemv_store<1>'s order
+  float xpre[(OUT == M2OUT_RESID_STATS || OUT == M2OUT_RESID) ? EPT : 1];
+  float gpre[(OUT == M2OUT_RESID_STATS || XM == M2X_LN_AFTER) ? EPT : 1];  // M2OUT_RESID_STATS: ln_2.weight[n]; M2X_LN_AFTER: G[n]
+  if constexpr (OUT == M2OUT_QKV) ripre = a.st.rowinfo[min(r0 + tid % (NT * 16), B - 1)];
+  if constexpr (OUT == M2OUT_RESID) {
+    // (B <= 8 c_proj) x and the MLP's pending copies up front, summed in gemv_store<GOUT_RESID>'s order
     // (x + c0 + c1 + c2 + c3, then + v): round 3, they were loaded in the epilogue, one more
     // dependent round trip after the MFMAs. The copies are loaded whether or not they are folded
     // (add_y: layers >= 1): no load under a branch.
@@ -2021,20 +2011,20 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
       xpre[k] = t;
     }
   }
-  if constexpr (OUT == 7 || XM == 1) {
+  if constexpr (OUT == M2OUT_RESID_STATS || XM == M2X_LN_AFTER) {
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
       const int e = min(tid + k * NW * 64, 16 * NT * 16 - 1), r = e / (NT * 16), b = e - r * (NT * 16);
       const int n = min(n0 + r, a.N - 1);
-      if constexpr (OUT == 7) xpre[k] = a.st.x[(size_t)min(r0 + b, B - 1) * D + n];
-      gpre[k] = OUT == 7 ? a.ln_w[n] : a.gsum[n];
+      if constexpr (OUT == M2OUT_RESID_STATS) xpre[k] = a.st.x[(size_t)min(r0 + b, B - 1) * D + n];
+      gpre[k] = OUT == M2OUT_RESID_STATS ? a.ln_w[n] : a.gsum[n];
     }
   }
-  // XM 1: the row statistics partials first (vmcnt retires in issue order, so the Chan combine
+  // M2X_LN_AFTER: the row statistics partials first (vmcnt retires in issue order, so the Chan combine
   // waits for them alone while the weights and operand rows stream), by every thread (clamped
   // row: no load under a branch), used by the first NT * 64
-  float2 sp[XM == 1 ? 12 : 1];
-  if constexpr (XM == 1) {
+  float2 sp[XM == M2X_LN_AFTER ? 12 : 1];
+  if constexpr (XM == M2X_LN_AFTER) {
     const int rr = min(tid >> 2, NT * 16 - 1), q = tid & 3;
     const float2* xs = reinterpret_cast<const float2*>(a.st.xstat) + (size_t)min(r0 + rr, B - 1) * (D / 16) + q * 12;
 #pragma unroll
@@ -2061,7 +2051,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
   // every operand load in flight before the first MFMA (left to itself the scheduler interleaves
   // them with the MFMAs: ~7 KB in flight per wave instead of (6 + 6 NT) KB)
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (XM == 1) {  // (mean, rstd) per batch row into rs (read in the epilogue)
+  if constexpr (XM == M2X_LN_AFTER) {  // (mean, rstd) per batch row into rs (read in the epilogue)
     if (tid < NT * 16 * 4) {  // 4 lanes per row, 12 column blocks each (loaded above)
       const int rr = tid >> 2, q = tid & 3;
       const float2 (&p)[12] = sp;
@@ -2110,32 +2100,32 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += red[w][e];
-    if (OUT == 0 && n >= D) {  // K / V append at the row's (slot, pos), record prefetched
+    if (OUT == M2OUT_QKV && n >= D) {  // K / V append at the row's (slot, pos), record prefetched
       const int c = (n - D) % D, which = (n - D) / D;
       const int head = c / HD, d = c - head * HD;
       if (ripre.x < 0) continue;
       const size_t idx = kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, ripre.x, head, ripre.y) + d;
       store_kv(a, which, idx, v);
-    } else if (OUT == 5) {
-      if constexpr (XM == 1) {  // LayerNorm after the GEMM: rstd * (v - mean * G[n])
+    } else if (OUT == M2OUT_GELU_BF16) {
+      if constexpr (XM == M2X_LN_AFTER) {  // LayerNorm after the GEMM: rstd * (v - mean * G[n])
         const float2 st = rs[b - r0];
         v = (v - st.x * gpre[k]) * st.y;
       }
       a.st.hb[a.xpk ? xfrag(b, n, DFF) : (size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
-    } else if (OUT == 7) {
+    } else if (OUT == M2OUT_RESID_STATS) {
       const float xn = xpre[k] + v;
       a.st.x[(size_t)b * D + n] = xn;
       a.st.xb[a.xpk ? xfrag(b, n, D) : (size_t)b * D + n] = f32_to_bf16(xn * gpre[k]);
       xo[e] = xn;
-    } else if (OUT == 6) {  // split-K partial of mlp c_proj (K slice by) -> pending copy
+    } else if (OUT == M2OUT_SPLITK) {  // split-K partial of mlp c_proj (K slice by) -> pending copy
       a.yacc[((size_t)b * (KTOT / K) + by) * D + n] = v;
-    } else if (OUT == 1) {  // x (+ the folded copies, prefetched) + v
+    } else if (OUT == M2OUT_RESID) {  // x (+ the folded copies, prefetched) + v
       a.st.x[(size_t)b * D + n] = xpre[k] + v;
     } else {
       gemv_store<OUT>(a, n, b, v);
     }
   }
-  if constexpr (OUT == 7) {  // (mean, M2) of this block's 16 columns for every batch row
+  if constexpr (OUT == M2OUT_RESID_STATS) {  // (mean, M2) of this block's 16 columns for every batch row
     __syncthreads();
     if (tid < NT * 16 && r0 + tid < B) {
       float mean = 0.f;
@@ -2151,7 +2141,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
       reinterpret_cast<float2*>(a.st.xstat)[(size_t)(r0 + tid) * (D / 16) + bx] = make_float2(mean, m2);
     }
   }
-  TS_SAVE(OUT == 0 ? 1 : OUT == 7 ? 3 : OUT == 5 ? 4 : OUT == 6 ? 5 : 6, a.layer, blockIdx.x + gridDim.x * blockIdx.y);
+  TS_SAVE(OUT == M2OUT_QKV ? 1 : OUT == M2OUT_RESID_STATS ? 3 : OUT == M2OUT_GELU_BF16 ? 4 : OUT == M2OUT_SPLITK ? 5 : 6, a.layer, blockIdx.x + gridDim.x * blockIdx.y);
 }
 
 // measured alternatives to the batched v2 layout (round 1/2, us/step at B = 32, t = 256-512), removed:
@@ -2200,41 +2190,42 @@ static void launch_mproj_split(const GemvArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((ar_mfma2_kernel<768, 4, OUT, DFF>), grid, block, 0, s, b);
 }
 
-// Batched GEMM with the per-row prologue fused (K = 768; small B): every block builds the
-// LayerNorm (MODE 0), LayerNorm of x + pending copies (MODE 4) or embedding + LayerNorm (MODE 3;
-// block 0 also stores x) of all B rows into
+// Batched GEMM with the per-row prologue fused (K = 768; small B; OUT: MLOUT_*, MODE: MLMODE_*,
+// ar_plan.h): every block builds the LayerNorm (MLMODE_LN), LayerNorm of x + pending copies
+// (MLMODE_LN_Y) or embedding + LayerNorm (MLMODE_EMBED; block 0 also stores x) of all B rows into
 // an LDS bf16 tile, then runs the MFMA 16 x (NT*16) tile of its 16 weight rows from it. The rows
 // are recomputed by every block (B x 3 KB of x from L2) instead of paying a separate rows kernel
 // and its launch boundary; the weight fragments are in flight while the rows are normalised.
-// MODE 7 (c_attn layer 0 of the deferred select at 4 <= B <= 8, defer_sel 3): MODE 3 after committing
-// the previous step's greedy select from lm_head's granules (block 0 writes the state and the shadow
-// records, attention layer 0 copies them back, as the B <= 2 GEMV step's IN 5); every block builds the
-// rows from the new records, which the KV append of the epilogue uses too. OUT 3 with defer_sel 3:
-// the block's top-1 / top-2 per row as one granule, the pending flag set by block 0.
+// MLMODE_EMBED_SELECT (c_attn layer 0 of the deferred select at 4 <= B <= 8, SEL_LN_GRAN): MLMODE_EMBED
+// after committing the previous step's greedy select from lm_head's granules (block 0 writes the state
+// and the shadow records, attention layer 0 copies them back, as the B <= 2 GEMV step's
+// GIN_EMBED_SELECT); every block builds the rows from the new records, which the KV append of the
+// epilogue uses too. MLOUT_LOGITS with SEL_LN_GRAN: the block's top-1 / top-2 per row as one granule,
+// the pending flag set by block 0.
 template <int NT, int OUT, int MODE>
 __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
   constexpr int K = 768, NW = 4, R = NT * 16, RW = R / NW;  // rows per wave
   constexpr int LDX = K + 8;                                 // bf16 row stride (16-B pad)
-  static_assert(MODE != 7 || (NT == 1 && OUT == 0), "the deferred select's c_attn: B <= 8");
-  constexpr int SR = MODE == 7 ? LM8_ROWS / NW : 1;          // rows per wave that can be live (B <= 8)
+  static_assert(MODE != MLMODE_EMBED_SELECT || (NT == 1 && OUT == MLOUT_QKV), "the deferred select's c_attn: B <= 8");
+  constexpr int SR = MODE == MLMODE_EMBED_SELECT ? LM8_ROWS / NW : 1;          // rows per wave that can be live (B <= 8)
   __shared__ __attribute__((aligned(16))) bf16_t xs[R * LDX];
   __shared__ float red[NW][NT * 256];
-  __shared__ float lgs[OUT == 3 && NT == 1 ? 16 * 17 : 1];
-  __shared__ int4 ri_s[MODE == 7 ? LM8_ROWS : 1];
+  __shared__ float lgs[OUT == MLOUT_LOGITS && NT == 1 ? 16 * 17 : 1];
+  __shared__ int4 ri_s[MODE == MLMODE_EMBED_SELECT ? LM8_ROWS : 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int n0 = blockIdx.x * 16;
   const int B = a.B;
   // 1. row inputs (x rows or control records) first, then the weight fragments
   // (clamped rows, unconditional loads: a load under a branch drains everything in flight; the
   // pending copies of the first YR rows come with them, the rest are loaded in step 2)
-  constexpr int YR = MODE == 4 ? (RW < 2 ? RW : 2) : 0;
+  constexpr int YR = MODE == MLMODE_LN_Y ? (RW < 2 ? RW : 2) : 0;
   float4 xv[RW][3], ya[YR > 0 ? YR : 1][YCS][3];
   int4 ri[RW];
-  // MODE 7: the select's inputs with the control records (clamped rows, unconditional loads)
+  // MLMODE_EMBED_SELECT: the select's inputs with the control records (clamped rows, unconditional loads)
   LmGran8 lmg[SR];
   int2 rxp[SR];
   unsigned selpend = 0u;
-  if constexpr (MODE == 7) {
+  if constexpr (MODE == MLMODE_EMBED_SELECT) {
     selpend = *a.st.selp;
 #pragma unroll
     for (int i = 0; i < SR; ++i) {
@@ -2246,10 +2237,10 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
 #pragma unroll
   for (int i = 0; i < RW; ++i) {
     const int b = min(wave + NW * i, B - 1);
-    if (MODE == 0 || MODE == 4) {
+    if (MODE == MLMODE_LN || MODE == MLMODE_LN_Y) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) xv[i][j] = *reinterpret_cast<const float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4);
-    } else if (MODE != 7 || i < SR) {
+    } else if (MODE != MLMODE_EMBED_SELECT || i < SR) {
       ri[i] = a.st.rowinfo[b];
     }
     if (i < YR)
@@ -2269,8 +2260,8 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
   for (int kk = 0; kk < 6; ++kk)  // fragment-packed weights (a.Wf): 6 contiguous KB per wave
     wf[kk] = *reinterpret_cast<const uint4*>(
         reinterpret_cast<const bf16_t*>(a.Wf) + (((size_t)(n0 >> 4) * (K / 32) + wave * 6 + kk) * 64 + lane) * 8);
-  if constexpr (MODE == 7) {
-    // commit the previous step's select (ar_embed_select_kernel's argmax_commit, B <= 2 IN 5's shadow
+  if constexpr (MODE == MLMODE_EMBED_SELECT) {
+    // commit the previous step's select (ar_embed_select_kernel's argmax_commit, B <= 2 GIN_EMBED_SELECT's shadow
     // records); reduction and record select unconditional so that the granule loads stay up front
 #pragma unroll
     for (int i = 0; i < SR; ++i) {
@@ -2303,13 +2294,13 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
   for (int i = 0; i < RW; ++i) {
     const int b = wave + NW * i;
     uint2* dst = reinterpret_cast<uint2*>(xs + b * LDX);
-    if (b < B && (MODE != 7 || i < SR)) {
-      if (MODE == 3 || MODE == 7) {
+    if (b < B && (MODE != MLMODE_EMBED_SELECT || i < SR)) {
+      if (MODE == MLMODE_EMBED || MODE == MLMODE_EMBED_SELECT) {
         embed_row(a, ri[i], lane, xv[i]);
         if (blockIdx.x == 0)
 #pragma unroll
           for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = xv[i][j];
-      } else if (MODE == 4) {  // + the pending split-K copies of the previous mlp c_proj
+      } else if (MODE == MLMODE_LN_Y) {  // + the pending split-K copies of the previous mlp c_proj
 #pragma unroll
         for (int c = 0; c < YCS; ++c)
 #pragma unroll
@@ -2351,8 +2342,8 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += red[w][e];
-    if constexpr (OUT == 3 && NT == 1) lgs[r * 17 + b] = v;
-    if constexpr (MODE == 7) {  // c_attn's store with this step's new record (gemv_store<0> reads rowinfo)
+    if constexpr (OUT == MLOUT_LOGITS && NT == 1) lgs[r * 17 + b] = v;
+    if constexpr (MODE == MLMODE_EMBED_SELECT) {  // c_attn's store with this step's new record (gemv_store<GOUT_QKV> reads rowinfo)
       if (n < D) {
         a.st.q[(size_t)b * D + n] = v;
       } else {
@@ -2361,14 +2352,14 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
         const int4 rr = ri_s[b];
         if (rr.x >= 0) store_kv(a, which, kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, rr.x, head, rr.y) + d, v);
       }
-    } else if (OUT == 5) {
+    } else if (OUT == MLOUT_GELU_BF16) {
       a.st.hb[(size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
     } else {
       gemv_store<OUT>(a, n, b, v);
     }
   }
-  if constexpr (OUT == 3 && NT == 1) {
-    if (a.defer_sel == 3) {  // (kernel argument: uniform) this block's granule per row, pending flag
+  if constexpr (OUT == MLOUT_LOGITS && NT == 1) {
+    if (a.defer_sel == SEL_LN_GRAN) {  // (kernel argument: uniform) this block's granule per row, pending flag
       // raw barrier after the LDS writes: __syncthreads() would also wait for the logits stores
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -2388,7 +2379,7 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
 template <int OUT, int MODE>
 static void launch_mfma_ln(const GemvArgs& a, hipStream_t s) {
   dim3 grid((a.N + 15) / 16), block(256);
-  if constexpr (MODE == 7) {  // (B <= 8 by defer_select_ln)
+  if constexpr (MODE == MLMODE_EMBED_SELECT) {  // (B <= LM8_ROWS: SEL_LN_GRAN, ar_plan_select)
     hipLaunchKernelGGL((ar_mfma_ln_kernel<1, OUT, MODE>), grid, block, 0, s, a);
   } else {
     if (a.B <= 16) hipLaunchKernelGGL((ar_mfma_ln_kernel<1, OUT, MODE>), grid, block, 0, s, a);
@@ -2412,7 +2403,7 @@ static void launch_mfma_ln(const GemvArgs& a, hipStream_t s) {
 template <int K, int NT, int IN, int OUT>
 __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
   constexpr int NW = K / 192, R = NT * 16, NTH = NW * 64;
-  constexpr bool STAGE = IN != 1;  // operand tile staged in LDS (K == 768)
+  constexpr bool STAGE = IN != BIN_ROWS;  // operand tile staged in LDS (K == 768)
   static_assert(!STAGE || K == 768, "the LDS operand tile holds K = 768 rows");
   constexpr int LDX = D + 8;  // bf16 row stride of the tile (16-B pad)
   __shared__ __attribute__((aligned(16))) bf16_t xs[STAGE ? R * LDX : 8];
@@ -2421,11 +2412,11 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
   const int n0 = blockIdx.x * 16, r0 = blockIdx.y * R;
   const int B = a.B;
   const bf16_t* __restrict__ W = reinterpret_cast<const bf16_t*>(a.W);
-  const bf16_t* __restrict__ X = K == D ? a.st.xn : a.st.hb;  // IN 1 operand rows
+  const bf16_t* __restrict__ X = K == D ? a.st.xn : a.st.hb;  // BIN_ROWS operand rows
   const int wrow = min(n0 + (lane & 15), a.N - 1);
   const int k0 = wave * 192 + 8 * (lane >> 4);
   uint4 wf[6];
-  if constexpr (IN == 0 || IN == 3) {
+  if constexpr (IN == BIN_LN || IN == BIN_EMBED) {
     constexpr int RPW = R / NW;  // rows per wave, normalised 4 at a time
     float4 g[3];
 #pragma unroll
@@ -2435,7 +2426,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {  // clamped row, unconditional loads (rows past B are not stored)
         const int b = min(r0 + wave * RPW + gi + i, B - 1);
-        if (IN == 0) {
+        if (IN == BIN_LN) {
 #pragma unroll
           for (int j = 0; j < 3; ++j) xv[i][j] = *reinterpret_cast<const float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4);
         } else {
@@ -2454,7 +2445,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
         const int rr = wave * RPW + gi + i, b = r0 + rr;
         uint2* dst = reinterpret_cast<uint2*>(xs + rr * LDX);
         if (b < B) {
-          if (IN == 3) {
+          if (IN == BIN_EMBED) {
             embed_row(a, ri[i], lane, xv[i]);
             if (blockIdx.x == 0)
 #pragma unroll
@@ -2469,7 +2460,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
         }
       }
     }
-  } else {  // IN 1: bf16 operand rows (hb, or xn of the separate merge kernel) straight from global
+  } else {  // BIN_ROWS: bf16 operand rows (hb, or xn of the separate merge kernel) straight from global
 #pragma unroll
     for (int kk = 0; kk < 6; ++kk) wf[kk] = *reinterpret_cast<const uint4*>(W + (size_t)wrow * K + k0 + kk * 32);
   }
@@ -2504,8 +2495,8 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += red[w][e];
-    if (OUT == 5) a.st.hb[(size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
-    else if (OUT == 1) a.st.x[(size_t)b * D + n] += v;
+    if (OUT == BOUT_GELU_BF16) a.st.hb[(size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
+    else if (OUT == BOUT_RESID) a.st.x[(size_t)b * D + n] += v;
     else gemv_store<OUT>(a, n, b, v);
   }
 }
@@ -2523,9 +2514,9 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
 // are summed through LDS in wave order: deterministic, and a row's result never depends on its batch
 // position (an MFMA column's dot product uses only that column's data).
 // ---------------------------------------------------------------------------------
-// KTOT > K (mlp c_proj, OUT 6): the K = 3072 reduction split over blockIdx.z into KTOT / K slices of
+// KTOT > K (mlp c_proj, FOUT_SPLITK): the K = 3072 reduction split over blockIdx.z into KTOT / K slices of
 // 768, each slice's partial stored to its pending copy (st.yacc), folded into x by the rows kernel
-// (ar_rows_kernel<5>) that normalises c_attn's / lm_head's operand rows (IN 6): 4x the blocks, a
+// (ar_rows_kernel<RMODE_LN_Y_F32>) that normalises c_attn's / lm_head's operand rows (FIN_LN_ROWS): 4x the blocks, a
 // quarter of the bytes per block.
 // CT column tiles per block (CT x K / 192 waves sharing the block's operand tile): CT = 2 halves the
 // blocks of the wide ops (c_fc, lm_head, the mlp c_proj slices) so that 192-256 blocks cover the CUs
@@ -2533,39 +2524,39 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
 template <int K, int NT, int IN, int OUT, int KTOT = K, int CT = 1>
 __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) {
   constexpr int NWK = K / 192, NW = NWK * CT, R = NT * 16, NTH = NW * 64;
-  constexpr bool STAGE = IN != 1 || CT > 1;  // K == 768: the operand tile in LDS (shared by the column tiles)
-  static_assert(KTOT == K || (IN == 1 && OUT == 6 && KTOT == YCOPIES * K), "split K: mlp c_proj into the pending copies");
-  // IN 4 (c_proj after a one-split attention, direct == 3): the normalised rows are split 0 of part_o
-  // IN 6 (c_attn / lm_head after ar_rows_kernel<5>): the LayerNorm'd fp32 rows in st.h
+  constexpr bool STAGE = IN != FIN_H || CT > 1;  // K == 768: the operand tile in LDS (shared by the column tiles)
+  static_assert(KTOT == K || (IN == FIN_H && OUT == FOUT_SPLITK && KTOT == YCOPIES * K), "split K: mlp c_proj into the pending copies");
+  // FIN_ATTN_ROWS (c_proj after a one-split attention, ATTN_F32_ROWS): the normalised rows are split 0 of part_o
+  // FIN_LN_ROWS (c_attn / lm_head after ar_rows_kernel<RMODE_LN_Y_F32>): the LayerNorm'd fp32 rows in st.h
   static_assert(!STAGE || K == 768, "the LDS operand tile holds K = 768 rows");
   constexpr int LDX = D + 4;  // fp32 row stride: 16 rows x 4 banks apart, conflict-free 16-B reads
   __shared__ __attribute__((aligned(16))) float xs[STAGE ? R * LDX : 4];
   __shared__ float red[NW][16 * R];
-  __shared__ float cf_s[IN == 2 ? R * N_HEAD * NSPLIT : 1];
+  __shared__ float cf_s[IN == FIN_MERGE ? R * N_HEAD * NSPLIT : 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int kw = wave % NWK;  // the wave's 192-wide K slice; wave / NWK its column tile
   const int nb = blockIdx.x * CT * 16, r0 = blockIdx.y * R, ks = KTOT > K ? blockIdx.z : 0;
   const int n0 = min(nb + (wave / NWK) * 16, a.N - 16);  // (a tile past N: the last one's weights, never stored)
   const int B = a.B;
-  // weights (fragment-packed, the wave's 12 contiguous KB), issued first for IN 1 / IN 2; behind the
+  // weights (fragment-packed, the wave's 12 contiguous KB), issued first for FIN_H / FIN_MERGE; behind the
   // first row inputs for the LayerNorm modes (their statistics then overlap the weight stream)
   const float4* wsrc = reinterpret_cast<const float4*>(a.Wf) + ((size_t)(n0 >> 4) * (KTOT / 16) + ks * (K / 16) + kw * 12) * 64 + lane;
   float4 wf[12];
-  if constexpr (IN == 1 || IN == 2 || IN == 4 || IN == 6) {
+  if constexpr (IN == FIN_H || IN == FIN_MERGE || IN == FIN_ATTN_ROWS || IN == FIN_LN_ROWS) {
 #pragma unroll
     for (int j = 0; j < 12; ++j) wf[j] = wsrc[j * 64];
     // all 12 in flight before anything else (left to itself the scheduler interleaved each load with
     // the MFMA that uses it: one memory latency per k group)
     __builtin_amdgcn_sched_barrier(0);
   }
-  if constexpr (IN == 0 || IN == 3) {
+  if constexpr (IN == FIN_LN || IN == FIN_EMBED) {
     constexpr int RPW = R / NW;  // rows per wave (4 or 8), all inputs in flight at once
     float4 xv[RPW][3];
     int4 ri[RPW];
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
       const int b = min(r0 + wave * RPW + i, B - 1);  // clamped: no load under a branch
-      if (IN == 0) {
+      if (IN == FIN_LN) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) xv[i][j] = *reinterpret_cast<const float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4);
       } else {
@@ -2584,7 +2575,7 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
       const int rr = wave * RPW + i, b = r0 + rr;
       float* dst = xs + rr * LDX;
       if (b < B) {
-        if (IN == 3) {
+        if (IN == FIN_EMBED) {
           embed_row(a, ri[i], lane, xv[i]);
           if (blockIdx.x == 0)
 #pragma unroll
@@ -2598,8 +2589,8 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
         for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(dst + j * 256 + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
-  } else if constexpr (IN == 2) {
-    // split-KV merge (as gemv_stage_input IN 2): coefficients per (row, head, split), then every
+  } else if constexpr (IN == FIN_MERGE) {
+    // split-KV merge (as gemv_stage_input GIN_MERGE): coefficients per (row, head, split), then every
     // element sums the partials of the nsm splits the attention ran at this B (attn_ns_max). The
     // splits past nsm have coefficient 0 (part_o is zeroed at allocation, finite): leaving them out
     // of the sum changes no bit, and at B = 32 (one split) it cuts the block's partial reads 16-fold
@@ -2652,7 +2643,7 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
     else if (nsm == 4) merge(std::integral_constant<int, 4>{});
     else if (nsm == 8) merge(std::integral_constant<int, 8>{});
     else merge(std::integral_constant<int, NSPLIT>{});
-  } else if constexpr (IN == 4) {
+  } else if constexpr (IN == FIN_ATTN_ROWS) {
     // one round trip: the rows as the attention normalised them (the merge of one split: the same
     // product o * (1 / l), the same bits), 16 B per load, all in flight (round 3: the 4-B loads of a
     // strided loop were issued a few at a time: c_proj 12.4 us at B = 32)
@@ -2670,8 +2661,8 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
       const int e = (tid + i * NTH) * 4, bb = e / D, c = e - bb * D;
       *reinterpret_cast<float4*>(xs + bb * LDX + c) = rv[i];
     }
-  } else if constexpr (IN == 6 || (IN == 1 && STAGE)) {
-    // the rows kernel's LayerNorm'd rows (IN 6), or the K slice of the h rows (IN 1, two column
+  } else if constexpr (IN == FIN_LN_ROWS || (IN == FIN_H && STAGE)) {
+    // the rows kernel's LayerNorm'd rows (FIN_LN_ROWS), or the K slice of the h rows (FIN_H, two column
     // tiles), 16 B per thread and load, all in flight (padded rows: row B-1, never stored)
     constexpr int NL = R * D / 4 / NTH;
     static_assert(R * D / 4 % NTH == 0, "whole float4 loads per thread");
@@ -2679,7 +2670,7 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int e = (tid + i * NTH) * 4, bb = e / D, c = e - bb * D;
-      rv[i] = *reinterpret_cast<const float4*>(a.st.h + (size_t)min(r0 + bb, B - 1) * (IN == 1 ? KTOT : D) + (IN == 1 ? ks * K : 0) + c);
+      rv[i] = *reinterpret_cast<const float4*>(a.st.h + (size_t)min(r0 + bb, B - 1) * (IN == FIN_H ? KTOT : D) + (IN == FIN_H ? ks * K : 0) + c);
     }
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
@@ -2727,7 +2718,7 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NWK; ++w) v += red[ct * NWK + w][el];
-    if constexpr (OUT == 6) a.yacc[((size_t)b * YCOPIES + ks) * D + n] = v;  // K slice ks -> its pending copy
+    if constexpr (OUT == FOUT_SPLITK) a.yacc[((size_t)b * YCOPIES + ks) * D + n] = v;  // K slice ks -> its pending copy
     else gemv_store<OUT>(a, n, b, v);
   }
 }
@@ -2836,22 +2827,11 @@ static void launch_bt(const GemvArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((ar_bt_kernel<K, 1, IN, OUT>), grid, block, 0, s, a);
 }
 
-// Attention launch shape, measured (tools/step_sweep.py, us/step): 4 waves per block (8 waves,
-// 128-key tiles: B = 32 t = 256+ 153.7 vs 149.4; B = 64 211.1 vs 209.0), 2 KV tiles in flight per
-// wave (4: B = 32 157.9 vs 152.0, B = 64 234.2 vs 216.3), splits until ns x 8 heads x B <= 256
-// blocks (B = 32 at t = 256-511: 1024 blocks 164, 512 169, 256 = one split that writes xn
-// itself 155.5; B = 16: 138 / 136 / 131; B = 8: 144 / 133 / 130).
-constexpr int ATTN_BLOCKS = 256;
+// (the launch shape: attn_ns_max and the plan's attention fields, ar_plan.h)
 // (round 3, measured no faster: 8-wave blocks for the one-split bf16 attention at B = 32, 132.1 vs 130.3
 // us/step at t = 0..1,023: the tile loop streams the KV history at ~7 TB/s either way)
-static int attn_ns_max(int B) {  // enough splits to fill the chip, no more (early-exit blocks cost)
-  int ns = NSPLIT;
-  while (ns > 1 && ns * N_HEAD * B > ATTN_BLOCKS) ns >>= 1;
-  return ns;
-}
-
 static void launch_attn(const ArState& st, int kvdtype, int B, int l, hipStream_t s, int ns_max = NSPLIT,
-                        int direct = 0, int selcopy = 0, bool qkv = false, bool nw8 = false) {
+                        int direct = ATTN_PARTIALS, int selcopy = 0, bool qkv = false, bool nw8 = false) {
   dim3 grid(ns_max, N_HEAD, B);
   // (round 4, measured slower: 16 waves and 256-key tiles for the one-split blocks at B <= 8, B = 8
   // t = 384-639 fp8 KV 103.9 vs 98.3 us/step, bf16 KV 109.6 vs 100.1)
@@ -2921,265 +2901,200 @@ void ar_launch_q0_tables(const ArWeights& w, int max_pos, float* text, float* co
 }
 
 // one op of the decode step, with the B-dependent kernel choice (shared by the step and the probes)
-// op: 0 c_attn (layer 0: + embedding) 1 attention 2 c_proj (+ split merge) 3 c_fc 4 mlp c_proj 5 lm_head
-template <typename TW>
-static bool use_mfma(int B) {
-  return sizeof(TW) == 2 && B >= MFMA_BATCH_MIN && B <= 64;
-}
-template <typename TW>
-static bool use_bt(int B) {
-  return use_mfma<TW>(B) && opts().bt && (B > 32 || opts().bt == 2);
-}
+// The kernel choice is the plan's (ar_plan.h: ArStepPlan, the OP_ / select / mode-code names); only the
+// per-B template choice is left to the launch_* helpers.
 
 // batched path v3: one kernel per op (plus the attention), final x rows at every boundary
-static void launch_op_bt(int op, GemvArgs& a, const ArWeights& w, int l, int kvdtype, int B, hipStream_t s) {
-  const int nsm = attn_ns_max(B);
+static void launch_op_bt(int op, GemvArgs& a, const ArWeights& w, int l, const ArStepPlan& p, hipStream_t s) {
   a.layer = l;
   a.yacc = nullptr;
   a.add_y = 0;
   switch (op) {
-    case 0:
+    case OP_QKV:
       a.W = w.w_attn[l]; a.N = 3 * D; a.ln_w = w.ln1[l];
-      if (l == 0 && a.defer_sel == 2) {  // embedding + the previous step's select, then c_attn
-        hipLaunchKernelGGL(ar_embed_select_kernel<>, dim3(B), dim3(256), 0, s, a);
-        launch_bt<768, 1, 0>(a, s);
+      if (p.sel != SEL_EMBED && p.sel != SEL_ARGMAX) ar_plan_bug(p, "v3 c_attn");
+      if (l == 0 && p.sel == SEL_EMBED) {  // embedding + the previous step's select, then c_attn
+        hipLaunchKernelGGL(ar_embed_select_kernel<>, dim3(p.B), dim3(256), 0, s, a);
+        launch_bt<768, BIN_ROWS, BOUT_QKV>(a, s);
       } else if (l == 0) {
-        launch_bt<768, 3, 0>(a, s);
+        launch_bt<768, BIN_EMBED, BOUT_QKV>(a, s);
       } else {
-        launch_bt<768, 0, 0>(a, s);
+        launch_bt<768, BIN_LN, BOUT_QKV>(a, s);
       }
       break;
-    case 1: launch_attn(a.st, kvdtype, B, l, s, nsm); break;
-    case 2:
+    case OP_ATTN: launch_attn(a.st, p.kv_dtype, p.B, l, s, p.nsplit); break;
+    case OP_CPROJ:
       a.W = w.w_aproj[l]; a.N = D;
-      launch_merge_bf16(a.st, B, nsm, s);
-      launch_bt<768, 1, 1>(a, s);
+      launch_merge_bf16(a.st, p.B, p.nsplit, s);
+      launch_bt<768, BIN_ROWS, BOUT_RESID>(a, s);
       break;
-    case 3: a.W = w.w_fc[l]; a.N = DFF; a.ln_w = w.ln2[l]; launch_bt<768, 0, 5>(a, s); break;
-    case 4: a.W = w.w_mproj[l]; a.N = D; launch_bt<3072, 1, 1>(a, s); break;
-    case 5: a.W = w.w_lm; a.N = VOCAB; a.ln_w = w.lnf; launch_bt<768, 0, 3>(a, s); break;
+    case OP_FC: a.W = w.w_fc[l]; a.N = DFF; a.ln_w = w.ln2[l]; launch_bt<768, BIN_LN, BOUT_GELU_BF16>(a, s); break;
+    case OP_MPROJ: a.W = w.w_mproj[l]; a.N = D; launch_bt<3072, BIN_ROWS, BOUT_RESID>(a, s); break;
+    case OP_LM_HEAD: a.W = w.w_lm; a.N = VOCAB; a.ln_w = w.lnf; launch_bt<768, BIN_LN, BOUT_LOGITS>(a, s); break;
   }
-}
-
-// deferred select: every row of the step is prefetched by its own wave of c_attn layer 0 (B <= 2,
-// one batch group) and lm_head runs LM_SEL_BLOCKS blocks of 8 rows
-template <typename TW>
-static bool defer_select(int B) {
-  static_assert(LM_SEL_BLOCKS <= LM_MAX_BLOCKS && LM_SEL_BLOCKS % 64 == 0, "deferred select granules");
-  return opts().defer_select && B <= 2 && !use_mfma<TW>(B);
-}
-template <typename TW>
-static bool use_f32b(int B);
-static bool f32b_qsplit(int B);
-// 4 <= B <= 8 on the LayerNorm-prologue GEMMs (ar_mfma_ln_kernel): the select folded into c_attn layer
-// 0's prologue from lm_head's granules (defer_sel 3) instead of ar_embed_select_kernel + the c_attn
-// launch (option defer_select 2: the embedding + select kernel at these B too, the cross-check)
-template <typename TW>
-static bool defer_select_ln(int B) {
-  return opts().defer_select == 1 && use_mfma<TW>(B) && B >= 4 && B <= MFMA_LN_MAX && B <= LM8_ROWS;
-}
-template <typename TW>
-static bool defer_select_batched(int B) {
-  // us/step (tools/step_sweep.py, t = 256+) argmax kernel / deferred: B = 3: 112.9 / 114.7 (B = 3
-  // keeps the argmax kernel), B = 4: 106.0 / 104.9, 8: 120.7 / 118.3, 12: 123.0 / 120.5,
-  // 16: 128.4 / 125.5, 32: 150.3 / 147.3, 64: 213.4 / 206.8
-  // fp32 parity mode (round 3): with the K-split c_attn (its layer-0 rows kernel becomes
-  // ar_embed_select_kernel<true>); B = 32 t = 384-639: 213.9 -> 210.8 us/step
-  return opts().defer_select && ((use_mfma<TW>(B) && B >= 4) || use_bt<TW>(B) || (use_f32b<TW>(B) && B >= 4 && f32b_qsplit(B)));
-}
-
-// measured at B = 1 (round 1): 16 h rows per block (192 blocks) 76.7 us/step; 32 rows (96 blocks)
-// +6.8 us; 12 rows (256 blocks, one per CU) 77.4 us; 8 accumulator copies slower than 4
-template <typename TW>
-static bool fused_mlp(int B) {
-  return sizeof(TW) == 2 && opts().fuse_mlp && B <= 2 && !use_mfma<TW>(B);
-}
-
-template <typename TW>
-static bool use_f32b(int B) {
-  return sizeof(TW) == 4 && opts().f32b && B >= MFMA_BATCH_MIN && B <= 64;
 }
 
 // batched fp32 parity steps: five exact-fp32 MFMA kernels + the attention per layer; the split-KV
-// partials are merged in c_proj's prologue; the select is the argmax kernel after lm_head.
-// mlp c_proj runs as 4 K slices into the pending copies (384 blocks of 4 waves instead of 96 of 16:
-// the 16-wave blocks each loaded 392 KB on 96 CUs); the rows kernel before c_attn (layers >= 1) and
-// lm_head folds them into x and leaves the LayerNorm'd fp32 rows the GEMM stages (IN 6). Option exp
+// partials are merged in c_proj's prologue.
+// p.ksplit: mlp c_proj runs as 4 K slices into the pending copies (384 blocks of 4 waves instead of 96 of
+// 16: the 16-wave blocks each loaded 392 KB on 96 CUs); the rows kernel before c_attn (layers >= 1) and
+// lm_head folds them into x and leaves the LayerNorm'd fp32 rows the GEMM stages (FIN_LN_ROWS). Option exp
 // bit 512: the unsplit mlp c_proj with x final at every boundary and the LayerNorm in the GEMM prologue.
-static bool f32b_qsplit(int B) { return !(opts().exp & 512) && B <= 32 && !(opts().exp & 1024); }
-static void launch_op_f32b(int op, GemvArgs& a, const ArWeights& w, int l, int kvdtype, int B, hipStream_t s) {
-  const bool ksp = !(opts().exp & 512);
+// p.qsplit: c_attn split over K too (B <= 32), its partials summed by the attention; option exp bit 1024: one launch
+static void launch_op_f32b(int op, GemvArgs& a, const ArWeights& w, int l, const ArStepPlan& p, hipStream_t s) {
+  const int B = p.B;
   a.layer = l;
-  a.yacc = ksp ? a.st.yacc : nullptr;
+  a.yacc = p.ksplit ? a.st.yacc : nullptr;
   a.add_y = 0;
   a.xpk = 0;
-  // c_attn split over K too (B <= 32), its partials summed by the attention; option exp bit 1024: one launch
-  const bool qsp = f32b_qsplit(B);
   switch (op) {
-    case 0:
+    case OP_QKV:
       a.W = w.w_attn[l]; a.Wf = w.f_attn[l]; a.N = 3 * D; a.ln_w = w.ln1[l];
-      if (qsp) {  // rows kernel (layer 0: embedding; else x + the MLP copies) -> fp32 rows, then the K slices
-        if (l == 0 && a.defer_sel == 2) hipLaunchKernelGGL(ar_embed_select_kernel<true>, dim3(B), dim3(256), 0, s, a);
-        else if (l == 0) hipLaunchKernelGGL((ar_rows_kernel<6>), dim3(B), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((ar_rows_kernel<5>), dim3(B), dim3(64), 0, s, a);
+      if (p.sel != SEL_ARGMAX && !(p.sel == SEL_EMBED && p.qsplit)) ar_plan_bug(p, "f32b c_attn");
+      if (p.qsplit) {  // rows kernel (layer 0: embedding; else x + the MLP copies) -> fp32 rows, then the K slices
+        if (l == 0 && p.sel == SEL_EMBED) hipLaunchKernelGGL(ar_embed_select_kernel<true>, dim3(B), dim3(256), 0, s, a);
+        else if (l == 0) hipLaunchKernelGGL((ar_rows_kernel<RMODE_EMBED_F32>), dim3(B), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y_F32>), dim3(B), dim3(64), 0, s, a);
         if (B <= 16) hipLaunchKernelGGL((ar_qkv_ksplit_f32_kernel<1>), dim3(3 * D / 64, 4), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((ar_qkv_ksplit_f32_kernel<2>), dim3(3 * D / 64, 4), dim3(256), 0, s, a);
       } else if (l == 0) {
-        launch_f32b<768, 3, 0>(a, s);
-      } else if (ksp) {
-        hipLaunchKernelGGL((ar_rows_kernel<5>), dim3(B), dim3(64), 0, s, a);
-        launch_f32b<768, 6, 0>(a, s);
+        launch_f32b<768, FIN_EMBED, FOUT_QKV>(a, s);
+      } else if (p.ksplit) {
+        hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y_F32>), dim3(B), dim3(64), 0, s, a);
+        launch_f32b<768, FIN_LN_ROWS, FOUT_QKV>(a, s);
       } else {
-        launch_f32b<768, 0, 0>(a, s);
+        launch_f32b<768, FIN_LN, FOUT_QKV>(a, s);
       }
       break;
-    case 1: launch_attn(a.st, kvdtype, B, l, s, attn_ns_max(B), attn_ns_max(B) == 1 ? 3 : 0, 0, qsp); break;
-    case 2:
+    case OP_ATTN: launch_attn(a.st, p.kv_dtype, B, l, s, p.nsplit, p.attn_direct, 0, p.qsplit); break;
+    case OP_CPROJ:
       a.W = w.w_aproj[l]; a.Wf = w.f_aproj[l]; a.N = D;
-      if (attn_ns_max(B) == 1) launch_f32b<768, 4, 1>(a, s);  // the attention wrote the rows (direct 3)
-      else launch_f32b<768, 2, 1>(a, s);
+      if (p.attn_direct == ATTN_F32_ROWS) launch_f32b<768, FIN_ATTN_ROWS, FOUT_RESID>(a, s);
+      else launch_f32b<768, FIN_MERGE, FOUT_RESID>(a, s);
       break;
-    case 3: a.W = w.w_fc[l]; a.Wf = w.f_fc[l]; a.N = DFF; a.ln_w = w.ln2[l]; launch_f32b<768, 0, 2>(a, s); break;
-    case 4:
+    case OP_FC: a.W = w.w_fc[l]; a.Wf = w.f_fc[l]; a.N = DFF; a.ln_w = w.ln2[l]; launch_f32b<768, FIN_LN, FOUT_GELU>(a, s); break;
+    case OP_MPROJ:
       a.W = w.w_mproj[l]; a.Wf = w.f_mproj[l]; a.N = D;
-      if (ksp) launch_f32b<768, 1, 6, DFF>(a, s);
-      else launch_f32b<3072, 1, 1>(a, s);
+      if (p.ksplit) launch_f32b<768, FIN_H, FOUT_SPLITK, DFF>(a, s);
+      else launch_f32b<3072, FIN_H, FOUT_RESID>(a, s);
       break;
-    case 5:
+    case OP_LM_HEAD:
       a.W = w.w_lm; a.Wf = w.f_lm; a.N = VOCAB; a.ln_w = w.lnf;
-      if (ksp) {
-        hipLaunchKernelGGL((ar_rows_kernel<5>), dim3(B), dim3(64), 0, s, a);
-        launch_f32b<768, 6, 3>(a, s);
+      if (p.ksplit) {
+        hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y_F32>), dim3(B), dim3(64), 0, s, a);
+        launch_f32b<768, FIN_LN_ROWS, FOUT_LOGITS>(a, s);
       } else {
-        launch_f32b<768, 0, 3>(a, s);
+        launch_f32b<768, FIN_LN, FOUT_LOGITS>(a, s);
       }
       break;
   }
 }
 
-// returns false when the op has no kernel of its own at this B (mlp c_proj inside the fused MLP)
+// returns false when the op has no kernel of its own in this plan (mlp c_proj inside the fused MLP)
 template <typename TW>
-static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, int kvdtype, int B, hipStream_t s) {
-  if (use_f32b<TW>(B) && !a.emb_row) {
-    launch_op_f32b(op, a, w, l, kvdtype, B, s);
+static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArStepPlan& p, hipStream_t s) {
+  if (p.path == PATH_F32B || p.path == PATH_BT) {
+    if (p.path == PATH_F32B) launch_op_f32b(op, a, w, l, p, s);
+    else launch_op_bt(op, a, w, l, p, s);
     return true;
   }
-  if (use_bt<TW>(B) && !a.emb_row) {
-    launch_op_bt(op, a, w, l, kvdtype, B, s);
-    return true;
-  }
-  const bool mf = use_mfma<TW>(B);
-  const bool fm = fused_mlp<TW>(B);
-  // batched steps at B >= 9: one attention split per (row, head), the head output written straight
-  // into the bf16 operand row (no merge kernel). Round 3, tools/step_sweep.py (graph replay, us per
-  // step at t = 128 / 640): bf16 KV B = 12 104.3 / 113.0 -> 95.4 / 107.7, B = 16 107.1 / 126.7 ->
-  // 97.4 / 119.0; fp8 KV B = 12 103.2 / 110.3 -> 95.4 / 108.4, B = 16 104.2 / 111.5 -> 96.1 / 109.2.
-  // At B = 8 (64 blocks) one split loses at long histories (fp8 KV 102.4 -> 105.7 at t = 640 while
-  // 98.1 -> 92.5 at t = 128): B <= 8 keeps the split-KV attention + merge.
-  // 5 <= B <= 8: one split too, in 8-wave blocks (128-key tiles: twice the KV bytes in flight per
-  // block, 40-64 blocks); tools/step_sweep.py, fp8 KV, B = 8, t = 128 / 640 / 896: 98.0 / 102.3 / 104.2
-  // -> 92.6 / 102.8 / 106.5 us (bf16 KV 98.7 / 105.9 / 108.5 -> 95.1 / 105.3 / 108.8): ~1 % over a
-  // 1,024-token utterance; at B = 4 it loses (91.9 / 94.5 / 95.5 -> 87.6 / 96.3 / 100.8). fp8 KV (half the bytes per
-  // key) keeps the 8-wave blocks up to B = 16: B = 12 / 16, t = 128 / 640 / 896: 95.8 / 108.3 / 114.8 ->
-  // 97.0 / 105.5 / 109.6 and 95.8 / 109.6 / 115.5 -> 97.0 / 106.8 / 110.2 us; bf16 KV there loses
-  // (B = 16: 97.0 / 109.9 / 128.1 -> 100.8 / 112.5 / 130.5). (The switches restoring the older forms,
-  // option exp bits 32 / 64 / 128, were removed in round 6.)
-  const bool a8 = mf && B >= 5 && (B <= 8 || (kvdtype == LVX_DTYPE_FP8 && B <= 16));
-  const int nsm = mf ? ((B > 8 || a8) ? 1 : attn_ns_max(B)) : NSPLIT;
+  const int B = p.B;
+  const bool ln = p.path == PATH_MFMA_LN, mf = ln || p.path == PATH_MFMA_ROWS, fm = p.fused_mlp;
   // the MFMA GEMMs read the fragment-packed weight copies (a.Wf; round 6: the row-major reads of option
   // exp bit 2, bit-identical and slower, removed)
-  // fragment-packed operand rows on the v2 steps with the rows kernel (9 <= B <= 32)
-  a.xpk = (mf && B > MFMA_LN_MAX && B <= 32) ? 1 : 0;
+  a.xpk = p.xpk;
   a.layer = l;
   a.yacc = mf ? a.st.yacc : nullptr;
   a.yfx = fm ? a.st.yfx : nullptr;
   a.add_y = l > 0;
   switch (op) {
-    case 0:
+    case OP_QKV:
       a.W = w.w_attn[l]; a.Wf = w.f_attn[l]; a.N = 3 * D; a.ln_w = w.ln1[l];
-      if (mf && l == 0 && a.defer_sel == 3) {  // the previous step's select + embedding in c_attn's prologue
-        launch_mfma_ln<0, 7>(a, s);
-      } else if (mf && l == 0 && a.defer_sel == 4) {  // select + c_attn from the q0 tables, 9 slices per row
+      // layer 0: the embedding, after the previous step's select in the plan's form
+      if (!(p.sel == SEL_ARGMAX || (mf ? p.sel == SEL_EMBED || p.sel == SEL_Q0_ROWS || (ln && p.sel == SEL_LN_GRAN)
+                                       : p.sel == SEL_GRAN)))
+        ar_plan_bug(p, "c_attn");
+      if (l == 0 && p.sel == SEL_LN_GRAN) {  // select + embedding in c_attn's prologue
+        launch_mfma_ln<MLOUT_QKV, MLMODE_EMBED_SELECT>(a, s);
+      } else if (l == 0 && p.sel == SEL_Q0_ROWS) {  // select + c_attn from the q0 tables, 9 slices per row
         hipLaunchKernelGGL(ar_q0_rows_kernel, dim3(3 * D / 256, B), dim3(256), 0, s, a);
-      } else if (mf && l == 0 && a.defer_sel == 2) {  // embedding + the previous step's select, then c_attn
+      } else if (l == 0 && p.sel == SEL_EMBED) {  // embedding + select, then c_attn
         hipLaunchKernelGGL(ar_embed_select_kernel<>, dim3(B), dim3(256), 0, s, a);
-        launch_mfma2<768, 0>(a, s);
-      } else if (mf && B <= MFMA_LN_MAX) {
-        if (l == 0) launch_mfma_ln<0, 3>(a, s);
-        else launch_mfma_ln<0, 4>(a, s);
+        launch_mfma2<768, M2OUT_QKV>(a, s);
+      } else if (ln) {
+        if (l == 0) launch_mfma_ln<MLOUT_QKV, MLMODE_EMBED>(a, s);
+        else launch_mfma_ln<MLOUT_QKV, MLMODE_LN_Y>(a, s);
       } else if (mf) {  // rows kernel: LayerNorm (layer 0: of the embedding; else of x + the MLP copies)
-        if (l == 0) hipLaunchKernelGGL((ar_rows_kernel<3>), dim3(B), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((ar_rows_kernel<4>), dim3(B), dim3(64), 0, s, a);
-        launch_mfma2<768, 0>(a, s);
-      } else if (l == 0 && a.defer_sel == 1 && opts().l0q && a.q0_text) {  // B <= 2, the q0 tables
+        if (l == 0) hipLaunchKernelGGL((ar_rows_kernel<RMODE_EMBED>), dim3(B), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y>), dim3(B), dim3(64), 0, s, a);
+        launch_mfma2<768, M2OUT_QKV>(a, s);
+      } else if (l == 0 && p.q0_gran) {  // B <= 2: select + c_attn from the q0 tables
         hipLaunchKernelGGL(ar_q0_gran_kernel, dim3(3 * D / 256), dim3(256), 0, s, a);
-      } else if (l == 0 && a.defer_sel) {
-        launch_gemv<TW, 768, 1, 2, 5, 0>(a, s);  // + the previous step's select
+      } else if (l == 0 && p.sel == SEL_GRAN) {
+        launch_gemv<TW, 768, 1, 2, GIN_EMBED_SELECT, GOUT_QKV>(a, s);
       } else if (l == 0) {
-        launch_gemv<TW, 768, 1, 2, 3, 0>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_EMBED, GOUT_QKV>(a, s);
       } else if (fm) {
-        launch_gemv<TW, 768, 1, 2, 4, 0>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN_Y, GOUT_QKV>(a, s);
       } else {
-        launch_gemv<TW, 768, 1, 2, 0, 0>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_QKV>(a, s);
       }
       break;
-    case 1:
-      launch_attn(a.st, kvdtype, B, l, s, nsm, (mf && nsm == 1) ? 1 + a.xpk : 0,
-                  (a.defer_sel == 1 || a.defer_sel == 3 || a.defer_sel == 4) && l == 0,
-                  false, a8);
+    case OP_ATTN:
+      launch_attn(a.st, p.kv_dtype, B, l, s, p.nsplit, p.attn_direct, p.selcopy && l == 0, false, p.attn8);
       break;
-    case 2:
+    case OP_CPROJ:
       a.W = w.w_aproj[l]; a.Wf = w.f_aproj[l]; a.N = D;
       if (mf) {
-        if (B > MFMA_LN_MAX) a.add_y = 0;  // ar_rows_kernel<4> of this layer's c_attn folded them
-        if (nsm > 1) launch_merge_bf16(a.st, B, nsm, s, a.xpk);  // nsm == 1: the attention wrote xn itself
-        a.ln_w = w.ln2[l];  // OUT 7: the bf16 copy is x * ln_2.weight (c_fc's operand)
+        if (!ln) a.add_y = 0;  // ar_rows_kernel<RMODE_LN_Y> of this layer's c_attn folded them
+        if (p.nsplit > 1) launch_merge_bf16(a.st, B, p.nsplit, s, a.xpk);  // one split: the attention wrote xn itself
+        a.ln_w = w.ln2[l];  // M2OUT_RESID_STATS: the bf16 copy is x * ln_2.weight (c_fc's operand)
         // + bf16 x and row statistics for c_fc; 16-row batch tiles (B = 32: 96 blocks of 49 KB operands
         // instead of 48 of 74 KB: -3.4 us/step at t = 512-1,151)
-        if (B > MFMA_LN_MAX) launch_mfma2<768, 7>(a, s, true);
-        else launch_mfma2<768, 1>(a, s);
+        if (!ln) launch_mfma2<768, M2OUT_RESID_STATS>(a, s, true);
+        else launch_mfma2<768, M2OUT_RESID>(a, s);
       } else {
-        launch_gemv<TW, 768, 1, 1, 2, 1>(a, s);
+        launch_gemv<TW, 768, 1, 1, GIN_MERGE, GOUT_RESID>(a, s);
       }
       break;
-    case 3:
+    case OP_FC:
       a.W = w.w_fc[l]; a.Wf = w.f_fc[l]; a.N = DFF; a.ln_w = w.ln2[l];
       if (fm) {  // 16 h rows per block (192 blocks)
         const bf16_t* wfc = reinterpret_cast<const bf16_t*>(w.w_fc[l]);
         const bf16_t* wpk = reinterpret_cast<const bf16_t*>(w.w_mproj_pk[l]);
         if (B <= 1) hipLaunchKernelGGL((ar_mlp_fused_kernel<1, 16>), dim3(DFF / 16), dim3(256), 0, s, a, wfc, wpk);
         else hipLaunchKernelGGL((ar_mlp_fused_kernel<2, 16>), dim3(DFF / 16), dim3(256), 0, s, a, wfc, wpk);
-      } else if (mf && B <= MFMA_LN_MAX) {
-        launch_mfma_ln<5, 0>(a, s);
+      } else if (ln) {
+        launch_mfma_ln<MLOUT_GELU_BF16, MLMODE_LN>(a, s);
       } else if (mf) {
         a.gsum = w.fc_gsum[l];
-        launch_mfma2<768, 5, 1>(a, s);  // LayerNorm from c_proj's row statistics, after the GEMM
+        launch_mfma2<768, M2OUT_GELU_BF16, M2X_LN_AFTER>(a, s);  // LayerNorm from c_proj's row statistics, after the GEMM
       } else {
-        launch_gemv<TW, 768, 1, 2, 0, 2>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_GELU>(a, s);
       }
       break;
-    case 4:
+    case OP_MPROJ:
       a.W = w.w_mproj[l]; a.Wf = w.f_mproj[l]; a.N = D;
       if (fm) return false;
-      if (mf && YCS < YCOPIES && B <= MFMA_LN_MAX)  // YCS K slices of DFF / YCS into the YCS copies
-        hipLaunchKernelGGL((ar_mfma2_kernel<DFF / YCS, 1, 6, DFF>), dim3(D / 16, YCS), dim3(DFF / YCS / 192 * 64), 0, s, a);
-      else if (mf) launch_mproj_split<6>(a, s);
-      else launch_gemv<TW, 3072, 4, 2, 1, 1>(a, s);
+      if (ln && YCS < YCOPIES)  // YCS K slices of DFF / YCS into the YCS copies
+        hipLaunchKernelGGL((ar_mfma2_kernel<DFF / YCS, 1, M2OUT_SPLITK, DFF>), dim3(D / 16, YCS), dim3(DFF / YCS / 192 * 64), 0, s, a);
+      else if (mf) launch_mproj_split<M2OUT_SPLITK>(a, s);
+      else launch_gemv<TW, 3072, 4, 2, GIN_H, GOUT_RESID>(a, s);
       break;
-    case 5:
+    case OP_LM_HEAD:
       a.W = w.w_lm; a.Wf = w.f_lm; a.N = VOCAB; a.ln_w = w.lnf;
-      if (mf && B <= MFMA_LN_MAX) {
-        launch_mfma_ln<3, 4>(a, s);
+      if (ln) {
+        launch_mfma_ln<MLOUT_LOGITS, MLMODE_LN_Y>(a, s);
       } else if (mf) {
-        hipLaunchKernelGGL((ar_rows_kernel<4>), dim3(B), dim3(64), 0, s, a);
-        launch_mfma2<768, 3>(a, s);
-      } else if (a.defer_sel == 1) {
-        if (fm) launch_gemv<TW, 768, 1, 2, 4, 9>(a, s);
-        else launch_gemv<TW, 768, 1, 2, 0, 9>(a, s);
+        hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y>), dim3(B), dim3(64), 0, s, a);
+        launch_mfma2<768, M2OUT_LOGITS>(a, s);
+      } else if (p.sel == SEL_GRAN) {
+        if (fm) launch_gemv<TW, 768, 1, 2, GIN_LN_Y, GOUT_LOGITS_GRAN>(a, s);
+        else launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_LOGITS_GRAN>(a, s);
       } else if (fm) {
-        launch_gemv<TW, 768, 1, 2, 4, 3>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN_Y, GOUT_LOGITS>(a, s);
       } else {
-        launch_gemv<TW, 768, 1, 2, 0, 3>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_LOGITS>(a, s);
       }
       break;
   }
@@ -3204,60 +3119,48 @@ static GemvArgs make_args(const ArWeights& w, const ArState& st, int kvdtype, in
 }
 
 
-// returns whether the greedy select is deferred into the next step (no argmax kernel after lm_head)
 template <typename TW>
-static bool ar_layers(const ArWeights& w, const ArState& st, int kvdtype, int B, const float* emb_row, int slot,
-                      int pos, float* logits_dst, bool select, hipStream_t s) {
-  GemvArgs a = make_args<TW>(w, st, kvdtype, B, emb_row);
-  a.defer_sel = (select && !emb_row) ? (defer_select<TW>(B) ? 1 : defer_select_batched<TW>(B) ? (defer_select_ln<TW>(B) ? 3 : 2) : 0) : 0;
-  // bf16 with option l0q, 4 <= B <= 32: the previous step's select and layer 0's c_attn from the q0
-  // tables in one launch, ar_q0_rows_kernel (9 column slices per row; defer_sel 4): at B > 8 the c_attn
-  // GEMM launch goes, at 4 <= B <= 8 the c_attn-with-select launch reads table rows instead of weight
-  // slices (round 6, us per step at t = 384-639, each A/B on one box: the tables in one block per row
-  // took B = 32 -2.9, B = 8 -1.8 / -2.5 (fp8 / bf16 KV), B = 4 -1.4 (l0q_ab.txt, b8_l0q_ab.txt); the 9
-  // slices per row a further -1.1 / -1.7 / -1.7 (q0rows_ab.txt); the reference-agreement measures
-  // unchanged). B <= 2 keep their granule select with the tables in ar_q0_gran_kernel.
-  if ((a.defer_sel == 2 || a.defer_sel == 3) && use_mfma<TW>(B) && B <= 32 && opts().l0q && w.q0_text) a.defer_sel = 4;
+static void ar_layers(const ArWeights& w, const ArState& st, const ArStepPlan& p, const float* emb_row, int slot,
+                      int pos, float* logits_dst, hipStream_t s) {
+  static_assert(LM_SEL_BLOCKS <= LM_MAX_BLOCKS && LM_SEL_BLOCKS % 64 == 0, "deferred select granules");
+  GemvArgs a = make_args<TW>(w, st, p.kv_dtype, p.B, emb_row);
+  a.defer_sel = p.sel;
   if (emb_row) hipLaunchKernelGGL(ar_row_state_kernel, dim3(1), dim3(1), 0, s, st, slot, pos);
   for (int l = 0; l < N_LAYER; ++l)
-    for (int op = 0; op < 5; ++op) launch_op<TW>(op, a, w, l, kvdtype, B, s);
+    for (int op = OP_QKV; op < OP_LM_HEAD; ++op) launch_op<TW>(op, a, w, l, p, s);
   a.dst = logits_dst;
-  launch_op<TW>(5, a, w, N_LAYER - 1, kvdtype, B, s);
-  return a.defer_sel != 0;
+  launch_op<TW>(OP_LM_HEAD, a, w, N_LAYER - 1, p, s);
 }
 
-// Launch one op of the decode step `iters` times (bench.py times it with HIP events); layer 1.
-template <typename TW>
-static int ar_probe_impl(const ArWeights& w, const ArState& st, int kvdtype, int B, int which, int iters,
-                         hipStream_t s) {
-  if (which < 0 || which > 5) return -1;
-  if (which == 4 && fused_mlp<TW>(B)) return 1;  // no kernel of its own at this B
-  if (iters == 0) return 0;                       // validation only
-  GemvArgs a = make_args<TW>(w, st, kvdtype, B, nullptr);
+// Launch one op of the decode step `iters` times (bench.py times it with HIP events); layer 1,
+// without the select (the argmax-kernel form of the op). which: OP_*
+int ar_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int which, int iters,
+             hipStream_t s) {
+  ArStepPlan p = ar_plan_step(opts(), wdtype, kvdtype, B, false, false);
+  p.sel = SEL_ARGMAX;  // (layer >= 1: the plan's layer-0 fields are not read)
+  if (which < OP_QKV || which > OP_LM_HEAD) return -1;
+  if (which == OP_MPROJ && p.fused_mlp) return 1;  // no kernel of its own at this B
+  if (iters == 0) return 0;                        // validation only
+  GemvArgs a = make_args<float>(w, st, kvdtype, B, nullptr);
   a.dst = st.logits;
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
+  const int l = which == OP_LM_HEAD ? N_LAYER - 1 : 1;
   for (int i = 0; i < iters; ++i)
-    if (!launch_op<TW>(which, a, w, which == 5 ? N_LAYER - 1 : 1, kvdtype, B, s))
+    if (!(p.bf16 ? launch_op<bf16_t>(which, a, w, l, p, s) : launch_op<float>(which, a, w, l, p, s)))
       return 1;  // no kernel of its own at this B
   return 0;
 }
 
-int ar_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int which, int iters,
-             hipStream_t s) {
-  return wdtype == LVX_DTYPE_BF16 ? ar_probe_impl<bf16_t>(w, st, kvdtype, B, which, iters, s)
-                                  : ar_probe_impl<float>(w, st, kvdtype, B, which, iters, s);
+void ar_launch_step(const ArWeights& w, const ArState& st, const ArStepPlan& p, const float* emb_row, int slot,
+                    int pos, float* logits_out, hipStream_t s) {
+  float* dst = p.row ? logits_out : st.logits;
+  const float* er = p.row ? emb_row : nullptr;
+  if (p.bf16) ar_layers<bf16_t>(w, st, p, er, slot, pos, dst, s);
+  else ar_layers<float>(w, st, p, er, slot, pos, dst, s);
+  if (!p.row && p.sel == SEL_ARGMAX) hipLaunchKernelGGL(ar_argmax_kernel, dim3(p.B), dim3(256), 0, s, st);
 }
 
-void ar_launch_step(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int mode,
-                    const float* emb_row, int slot, int pos, float* logits_out, hipStream_t s) {
-  float* dst = mode == 0 ? st.logits : logits_out;
-  const float* er = mode == 0 ? nullptr : emb_row;
-  const bool deferred = wdtype == LVX_DTYPE_BF16 ? ar_layers<bf16_t>(w, st, kvdtype, B, er, slot, pos, dst, mode == 0, s)
-                                                : ar_layers<float>(w, st, kvdtype, B, er, slot, pos, dst, mode == 0, s);
-  if (mode == 0 && !deferred) hipLaunchKernelGGL(ar_argmax_kernel, dim3(B), dim3(256), 0, s, st);
-}
-
-// test hook (select probe path 3): the 4 <= B <= 8 granule select as c_attn layer 0 (MODE 7) runs it
+// test hook (select probe path 3): the 4 <= B <= 8 granule select as c_attn layer 0 (MLMODE_EMBED_SELECT) runs it
 // (lmg8_reduce + softmax_ties), committed with argmax_commit
 __global__ __launch_bounds__(64) void ar_select8_probe_kernel(ArState st) {
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -3287,14 +3190,14 @@ __global__ __launch_bounds__(64) void ar_select_final_kernel(ArState st) {
 }
 
 // Test hook (lvx_select_probe): the greedy select of each production path over given logits
-// (st.logits). path 0: ar_argmax_kernel; 1: per-block lm_head granules formed as OUT 9 forms them
+// (st.logits). path 0: ar_argmax_kernel; 1: per-block lm_head granules formed as GOUT_LOGITS_GRAN forms them
 // (8 consecutive vocabulary rows per block), reduced by ar_select_final_kernel (lmg_reduce +
-// softmax_ties, the same code as the deferred select in c_attn layer 0, IN 5); 2: the batched
+// softmax_ties, the same code as the deferred select in c_attn layer 0, GIN_EMBED_SELECT); 2: the batched
 // deferred select, ar_embed_select_kernel.
 __global__ void ar_select_probe_prep_kernel(ArState st, int B, int path) {
   const int blk = blockIdx.x, b = threadIdx.x;
   if (b >= B) return;
-  if (path == 3 && blk < LM8_BLOCKS) {  // as ar_mfma_ln_kernel OUT 3 forms them: 16 vocabulary rows per block
+  if (path == 3 && blk < LM8_BLOCKS) {  // as ar_mfma_ln_kernel MLOUT_LOGITS forms them: 16 vocabulary rows per block
     Best r{-INFINITY, -INFINITY, 0x7fffffff};
     for (int n = blk * 16; n < blk * 16 + 16; ++n) r = best_merge(r, Best{st.logits[(size_t)b * VOCAB + n], -INFINITY, n});
     reinterpret_cast<u64x2_t*>(st.lmbest)[(size_t)blk * LM8_ROWS + b] = lm_granule(r);
@@ -3331,11 +3234,9 @@ int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipS
   return 0;
 }
 
-void ar_launch_steps_end(const ArState& st, int wdtype, int B, hipStream_t s) {
-  const bool d = wdtype == LVX_DTYPE_BF16 ? defer_select<bf16_t>(B) : defer_select<float>(B);
-  const bool db = wdtype == LVX_DTYPE_BF16 ? defer_select_batched<bf16_t>(B) : defer_select_batched<float>(B);
-  if (d) hipLaunchKernelGGL(ar_select_final_kernel, dim3(B), dim3(64), 0, s, st);
-  else if (db) hipLaunchKernelGGL(ar_argmax_kernel, dim3(B), dim3(256), 0, s, st);
+void ar_launch_steps_end(const ArState& st, const ArStepPlan& p, hipStream_t s) {
+  if (p.end == END_SELECT_FINAL) hipLaunchKernelGGL(ar_select_final_kernel, dim3(p.B), dim3(64), 0, s, st);
+  else if (p.end == END_ARGMAX) hipLaunchKernelGGL(ar_argmax_kernel, dim3(p.B), dim3(256), 0, s, st);
 }
 
 // ---------------------------------------------------------------------------------

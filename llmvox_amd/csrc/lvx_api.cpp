@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "llmvox.h"
-#include "lvx_internal.h"
+#include "ar_plan.h"
 
 using namespace lvx;
 
@@ -737,8 +737,8 @@ int lvx_ar_forward_row(lvx_ctx* c, int slot, int pos, const float* emb_row, floa
   HIP_TRY(hipSetDevice(c->cfg.device));
   const Opts o = c->opts_snapshot();
   OptScope os(&o);
-  ar_launch_step(c->arw, c->st, c->cfg.weight_dtype, c->cfg.kv_dtype, 1, 1, emb_row, slot, pos, logits,
-                 (hipStream_t)stream);
+  ar_launch_step(c->arw, c->st, ar_plan_step(o, c->cfg.weight_dtype, c->cfg.kv_dtype, 1, true, false), emb_row, slot,
+                 pos, logits, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LVX_OK;
 }
@@ -802,26 +802,30 @@ static int ar_step_impl(lvx_ctx* c, int n_steps, int B, const int32_t* slots, co
   st.margin_plan = margin_plan;
   hipStream_t s = (hipStream_t)stream;
   ar_launch_rowinfo_init(st, B, s);  // per-row control records, then advanced by every step
+  // one plan per call: the steps and the commit of the last one cannot disagree
+  auto plan = [&](const Opts& o) {
+    return ar_plan_step(o, c->cfg.weight_dtype, c->cfg.kv_dtype, B, false, c->arw.q0_text != nullptr);
+  };
   // null-stream callers (torch's default stream) launch the steps one by one: replaying the same
   // steps as graphs on a stream of their own measured no faster (round 1)
   if (!c->use_graphs || s == nullptr) {
     const Opts o = c->opts_snapshot();
     OptScope os(&o);
-    for (int i = 0; i < n_steps; ++i)
-      ar_launch_step(c->arw, st, c->cfg.weight_dtype, c->cfg.kv_dtype, B, 0, nullptr, 0, 0, nullptr, s);
-    ar_launch_steps_end(st, c->cfg.weight_dtype, B, s);
+    const ArStepPlan p = plan(o);
+    for (int i = 0; i < n_steps; ++i) ar_launch_step(c->arw, st, p, nullptr, 0, 0, nullptr, s);
+    ar_launch_steps_end(st, p, s);
     HIP_TRY(hipGetLastError());
     return LVX_OK;
   }
   std::lock_guard<std::mutex> lk(c->mu);
   const Opts o = c->opts;  // the options the cached graphs were captured under (epoch checked under mu)
   OptScope os(&o);
+  const ArStepPlan p = plan(o);
   // graphs of kGraphSteps consecutive steps (one replay per kGraphSteps tokens) + 1-step graph
   auto get_graph = [&](int nst, hipGraphExec_t* out) -> int {
     GraphKey key{B, plan_stride, nst, slots, text_plan, rowstep, tok_plan, margin_plan, stream};
     return cached_graph(c, key, s, [&](hipStream_t cs) {
-      for (int i = 0; i < nst; ++i)
-        ar_launch_step(c->arw, st, c->cfg.weight_dtype, c->cfg.kv_dtype, B, 0, nullptr, 0, 0, nullptr, cs);
+      for (int i = 0; i < nst; ++i) ar_launch_step(c->arw, st, p, nullptr, 0, 0, nullptr, cs);
     }, out);
   };
   int left = n_steps;
@@ -835,7 +839,7 @@ static int ar_step_impl(lvx_ctx* c, int n_steps, int B, const int32_t* slots, co
     if (int r = get_graph(1, &g1)) return r;
     for (; left > 0; --left) HIP_TRY(hipGraphLaunch(g1, s));
   }
-  ar_launch_steps_end(st, c->cfg.weight_dtype, B, s);
+  ar_launch_steps_end(st, p, s);
   HIP_TRY(hipGetLastError());
   return LVX_OK;
 }

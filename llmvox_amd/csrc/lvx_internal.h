@@ -29,18 +29,22 @@ constexpr int LM_MAX_BLOCKS = 1024;  // lm_head blocks of the fused argmax tail 
 // calling thread for the duration of the call (OptScope); the launch helpers read them through
 // opts(). Options set on one context therefore never change another context's kernels, and a
 // launch never reads an option while another thread writes it.
+// What the AR options make a step run is decided in one place, ar_plan_step (ar_plan.h).
 struct Opts {
-  int defer_select = 1;  // greedy select deferred into the next step's first kernel; 0: argmax kernel;
-                         // 2: as 1 but 4 <= B <= 8 through ar_embed_select_kernel (cross-check)
+  int defer_select = 1;  // greedy select deferred into the next step's first kernel, in the form the step's
+                         // path can run (ArSelect: B <= 2 and B >= 4; B = 3 keeps the argmax kernel);
+                         // 0: argmax kernel; 2: as 1 without the 4 <= B <= 8 prologue granules (cross-check)
   int fuse_mlp = 1;      // bf16, B <= 2: c_fc + gelu + mlp c_proj in one kernel; 0: two GEMV kernels
-  int bt = 1;            // 1: batched v3 for 32 < B <= 64; 2: v3 for every batched B (cross-check); 0: off
+  int bt = 1;            // 1: batched v3 for 32 < B <= 64; 2: v3 for every batched B (3..64, cross-check; its
+                         // deferred select is the embedding + select kernel at every B >= 4); 0: off
   int codec_g2 = 1, codec_skinny = 1, codec_g3 = 1, codec_g3f = 2;  // codec GEMM kernels (cross-checks)
   int codec_exp = 0;     // codec A/B bits (bit-identical variants)
   int exp = 0;           // AR cross-check bits (fp32 tiles / one-launch forms: tests/test_gpu_f32b.py)
   int f32b = 1;          // fp32 batched steps on exact-fp32 MFMA; 0: the GEMV family
   int ln_max = 8;        // batched steps with the LayerNorm fused into the GEMM prologue for B <= ln_max
-  int l0q = 1;           // bf16, B <= 32 (not 3): layer 0's q / k / v from the precomputed tables (ArWeights q0_*)
-                         // in the embedding + select kernel; 0: that kernel + the c_attn GEMM (cross-check)
+  int l0q = 1;           // bf16 GEMV / MFMA steps with a deferred select, B <= 32 (not 3): layer 0's q / k / v from
+                         // the precomputed tables (ArWeights q0_*) in the kernel that commits the select
+                         // (ar_q0_gran_kernel, ar_q0_rows_kernel); 0: the path's other select form + c_attn
 };
 const Opts& opts();  // the calling thread's bound options (the defaults when none is bound)
 struct OptScope {    // binds `o` to this thread until the scope ends
@@ -66,7 +70,7 @@ struct ArWeights {
   const void* w_mproj[N_LAYER] = {};  // [768][3072]
   const void* w_mproj_pk[N_LAYER] = {};  // bf16 only: thread-packed copy for the fused MLP (pack_mproj)
   const float* fc_gsum[N_LAYER] = {};    // bf16 only: G[n] = sum_k ln_2.weight[k] * bf16(c_fc W[n][k]) (batched
-                                         // c_fc: LayerNorm applied after the GEMM, ar_mfma2_kernel XM 1)
+                                         // c_fc: LayerNorm applied after the GEMM, ar_mfma2_kernel M2X_LN_AFTER)
   const void* w_lm = nullptr;         // [4096][768]
   // bf16 only: layer 0's c_attn as table rows (ar_embed_select_kernel QKV). The step's input row is
   // x = cat(text_table[t], codebook[c]) / den + wpe[p] and c_attn multiplies LN1(x) = (x - mean) * rstd
@@ -129,16 +133,18 @@ struct ArState {
   int max_pos = 0, max_streams = 0, kv_chunks = 0;
 };
 
-// Launches the whole decode step (embed -> 4 blocks -> lm_head [-> argmax]).
-// mode 0: fused step (inputs from st.slots/st.text_ids, argmax + state advance)
-// mode 1: drop-in row forward (emb_row given, single stream, logits to `logits_out`)
-void ar_launch_step(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int mode,
-                    const float* emb_row, int slot, int pos, float* logits_out, hipStream_t s);
+// Launches the whole decode step (embed -> 4 blocks -> lm_head [-> select]) that the plan `p`
+// describes (ar_plan.h: ar_plan_step, called once per C-ABI call for its steps and their end commit).
+// fused step (!p.row): inputs from st.slots / st.text_plan, select + state advance
+// drop-in row forward (p.row): emb_row given, single stream, logits to `logits_out`
+struct ArStepPlan;
+void ar_launch_step(const ArWeights& w, const ArState& st, const ArStepPlan& p, const float* emb_row, int slot,
+                    int pos, float* logits_out, hipStream_t s);
 
 int ar_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int which, int iters,
              hipStream_t s);
 void ar_launch_rowinfo_init(const ArState& st, int B, hipStream_t s);
-void ar_launch_steps_end(const ArState& st, int wdtype, int B, hipStream_t s);  // deferred select: commit the last step
+void ar_launch_steps_end(const ArState& st, const ArStepPlan& p, hipStream_t s);  // deferred select: commit the last step
 int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipStream_t s);  // test hook
 // ArWeights::q0_text / q0_code / q0_pos from the bf16 c_attn weight of layer 0 (lvx_finalize)
 void ar_launch_q0_tables(const ArWeights& w, int max_pos, float* text, float* code, float* pos, hipStream_t s);

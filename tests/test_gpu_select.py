@@ -113,6 +113,24 @@ def eng_batched():
     e.close()
 
 
+def _run_batched(e, B, slots, calls):
+    dev = e.device
+    rng = np.random.default_rng(B)
+    n = sum(calls)
+    plan = torch.from_numpy(rng.integers(3, 384, size=(B, n)).astype(np.int32)).to(dev)
+    for s in range(48):
+        e.reset_slot(s)
+    st = torch.tensor(slots, dtype=torch.int32, device=dev)
+    rowstep = torch.zeros(B, dtype=torch.int32, device=dev)
+    tok = torch.full((B, n), -7, dtype=torch.int32, device=dev)
+    margin = torch.zeros(B, n, dtype=torch.float32, device=dev)
+    for c in calls:
+        e.ar_steps(c, st, plan, rowstep, tok, margin)
+    e.check_errors()
+    pos = [e.slot_position(s) for s in slots if s >= 0]
+    return tok.cpu().numpy(), margin.cpu().numpy(), rowstep.cpu().numpy(), pos, e.last_logits(B).cpu().numpy()
+
+
 @pytest.mark.parametrize("B,ref_mode", [(4, 0), (8, 0), (32, 0), (48, 0), (4, 2), (5, 2), (8, 2)])
 def test_batched_deferred_select_matches_argmax_kernel(eng_batched, B, ref_mode):
     """Batched steps (MFMA / v3 paths): the select runs in the next step's first kernel (4 <= B <= 8:
@@ -129,21 +147,7 @@ def test_batched_deferred_select_matches_argmax_kernel(eng_batched, B, ref_mode)
     calls = [3, 17, 1, 16]
 
     def run():
-        dev = e.device
-        rng = np.random.default_rng(B)
-        n = sum(calls)
-        plan = torch.from_numpy(rng.integers(3, 384, size=(B, n)).astype(np.int32)).to(dev)
-        for s in range(48):
-            e.reset_slot(s)
-        st = torch.tensor(slots, dtype=torch.int32, device=dev)
-        rowstep = torch.zeros(B, dtype=torch.int32, device=dev)
-        tok = torch.full((B, n), -7, dtype=torch.int32, device=dev)
-        margin = torch.zeros(B, n, dtype=torch.float32, device=dev)
-        for c in calls:
-            e.ar_steps(c, st, plan, rowstep, tok, margin)
-        e.check_errors()
-        pos = [e.slot_position(s) for s in slots if s >= 0]
-        return tok.cpu().numpy(), margin.cpu().numpy(), rowstep.cpu().numpy(), pos, e.last_logits(B).cpu().numpy()
+        return _run_batched(e, B, slots, calls)
 
     e.set_option("defer_select", ref_mode)
     try:
@@ -161,6 +165,38 @@ def test_batched_deferred_select_matches_argmax_kernel(eng_batched, B, ref_mode)
     n = sum(calls)
     assert got[2][B // 2] == 0 and (got[0][B // 2] == -7).all()
     assert all(got[2][b] == n for b in range(B) if b != B // 2)
+
+
+@pytest.mark.parametrize("B", [8, 16])
+def test_v3_deferred_select_at_small_b_matches_argmax_kernel(eng_batched, B):
+    """Option bt 2 (batched path v3 at every batched B) with the default l0q, 4 <= B <= 32: v3 has no
+    table form and no granule form, so its deferred select is the embedding + select kernel, as at
+    B > 32. Against the argmax kernel after every lm_head (defer_select 0): the same kernels for
+    everything but the select, bit-equal, with one idle row. (A plan that handed v3 the table form
+    committed nothing: every step but the last of a call lost its token.)"""
+    e = eng_batched
+    slots = list(range(B))
+    slots[B // 2] = -1
+    calls = [3, 17, 1, 16]
+    e.set_option("bt", 2)
+    try:
+        e.set_option("defer_select", 0)
+        ref = _run_batched(e, B, slots, calls)
+        e.set_option("defer_select", 1)
+        got = _run_batched(e, B, slots, calls)
+    finally:
+        e.set_option("defer_select", 1)
+        e.set_option("bt", 1)
+    live = [b for b in range(B) if b != B // 2]
+    for a, b, name in zip(got, ref, ["tokens", "margins", "rowstep", "positions", "logits"]):
+        if name == "logits":
+            a, b = a[live], b[live]
+        np.testing.assert_array_equal(np.asarray(a), np.asarray(b), err_msg=name)
+    n = sum(calls)
+    assert got[2][B // 2] == 0 and (got[0][B // 2] == -7).all()
+    assert all(got[2][b] == n for b in live)
+    assert not (got[0][live] == -7).any()
+    assert got[3] == [n] * len(live)
 
 
 @pytest.mark.parametrize("B,slots", [(1, [2]), (2, [0, 3]), (2, [1, -1])], ids=["B1", "B2", "B2-idle"])
