@@ -140,6 +140,36 @@ int lvx_error_take(lvx_ctx* ctx, int which, int32_t* bits_dev, void* stream);
 int lvx_error_status(int bits);
 /* Set a slot's position and previous token (rewind after a speculative run-ahead, or jump). */
 int lvx_stream_set(lvx_ctx* ctx, int slot, int pos, int prev_token, void* stream);
+/* Sampling of a slot's decode steps (reference: GPT.generate, src/model.py:384-410). temperature 0
+ * (the default of every slot): greedy. top_k 0 or >= 4096: no crop. Stream-ordered like
+ * lvx_stream_set: call it on the stream of the slot's decode steps. lvx_stream_reset keeps it.
+ * LVX_E_ARG for a slot out of range, temperature < 0 or not finite, top_k < 0.
+ *
+ * The rule of a sampled step (temperature T > 0, p the position of the step being decided, the value
+ * lvx_stream_position would give before it; all arithmetic fp32):
+ *   z[i] = logits[i] / T                          IEEE division, as the reference divides;
+ *   thr  = the top_k-th largest z (exact), i is kept iff z[i] >= thr: the ties at the threshold are
+ *          all kept, as in logits[logits < v[:, [-1]]] = -inf; with no crop every i is kept;
+ *   w[i] = exp(z[i] - max z) for kept i, else 0;  S = sum of w;
+ *   u    = (x0 >> 8) * 2^-24, x0 the first output word of Philox4x32-10 with the counter
+ *          (p, 0, 0, 0) and the key (seed & 0xffffffff, seed >> 32) (multipliers 0xD2511F53 /
+ *          0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, 10 rounds);
+ *   token = the first kept index, in vocabulary order, whose inclusive running sum of w exceeds u * S;
+ *          the last kept index if rounding leaves none.
+ * The running sums are formed as 16-term sums of consecutive indices and a tree over the 256 partial
+ * sums, so a token can differ from an exact-arithmetic evaluation only where u lies within ~2^-16 of a
+ * boundary of the cumulative distribution (tests/sampling_ref.py). Neither the slot nor the batch row
+ * enters the generator: the same (seed, position, logits) give the same token in any row of any
+ * batch, and a rewind (lvx_stream_set) reproduces the draws of the positions decoded again.
+ * margin_plan of a sampled row keeps its meaning, top-1 minus top-2 of the raw logits: it says how
+ * peaked the distribution was, not how close the drawn token was to another.
+ * While any slot of the context has temperature > 0, every lvx_ar_step(s) call of the context runs
+ * the plan of option "defer_select" 0 with the sampled select (ar_sample_kernel) after lm_head; rows
+ * of greedy slots run the argmax kernel's code inside it. In fp32 parity mode their ids are those of
+ * the default plan. In bf16 with option "l0q" 1 they are the "defer_select" 0 ids: layer 0's c_attn
+ * then comes from the GEMM instead of the table rows, and the logits differ in the last bits. With no
+ * slot sampling, plans, kernels and ids are exactly those of a context that never sampled. */
+int lvx_stream_sampling(lvx_ctx* ctx, int slot, float temperature, int top_k, uint64_t seed, void* stream);
 /* Measurement hook (bench.py): launch one kernel class of the decode step `iters` times for the
  * batch rows `slots` at their current positions (0 c_attn, 1 attention, 2 c_proj+merge,
  * 3 c_fc (with the bf16 fused MLP at B <= 2: c_fc + gelu + mlp c_proj), 4 mlp c_proj, 5 lm_head).
@@ -151,7 +181,10 @@ int lvx_probe_kernel(lvx_ctx* ctx, int which, int B, const int32_t* slots_dev, i
  * [B][4096], committed exactly as a decode step commits it (tok_plan[b][rowstep[b]], margin,
  * slot prev / position, rowstep advance). path 0: ar_argmax_kernel; 1: the lm_head-granule
  * reduction of the B <= 2 deferred select (B <= 4 here); 2: the batched deferred select
- * (ar_embed_select_kernel). plan_stride >= 2. */
+ * (ar_embed_select_kernel); 3: the 4 <= B <= 8 prologue-granule reduction (B <= 8); 4: the sampled
+ * select, ar_sample_kernel, with the slots' current lvx_stream_sampling parameters and positions
+ * (the commit advances the positions, so consecutive calls draw with consecutive counters).
+ * plan_stride >= 2. */
 int lvx_select_probe(lvx_ctx* ctx, int path, int B, const int32_t* slots_dev, const float* logits_dev,
                      const int32_t* text_plan_dev, int plan_stride, int32_t* rowstep_dev, int32_t* tok_plan_dev,
                      float* margin_plan_dev, void* stream);

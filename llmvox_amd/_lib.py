@@ -87,6 +87,7 @@ _SIGS = {
     "lvx_ar_logits": (_I, [_P, _I, _P, _P]),
     "lvx_probe_kernel": (_I, [_P, _I, _I, _P, _I, _P]),
     "lvx_stream_set": (_I, [_P, _I, _I, _I, _P]),
+    "lvx_stream_sampling": (_I, [_P, _I, ctypes.c_float, _I, ctypes.c_uint64, _P]),
     "lvx_select_probe": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "lvx_stream_position": (_I, [_P, _I, ctypes.POINTER(_I), _P]),
     "lvx_set_graphs": (_I, [_P, _I]),

@@ -1420,13 +1420,9 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
 // greedy select (streaming_server.py:342-347): argmax with first-index ties, top1-top2
 // margin, then the slot's prev token / position / plan step advance.
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ar_argmax_kernel(ArState st) {
-  __shared__ float sv[4], sv2[4];
-  __shared__ int si[4];
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int4 ri = st.rowinfo[b];
-  const int s = ri.x;
-  if (s < 0) return;
+// one block of 256 threads per batch row b (ri = its live rowinfo record); sv / sv2 / si: 4 LDS words each
+__device__ __forceinline__ void argmax_row(const ArState& st, int b, int4 ri, float* sv, float* sv2, int* si) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float4* lg = reinterpret_cast<const float4*>(st.logits + (size_t)b * VOCAB);
   Best bt{-INFINITY, -INFINITY, 0x7fffffff};
 #pragma unroll
@@ -1446,6 +1442,179 @@ __global__ __launch_bounds__(256) void ar_argmax_kernel(ArState st) {
     for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
     r = softmax_ties(st.logits + (size_t)b * VOCAB, r, lane);
     if (lane == 0) argmax_commit(st, b, ri, r);
+  }
+}
+
+__global__ __launch_bounds__(256) void ar_argmax_kernel(ArState st) {
+  __shared__ float sv[4], sv2[4];
+  __shared__ int si[4];
+  const int b = blockIdx.x;
+  const int4 ri = st.rowinfo[b];
+  if (ri.x < 0) return;
+  argmax_row(st, b, ri, sv, sv2, si);
+}
+
+// ---------------------------------------------------------------------------------
+// sampled select (reference: GPT.generate, src/model.py:384-410): temperature, top-k crop with the
+// ties at the threshold kept, one seeded draw from the softmax; SEL_SAMPLE, in ar_argmax_kernel's
+// place. The rule, which tests/sampling_ref.py recomputes on the CPU (include/llmvox.h has it in full):
+//   z[i] = logits[i] / T (IEEE fp32 division); thr = the k-th largest z (exact: a 4-pass radix select
+//   over order-preserving integer keys of z, 256-bin LDS histogram); kept i: z[i] >= thr;
+//   w[i] = exp(z[i] - max z) for kept i, else 0; S = sum w; u = (x0 >> 8) * 2^-24 with x0 the first word
+//   of Philox4x32-10(counter (pos, 0, 0, 0), key (seed lo, seed hi)); the token is the first index whose
+//   inclusive running sum of w exceeds u * S, the last kept index when rounding leaves none.
+// A thread owns 16 consecutive indices: 16-term running sums, then a block scan of the thread sums (DPP
+// in the wave, LDS across the 4 waves), then a min-reduce of the first crossing index: no serial
+// summation chain beyond the 16 terms (the test tolerance rests on that). Rows of a slot with
+// temperature 0 run ar_argmax_kernel's code. The commit is argmax_commit with the drawn token; the
+// margin stays top1 - top2 of the raw logits.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned z_key(float z) {  // a < b as floats => z_key(a) < z_key(b)
+  const unsigned u = __float_as_uint(z);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float key_z(unsigned k) {
+  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
+}
+// Scans over the wave in lane order: row_shr 1 / 2 / 4 / 8 within each 16-lane row (a lane shifted in
+// from outside the row reads 0), then the row totals through SGPRs
+__device__ __forceinline__ int wave_scan_i32(int v, int lane) {  // inclusive
+  v += dpp_i32<0x111>(v);
+  v += dpp_i32<0x112>(v);
+  v += dpp_i32<0x114>(v);
+  v += dpp_i32<0x118>(v);
+  const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31);
+  const int r2 = __builtin_amdgcn_readlane(v, 47), row = lane >> 4;
+  return v + (row == 0 ? 0 : row == 1 ? r0 : row == 2 ? r0 + r1 : r0 + r1 + r2);
+}
+__device__ __forceinline__ void wave_scan_f32(float x, int lane, float& excl, float& total) {  // exclusive + wave sum
+  float v = x;
+  v += dpp_f32<0x111>(v);
+  v += dpp_f32<0x112>(v);
+  v += dpp_f32<0x114>(v);
+  v += dpp_f32<0x118>(v);
+  const float r0 = lane_f32(v, 15), r1 = lane_f32(v, 31), r2 = lane_f32(v, 47), r3 = lane_f32(v, 63);
+  const int row = lane >> 4;
+  excl = (row == 0 ? 0.f : row == 1 ? r0 : row == 2 ? r0 + r1 : (r0 + r1) + r2) + dpp_f32<0x111>(v);
+  total = ((r0 + r1) + r2) + r3;
+}
+__device__ __forceinline__ int wave_min_i32(int v) {
+  v = min(v, dpp_i32<0xB1>(v));
+  v = min(v, dpp_i32<0x4E>(v));
+  v = min(v, dpp_i32<0x128>(v));
+  v = min(v, dpp_i32<0x124>(v));
+  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
+             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+__global__ __launch_bounds__(256) void ar_sample_kernel(ArState st) {
+  __shared__ float sv[4], sv2[4], wsum[4];
+  __shared__ int si[4], wcnt[4], wfirst[4], wlast[4];
+  __shared__ unsigned hist[256], pick[2];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int4 ri = st.rowinfo[b];
+  const int s = ri.x;
+  if (s < 0) return;
+  const float T = st.smp_temp[s];
+  if (!(T > 0.f)) {  // a greedy slot beside sampling ones: ar_argmax_kernel's code (block-uniform branch)
+    argmax_row(st, b, ri, sv, sv2, si);
+    return;
+  }
+  const int K = st.smp_topk[s];
+  const uint2 seed = st.smp_seed[s];
+  // 16 consecutive logits per thread; top-1 / top-2 of the raw logits for the margin
+  const float4* lg = reinterpret_cast<const float4*>(st.logits + (size_t)b * VOCAB) + tid * 4;
+  float z[16];
+  Best bt{-INFINITY, -INFINITY, 0x7fffffff};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float4 v = lg[k];
+    const int i0 = tid * 16 + k * 4;
+    z[k * 4] = v.x; z[k * 4 + 1] = v.y; z[k * 4 + 2] = v.z; z[k * 4 + 3] = v.w;
+    bt = best_merge(bt, Best{v.x, -INFINITY, i0});
+    bt = best_merge(bt, Best{v.y, -INFINITY, i0 + 1});
+    bt = best_merge(bt, Best{v.z, -INFINITY, i0 + 2});
+    bt = best_merge(bt, Best{v.w, -INFINITY, i0 + 3});
+  }
+  bt = best_wave(bt);
+  if (lane == 0) { sv[wave] = bt.v; sv2[wave] = bt.v2; si[wave] = bt.i; }
+  __syncthreads();
+  Best r{sv[0], sv2[0], si[0]};
+  for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
+#pragma unroll
+  for (int j = 0; j < 16; ++j) z[j] = z[j] / T;
+  const float zmax = r.v / T;  // = max z: the division is monotone
+
+  // top-k threshold: the K-th largest z, digit by digit from the top byte of the keys. Thread t owns bin
+  // 255 - t, so that the scan in thread order counts the keys in this bin and every higher one; the bin
+  // where that count first reaches the rank still wanted holds the K-th largest key.
+  float thr = -INFINITY;
+  if (K > 0 && K < VOCAB) {
+    unsigned prefix = 0;
+    int want = K;
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+      const int sh = 24 - 8 * pass;
+      hist[tid] = 0u;
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const unsigned key = z_key(z[j]);
+        if (pass == 0 || (key >> ((sh + 8) & 31)) == prefix) atomicAdd(&hist[(key >> sh) & 255u], 1u);
+      }
+      __syncthreads();
+      const int c = (int)hist[255 - tid];
+      int sc = wave_scan_i32(c, lane);
+      if (lane == 63) wcnt[wave] = sc;
+      __syncthreads();
+      for (int w = 0; w < wave; ++w) sc += wcnt[w];
+      if (sc >= want && sc - c < want) {  // exactly one thread
+        pick[0] = (unsigned)(255 - tid);
+        pick[1] = (unsigned)(want - (sc - c));
+      }
+      __syncthreads();
+      prefix = (prefix << 8) | pick[0];
+      want = (int)pick[1];
+    }
+    thr = key_z(prefix);
+  }
+
+  // weights and the thread's inclusive running sums
+  float run[16], acc = 0.f;
+  int last = -1;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const bool kept = z[j] >= thr;
+    acc += kept ? expf(z[j] - zmax) : 0.f;
+    run[j] = acc;
+    if (kept) last = tid * 16 + j;
+  }
+  float excl, wtot;
+  wave_scan_f32(acc, lane, excl, wtot);
+  if (lane == 0) wsum[wave] = wtot;
+  __syncthreads();
+  float base = 0.f;
+  for (int w = 0; w < wave; ++w) base += wsum[w];
+  const float S = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  const float P = base + excl;
+
+  uint32_t ctr[4] = {(uint32_t)ri.y, 0u, 0u, 0u};
+  philox4x32_10(ctr, seed.x, seed.y);
+  const float u = (float)(ctr[0] >> 8) * 5.9604644775390625e-08f;  // 24 bits: exact in fp32
+  const float target = u * S;
+  int first = 0x7fffffff;
+#pragma unroll
+  for (int j = 15; j >= 0; --j)
+    if (P + run[j] > target) first = tid * 16 + j;
+  first = wave_min_i32(first);
+  last = -wave_min_i32(-last);
+  if (lane == 0) { wfirst[wave] = first; wlast[wave] = last; }
+  __syncthreads();
+  if (tid == 0) {
+    first = min(min(wfirst[0], wfirst[1]), min(wfirst[2], wfirst[3]));
+    last = max(max(wlast[0], wlast[1]), max(wlast[2], wlast[3]));
+    r.i = first != 0x7fffffff ? first : max(last, 0);
+    argmax_commit(st, b, ri, r);
   }
 }
 
@@ -3120,9 +3289,12 @@ static GemvArgs make_args(const ArWeights& w, const ArState& st, int kvdtype, in
 
 
 template <typename TW>
-static void ar_layers(const ArWeights& w, const ArState& st, const ArStepPlan& p, const float* emb_row, int slot,
+static void ar_layers(const ArWeights& w, const ArState& st, const ArStepPlan& plan, const float* emb_row, int slot,
                       int pos, float* logits_dst, hipStream_t s) {
   static_assert(LM_SEL_BLOCKS <= LM_MAX_BLOCKS && LM_SEL_BLOCKS % 64 == 0, "deferred select granules");
+  // SEL_SAMPLE: the layers and lm_head run as under SEL_ARGMAX (ar_launch_step swaps the kernel after lm_head)
+  ArStepPlan p = plan;
+  if (p.sel == SEL_SAMPLE) p.sel = SEL_ARGMAX;
   GemvArgs a = make_args<TW>(w, st, p.kv_dtype, p.B, emb_row);
   a.defer_sel = p.sel;
   if (emb_row) hipLaunchKernelGGL(ar_row_state_kernel, dim3(1), dim3(1), 0, s, st, slot, pos);
@@ -3158,6 +3330,7 @@ void ar_launch_step(const ArWeights& w, const ArState& st, const ArStepPlan& p, 
   if (p.bf16) ar_layers<bf16_t>(w, st, p, er, slot, pos, dst, s);
   else ar_layers<float>(w, st, p, er, slot, pos, dst, s);
   if (!p.row && p.sel == SEL_ARGMAX) hipLaunchKernelGGL(ar_argmax_kernel, dim3(p.B), dim3(256), 0, s, st);
+  if (!p.row && p.sel == SEL_SAMPLE) hipLaunchKernelGGL(ar_sample_kernel, dim3(p.B), dim3(256), 0, s, st);
 }
 
 // test hook (select probe path 3): the 4 <= B <= 8 granule select as c_attn layer 0 (MLMODE_EMBED_SELECT) runs it
@@ -3193,7 +3366,7 @@ __global__ __launch_bounds__(64) void ar_select_final_kernel(ArState st) {
 // (st.logits). path 0: ar_argmax_kernel; 1: per-block lm_head granules formed as GOUT_LOGITS_GRAN forms them
 // (8 consecutive vocabulary rows per block), reduced by ar_select_final_kernel (lmg_reduce +
 // softmax_ties, the same code as the deferred select in c_attn layer 0, GIN_EMBED_SELECT); 2: the batched
-// deferred select, ar_embed_select_kernel.
+// deferred select, ar_embed_select_kernel; 4: the sampled select, ar_sample_kernel.
 __global__ void ar_select_probe_prep_kernel(ArState st, int B, int path) {
   const int blk = blockIdx.x, b = threadIdx.x;
   if (b >= B) return;
@@ -3217,7 +3390,7 @@ __global__ void ar_select_probe_prep_kernel(ArState st, int B, int path) {
 }
 
 int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipStream_t s) {
-  if (path < 0 || path > 3 || B < 1 || (path == 1 && B > 4) || (path == 3 && B > LM8_ROWS)) return -1;
+  if (path < 0 || path > 4 || B < 1 || (path == 1 && B > 4) || (path == 3 && B > LM8_ROWS)) return -1;
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
   hipLaunchKernelGGL(ar_select_probe_prep_kernel, dim3(LM_SEL_BLOCKS), dim3(64), 0, s, st, B, path);
   if (path == 0) {
@@ -3226,6 +3399,8 @@ int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipS
     hipLaunchKernelGGL(ar_select_final_kernel, dim3(B), dim3(64), 0, s, st);
   } else if (path == 3) {
     hipLaunchKernelGGL(ar_select8_probe_kernel, dim3(B), dim3(64), 0, s, st);
+  } else if (path == 4) {  // the sampled select, with the slots' current parameters and positions
+    hipLaunchKernelGGL(ar_sample_kernel, dim3(B), dim3(256), 0, s, st);
   } else {
     GemvArgs a = make_args<float>(w, st, LVX_DTYPE_F32, B, nullptr);
     a.ln_w = w.ln1[0];
@@ -3271,12 +3446,23 @@ __global__ void set_slot_kernel(int32_t* pos, int32_t* prev, int slot, int p, in
   prev[slot] = tok;
 }
 
+__global__ void set_sampling_kernel(float* temp, int32_t* topk, uint2* seed, int slot, float t, int k, uint2 sd) {
+  temp[slot] = t;
+  topk[slot] = k;
+  seed[slot] = sd;
+}
+
 void ar_launch_rowinfo_init(const ArState& st, int B, hipStream_t s) {
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
 }
 
 void launch_set_slot(int32_t* pos, int32_t* prev, int slot, int p, int tok, hipStream_t s) {
   hipLaunchKernelGGL(set_slot_kernel, dim3(1), dim3(1), 0, s, pos, prev, slot, p, tok);
+}
+
+void launch_set_sampling(const ArState& st, int slot, float temperature, int top_k, uint64_t seed, hipStream_t s) {
+  hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(1), 0, s, st.smp_temp, st.smp_topk, st.smp_seed, slot,
+                     temperature, top_k, make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
 }
 
 // Take (read and clear, one atomic per word) the masked bits of the AR word words[0] and the codec

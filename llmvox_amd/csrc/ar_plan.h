@@ -60,7 +60,10 @@ enum ArPath { PATH_GEMV, PATH_MFMA_LN, PATH_MFMA_ROWS, PATH_BT, PATH_F32B };
 //   SEL_EMBED    batched: the next step's ar_embed_select_kernel reduces the logits, then c_attn
 //   SEL_LN_GRAN  4 <= B <= 8: granules reduced in the prologue of c_attn layer 0 (MLMODE_EMBED_SELECT)
 //   SEL_Q0_ROWS  bf16, 4 <= B <= 32: select + layer 0's c_attn from the q0 tables (ar_q0_rows_kernel)
-enum ArSelect { SEL_ARGMAX = 0, SEL_GRAN = 1, SEL_EMBED = 2, SEL_LN_GRAN = 3, SEL_Q0_ROWS = 4 };
+//   SEL_SAMPLE   ar_sample_kernel after lm_head: the seeded temperature / top-k draw of the slots that
+//                sample, the greedy select for the others (not deferred: the step's other kernels run
+//                as under SEL_ARGMAX, and GemvArgs::defer_sel carries SEL_ARGMAX)
+enum ArSelect { SEL_ARGMAX = 0, SEL_GRAN = 1, SEL_EMBED = 2, SEL_LN_GRAN = 3, SEL_Q0_ROWS = 4, SEL_SAMPLE = 5 };
 enum ArEndCommit { END_NONE, END_SELECT_FINAL, END_ARGMAX };  // kernel that commits a call's last step
 
 struct ArStepPlan {
@@ -126,8 +129,14 @@ inline ArSelect ar_plan_select(const Opts& o, const ArStepPlan& p, bool q0) {
   return SEL_EMBED;
 }
 
-// row: the drop-in row forward (no select); q0: ArWeights::q0_text exists (bf16, lvx_finalize)
-inline ArStepPlan ar_plan_step(const Opts& o, int wdtype, int kvdtype, int B, bool row, bool q0) {
+// row: the drop-in row forward (no select); q0: ArWeights::q0_text exists (bf16, lvx_finalize);
+// sample: some slot of the context samples (lvx_stream_sampling): the plan of option defer_select 0 with
+// ar_sample_kernel in the argmax kernel's place (a deferred form cannot host the draw: its select runs
+// inside the next step's first kernel). The row forward has no select and ignores it.
+inline ArStepPlan ar_plan_step(const Opts& o_, int wdtype, int kvdtype, int B, bool row, bool q0, bool sample = false) {
+  sample = sample && !row;
+  Opts o = o_;
+  if (sample) o.defer_select = 0;
   ArStepPlan p{};
   p.B = B; p.kv_dtype = kvdtype; p.bf16 = wdtype == LVX_DTYPE_BF16; p.row = row;
   const bool batched = !row && B >= MFMA_BATCH_MIN && B <= 64;
@@ -143,8 +152,8 @@ inline ArStepPlan ar_plan_step(const Opts& o, int wdtype, int kvdtype, int B, bo
   p.ksplit = p.path == PATH_F32B && !(o.exp & 512);
   p.qsplit = p.ksplit && B <= 32 && !(o.exp & 1024);
 
-  p.sel = row ? SEL_ARGMAX : ar_plan_select(o, p, q0);
-  p.end = p.sel == SEL_ARGMAX ? END_NONE : p.sel == SEL_GRAN ? END_SELECT_FINAL : END_ARGMAX;
+  p.sel = row ? SEL_ARGMAX : sample ? SEL_SAMPLE : ar_plan_select(o, p, q0);
+  p.end = p.sel == SEL_ARGMAX || p.sel == SEL_SAMPLE ? END_NONE : p.sel == SEL_GRAN ? END_SELECT_FINAL : END_ARGMAX;
   p.selcopy = p.sel == SEL_GRAN || p.sel == SEL_LN_GRAN || p.sel == SEL_Q0_ROWS;
   p.q0_gran = p.sel == SEL_GRAN && o.l0q && q0;
   // fused MLP, measured at B = 1 (round 1): 16 h rows per block (192 blocks) 76.7 us/step; 32 rows (96

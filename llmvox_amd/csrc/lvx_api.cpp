@@ -159,9 +159,10 @@ struct GraphKey {
   int B, stride, nsteps;
   const void *slots, *text, *rowstep, *tok, *margin;
   void* stream;
+  bool sample = false;  // captured with the sampled select (greedy and sampling graphs sit side by side)
   bool operator<(const GraphKey& o) const {
-    return std::tie(B, stride, nsteps, slots, text, rowstep, tok, margin, stream) <
-           std::tie(o.B, o.stride, o.nsteps, o.slots, o.text, o.rowstep, o.tok, o.margin, o.stream);
+    return std::tie(B, stride, nsteps, slots, text, rowstep, tok, margin, stream, sample) <
+           std::tie(o.B, o.stride, o.nsteps, o.slots, o.text, o.rowstep, o.tok, o.margin, o.stream, o.sample);
   }
 };
 
@@ -203,8 +204,14 @@ struct lvx_ctx {
   unsigned graph_epoch = 0;  // opt_epoch when the cached graphs were captured
   hipStream_t capture_stream = nullptr;  // lvx_set_capture_stream (not owned); null: capture on the caller's
   hipStream_t own_capture_stream = nullptr;  // created for null-stream callers only (cached_graph)
+  std::vector<float> smp_temp;  // host mirror of ArState::smp_temp (lvx_stream_sampling, under mu)
+  int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
   std::mutex mu;
 
+  bool sampling_snapshot() {
+    std::lock_guard<std::mutex> lk(mu);
+    return n_sampling > 0;
+  }
   // a snapshot of the options, taken under mu: the caller binds it (OptScope) for its launches
   Opts opts_snapshot() {
     std::lock_guard<std::mutex> lk(mu);
@@ -338,7 +345,7 @@ static std::vector<float> pack_frag32(const std::vector<float>& w, int N, int K)
 
 extern "C" {
 
-int lvx_version(void) { return 1; }
+int lvx_version(void) { return 2; }
 
 const char* lvx_last_error(void) { return g_err.c_str(); }
 
@@ -581,6 +588,12 @@ int lvx_finalize(lvx_ctx* c) {
   st.max_pos = P;
   st.max_streams = S;
   st.kv_chunks = (P + KV_CHUNK - 1) / KV_CHUNK;
+  if ((r = c->dalloc(&st.smp_temp, S)) || (r = c->dalloc(&st.smp_topk, S)) || (r = c->dalloc(&st.smp_seed, S))) return r;
+  HIP_TRY(hipMemset(st.smp_temp, 0, S * 4));  // every slot greedy
+  HIP_TRY(hipMemset(st.smp_topk, 0, S * 4));
+  HIP_TRY(hipMemset(st.smp_seed, 0, S * 8));
+  c->smp_temp.assign(S, 0.f);
+  c->n_sampling = 0;
   if ((r = c->dalloc(&st.slots, S)) || (r = c->dalloc(&st.pos, S)) || (r = c->dalloc(&st.prev, S)) ||
       (r = c->dalloc(&st.err, 4)) || (r = c->dalloc(&st.x, (size_t)S * D)) || (r = c->dalloc(&st.q, (size_t)S * D)) ||
       (r = c->dalloc(&st.part_o, (size_t)S * N_HEAD * NSPLIT * HD)) ||
@@ -672,6 +685,22 @@ int lvx_stream_set(lvx_ctx* c, int slot, int pos, int prev_token, void* stream) 
   if (prev_token < 0 || prev_token >= VOCAB) return fail(LVX_E_ARG, "prev_token out of range");
   HIP_TRY(hipSetDevice(c->cfg.device));
   launch_set_slot(c->st.pos, c->st.prev, slot, pos, prev_token, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+int lvx_stream_sampling(lvx_ctx* c, int slot, float temperature, int top_k, uint64_t seed, void* stream) {
+  NEED_FINAL(c);
+  if (slot < 0 || slot >= c->cfg.max_streams) return fail(LVX_E_ARG, "slot out of range");
+  if (!std::isfinite(temperature) || temperature < 0.f) return fail(LVX_E_ARG, "temperature must be finite and >= 0");
+  if (top_k < 0) return fail(LVX_E_ARG, "top_k must be >= 0");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->n_sampling += (temperature > 0.f) - (c->smp_temp[slot] > 0.f);
+    c->smp_temp[slot] = temperature;
+  }
+  launch_set_sampling(c->st, slot, temperature, top_k, seed, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LVX_OK;
 }
@@ -803,15 +832,16 @@ static int ar_step_impl(lvx_ctx* c, int n_steps, int B, const int32_t* slots, co
   hipStream_t s = (hipStream_t)stream;
   ar_launch_rowinfo_init(st, B, s);  // per-row control records, then advanced by every step
   // one plan per call: the steps and the commit of the last one cannot disagree
-  auto plan = [&](const Opts& o) {
-    return ar_plan_step(o, c->cfg.weight_dtype, c->cfg.kv_dtype, B, false, c->arw.q0_text != nullptr);
+  // (while a slot of the context samples: the sampled select, whatever slots this call drives)
+  auto plan = [&](const Opts& o, bool sample) {
+    return ar_plan_step(o, c->cfg.weight_dtype, c->cfg.kv_dtype, B, false, c->arw.q0_text != nullptr, sample);
   };
   // null-stream callers (torch's default stream) launch the steps one by one: replaying the same
   // steps as graphs on a stream of their own measured no faster (round 1)
   if (!c->use_graphs || s == nullptr) {
     const Opts o = c->opts_snapshot();
     OptScope os(&o);
-    const ArStepPlan p = plan(o);
+    const ArStepPlan p = plan(o, c->sampling_snapshot());
     for (int i = 0; i < n_steps; ++i) ar_launch_step(c->arw, st, p, nullptr, 0, 0, nullptr, s);
     ar_launch_steps_end(st, p, s);
     HIP_TRY(hipGetLastError());
@@ -820,10 +850,11 @@ static int ar_step_impl(lvx_ctx* c, int n_steps, int B, const int32_t* slots, co
   std::lock_guard<std::mutex> lk(c->mu);
   const Opts o = c->opts;  // the options the cached graphs were captured under (epoch checked under mu)
   OptScope os(&o);
-  const ArStepPlan p = plan(o);
+  const bool sample = c->n_sampling > 0;
+  const ArStepPlan p = plan(o, sample);
   // graphs of kGraphSteps consecutive steps (one replay per kGraphSteps tokens) + 1-step graph
   auto get_graph = [&](int nst, hipGraphExec_t* out) -> int {
-    GraphKey key{B, plan_stride, nst, slots, text_plan, rowstep, tok_plan, margin_plan, stream};
+    GraphKey key{B, plan_stride, nst, slots, text_plan, rowstep, tok_plan, margin_plan, stream, sample};
     return cached_graph(c, key, s, [&](hipStream_t cs) {
       for (int i = 0; i < nst; ++i) ar_launch_step(c->arw, st, p, nullptr, 0, 0, nullptr, cs);
     }, out);
@@ -926,7 +957,7 @@ int lvx_select_probe(lvx_ctx* c, int path, int B, const int32_t* slots, const fl
   NEED_FINAL(c);
   if (B < 1 || B > c->cfg.max_streams || (path == 1 && B > 4) || (path == 3 && B > 8))
     return fail(LVX_E_ARG, "B out of range for this path");
-  if (path < 0 || path > 3) return fail(LVX_E_ARG, "path must be 0, 1, 2 or 3");
+  if (path < 0 || path > 4) return fail(LVX_E_ARG, "path must be 0, 1, 2, 3 or 4");
   if (!slots || !logits || !text_plan || !rowstep || !tok_plan || plan_stride < 2)
     return fail(LVX_E_ARG, "null argument or plan_stride < 2");
   HIP_TRY(hipSetDevice(c->cfg.device));

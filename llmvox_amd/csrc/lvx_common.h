@@ -31,6 +31,30 @@ __device__ __forceinline__ fp8_t f32_to_fp8(float f) {
   return (fp8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(f, f, 0, false) & 0xff);
 }
 
+// Philox4x32-10 (Salmon et al., SC'11), counter c[4] -> c[4] under the key (k0, k1): the stateless
+// generator of the sampled select (ar_sample_kernel). Plain integer arithmetic, the same words on the
+// host (tests/ar_plan_sample_dump.cpp prints the known answers) and the device.
+__host__ __device__ __forceinline__ uint32_t philox_mulhi(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umulhi(a, b);
+#else
+  return (uint32_t)(((uint64_t)a * b) >> 32);
+#endif
+}
+__host__ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = philox_mulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const uint32_t hi1 = philox_mulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;  // Weyl sequence of the key, bumped between rounds
+    k1 += 0xBB67AE85u;
+  }
+}
+
 // a + w.x x.x + w.y x.y + w.z x.z + w.w x.w as an explicit fma chain: the rounding does not
 // depend on how the compiler contracts each unrolled copy, so equal batch rows stay bit-equal
 __device__ __forceinline__ float dot4_fma(float a, float4 w, float4 x) {

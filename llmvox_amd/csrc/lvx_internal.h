@@ -107,6 +107,10 @@ struct ArState {
   uint32_t* selrow = nullptr;    // [B] batched deferred select: row b's logits not yet committed
   int32_t* pos = nullptr;       // [max_streams] per-slot next position
   int32_t* prev = nullptr;      // [max_streams] per-slot previous token
+  // per-slot sampling parameters (lvx_stream_sampling; read by ar_sample_kernel, so graphs replay unchanged)
+  float* smp_temp = nullptr;    // [max_streams] temperature; 0: the slot decodes greedily
+  int32_t* smp_topk = nullptr;  // [max_streams] top-k crop; 0 or >= VOCAB: none
+  uint2* smp_seed = nullptr;    // [max_streams] Philox key (seed low word, high word)
   int32_t* err = nullptr;       // [4] error words: [0] AR (1 KV capacity, 2 plan overrun, 4 text id / code out
                                 // of range in the drop-in gathers, 32 fused-MLP fixed-point range); [1] codec
                                 // (4 code out of range, 8 ISTFT envelope); [2] / [3] take slots of
@@ -149,6 +153,7 @@ int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipS
 // ArWeights::q0_text / q0_code / q0_pos from the bf16 c_attn weight of layer 0 (lvx_finalize)
 void ar_launch_q0_tables(const ArWeights& w, int max_pos, float* text, float* code, float* pos, hipStream_t s);
 void launch_set_slot(int32_t* pos, int32_t* prev, int slot, int p, int tok, hipStream_t s);
+void launch_set_sampling(const ArState& st, int slot, float temperature, int top_k, uint64_t seed, hipStream_t s);
 void launch_err_take(int32_t* words, int mask_ar, int mask_codec, int32_t* out, hipStream_t s);
 void launch_text_embed(const float* table, const int64_t* ids, int n, float* out, int32_t* err, hipStream_t s);
 void launch_codes_to_features(const float* codebook, const int64_t* codes, int B, int L, float* feats,

@@ -93,6 +93,12 @@ class Engine:
     def set_slot(self, slot: int, pos: int, prev_token: int = 0):
         _lib.check(self.lib.lvx_stream_set(self.h, slot, pos, prev_token, self.stream_handle()))
 
+    def set_sampling(self, slot: int, temperature: float = 0.0, top_k: int = 0, seed: int = 0):
+        """Seeded temperature / top-k sampling of the slot's decode steps (lvx_stream_sampling; temperature 0:
+        greedy). Stream-ordered on the current stream, like ``set_slot``."""
+        _lib.check(self.lib.lvx_stream_sampling(self.h, slot, float(temperature), int(top_k),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, self.stream_handle()))
+
     def slot_position(self, slot: int) -> int:
         v = ctypes.c_int()
         _lib.check(self.lib.lvx_stream_position(self.h, slot, ctypes.byref(v), self.stream_handle()))
@@ -112,7 +118,8 @@ class Engine:
     def select_probe(self, path: int, slots: torch.Tensor, logits: torch.Tensor, text_plan: torch.Tensor,
                      rowstep: torch.Tensor, tok_plan: torch.Tensor, margin_plan: Optional[torch.Tensor] = None):
         """Test hook: one production select path (0 argmax kernel, 1 deferred lm_head granules,
-        2 batched deferred select) over the given logits [B, 4096], committed as a step commits."""
+        2 batched deferred select, 3 the 4 <= B <= 8 prologue granules, 4 the sampled select with the
+        slots' current set_sampling parameters) over the given logits [B, 4096], committed as a step commits."""
         B, stride = text_plan.shape
         logits = logits.to(self.device, torch.float32).contiguous()
         _lib.check(self.lib.lvx_select_probe(self.h, path, B, _ptr(slots), _ptr(logits), _ptr(text_plan), stride,

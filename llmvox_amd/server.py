@@ -39,6 +39,7 @@ Differences, on purpose:
     out of service (its requests end with the error; new requests go to the other devices).
 """
 
+import os
 import threading
 from queue import Queue
 from typing import List, Optional
@@ -237,8 +238,10 @@ class TTSService:
         G = len(self.workers)
         return [self.workers[(k + i) % G] for i in range(G)]
 
-    def submit(self, text: str) -> _Session:
-        """Open the request's two replica streams on the first device (round robin from k mod G)
+    def submit(self, text: str, sampling=None) -> _Session:
+        """``sampling``: a ``sampling.Sampling`` makes the request's streams draw their tokens (seeded
+        temperature / top-k; the replicas and the sentences each from a seed of their own), None: greedy.
+        Open the request's two replica streams on the first device (round robin from k mod G)
         that is in service and has two free KV slots. Requests run for different lengths, so the
         devices fill unevenly: a full device passes the request on instead of refusing it (ADVICE
         r03); only when no device has room is it refused."""
@@ -251,13 +254,14 @@ class TTSService:
             with w.lock:
                 if w.error is not None or len(w.sched.free_slots) < 2:
                     continue
-                return self._open(w, text, queues)
+                return self._open(w, text, queues, sampling)
         if not in_service:
             raise RuntimeError("TTS scheduler thread failed") from self.workers[0].error
         raise RuntimeError("no free KV slots: too many concurrent requests")
 
-    def _open(self, w: _Worker, text: str, queues) -> _Session:  # (caller holds w.lock)
-        streams = [w.sched.open_stream(index=i, dump_size=self.dumps[i], sink=queues[i], eoa_id=self.eoa_id)
+    def _open(self, w: _Worker, text: str, queues, sampling=None) -> _Session:  # (caller holds w.lock)
+        kw = {} if sampling is None else {"sampling": sampling}
+        streams = [w.sched.open_stream(index=i, dump_size=self.dumps[i], sink=queues[i], eoa_id=self.eoa_id, **kw)
                    for i in range(2)]
         s = _Session(streams, queues, w)
 
@@ -332,18 +336,42 @@ class TTSService:
                 w.sched.close()
 
 
-def create_app(service, cors: bool = True):
+def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
-    on another origin can stream; ``cors=False`` leaves it off). The reference's /voicechat,
+    on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
+    (>= 0, finite; 0: greedy), ``top_k`` (>= 0; 0: no crop) and ``seed`` (int >= 0; absent with a
+    temperature > 0: drawn from os.urandom), the reference's GPT.generate controls; ``temperature`` /
+    ``top_k`` here are the defaults of requests that name none of the three. Invalid values: 422. The reference's /voicechat,
     /multimodalchat and /vlmschat differ from /tts only in the producer (ASR / multimodal LLM,
     out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import StreamingResponse
     from pydantic import BaseModel
 
+    from .sampling import Sampling
+    Sampling(temperature, top_k)  # (the defaults are validated at start-up)
+
     class TTSRequest(BaseModel):
         text: str
+        temperature: Optional[float] = None
+        top_k: Optional[int] = None
+        seed: Optional[int] = None
+
+    def sampling_of(request):
+        """The request's Sampling, or None for a greedy request (then submit gets the text alone)."""
+        named = not (request.temperature is None and request.top_k is None and request.seed is None)
+        t = request.temperature if named and request.temperature is not None else temperature
+        k = request.top_k if named and request.top_k is not None else top_k
+        try:
+            sp = Sampling(t, k, request.seed if request.seed is not None else 0)
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        if not sp.temperature > 0:
+            return None
+        if request.seed is None:
+            sp = Sampling(sp.temperature, sp.top_k, int.from_bytes(os.urandom(8), "little"))
+        return sp
 
     app = FastAPI(title="llmvox_amd streaming TTS")
     if cors:
@@ -358,8 +386,9 @@ def create_app(service, cors: bool = True):
 
     @app.post("/tts")
     def tts(request: TTSRequest):
+        sp = sampling_of(request)
         try:
-            session = service.submit(request.text)
+            session = service.submit(request.text) if sp is None else service.submit(request.text, sampling=sp)
         except RuntimeError as e:
             raise HTTPException(status_code=503, detail=str(e))
         return StreamingResponse(service.chunks(session), media_type="application/octet-stream")
@@ -392,6 +421,9 @@ def main(argv=None):
     ap.add_argument("--llm-checkpoint", default=None,
                     help="local HF causal-LM directory: /tts speaks its reply to the request text")
     ap.add_argument("--llm-max-tokens", type=int, default=1000)
+    ap.add_argument("--temperature", type=float, default=0.0,
+                    help="sampling temperature of requests that name no sampling field (0: greedy)")
+    ap.add_argument("--top-k", type=int, default=0, help="their top-k crop (0: none)")
     a = ap.parse_args(argv)
     from .engine import build_engine
     from . import weights as W
@@ -416,7 +448,7 @@ def main(argv=None):
                           "llm_max_tokens": a.llm_max_tokens}).load()
     svc = TTSService(engines, stream_model=sm)
     import uvicorn
-    uvicorn.run(create_app(svc), host=a.host, port=a.port)
+    uvicorn.run(create_app(svc, temperature=a.temperature, top_k=a.top_k), host=a.host, port=a.port)
 
 
 if __name__ == "__main__":

@@ -409,6 +409,9 @@ class FusedStream:
         self.events: List[object] = []   # decoded items in order: bytes or signals
         self.tokens: List[int] = []      # every greedy token consumed (diagnostics / tests)
         self.fed = False                 # a word has been fed (the service caps only fed streams)
+        self.sampling = None             # a sampling.Sampling: the slot draws its tokens (open_stream)
+        self.index = 0                   # replica index of the request (enters the segment seeds)
+        self.segment = 0                 # sentences ended so far: each one draws from a seed of its own
 
     def feed(self, word):
         self.fed = True
@@ -590,19 +593,38 @@ class FusedScheduler:
                 "tok_h": torch.zeros((R, n), dtype=torch.int32, pin_memory=pin),
                 "err_h": torch.zeros((1,), dtype=torch.int32, pin_memory=pin)}
 
-    def open_stream(self, index=0, dump_size=C.INITIAL_DUMP_SIZE_1, sink=None, **kw) -> FusedStream:
+    def open_stream(self, index=0, dump_size=C.INITIAL_DUMP_SIZE_1, sink=None, sampling=None, **kw) -> FusedStream:
+        """sampling: a ``sampling.Sampling`` (temperature > 0) makes the stream draw its tokens, every
+        sentence from ``segment_seed(seed, index, sentence)``; None (or temperature 0): greedy, and the
+        engine's ``set_sampling`` is never called."""
+        if sampling is not None and not sampling.temperature > 0:
+            sampling = None
+        if sampling is not None and not hasattr(self.engine, "set_sampling"):
+            raise RuntimeError("this engine cannot sample (it has no set_sampling): open the stream without `sampling`")
         if not self.free_slots:
             raise RuntimeError("no free KV slot")
         slot = self.free_slots.pop()
         st = FusedStream(self, slot, SegmentMachine(index=index, dump_size=dump_size, **kw), sink)
+        st.sampling, st.index = sampling, index
         with self._on_ar():
             self.engine.reset_slot(slot)  # (stream-ordered behind any chunk in flight on the slot)
+            self._seed_segment(st)
         self.streams.append(st)
         return st
+
+    def _seed_segment(self, st: FusedStream):
+        """Queue (on the AR stream: the caller holds _on_ar) the parameters of the stream's current sentence."""
+        if st.sampling is not None:
+            from .sampling import segment_seed
+            sp = st.sampling
+            self.engine.set_sampling(st.slot, sp.temperature, sp.top_k, segment_seed(sp.seed, st.index, st.segment))
 
     def close_stream(self, st: FusedStream):
         self.streams.remove(st)
         self.free_slots.append(st.slot)
+        if st.sampling is not None:  # the slot's next stream starts greedy (behind this one's chunks in flight)
+            with self._on_ar():
+                self.engine.set_sampling(st.slot, 0.0, 0, 0)
 
     def close(self):
         """Stop the delivery thread (after delivering what is queued)."""
@@ -791,8 +813,12 @@ class FusedScheduler:
             if reset:
                 # run-ahead past end-of-audio: drop the rest, restart the slot at position 0
                 # (queued behind any newer chunk in flight, whose row of this stream is discarded)
+                # (a sampling stream: the next sentence's seed in the same place in stream order, so the
+                # discarded run-ahead rows and the serial schedule see the same parameters)
+                st.segment += 1
                 with self._on_ar():
                     self.engine.set_slot(st.slot, 0, 0)
+                    self._seed_segment(st)
                 for newer in self.inflight:
                     newer.bad.add(st)
                 ended.add(st)

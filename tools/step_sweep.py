@@ -3,7 +3,10 @@ option sets; each config measured 3 times (median).
 usage: python tools/step_sweep.py B P0 'opt=v,...' ['opt=v' ...]
 LVX_SWEEP_STREAM=1: run on a torch side stream (the library then replays 16-step HIP graphs; on the
 default (null) stream it launches every kernel). LVX_SWEEP_KV=fp8: fp8 KV cache (configs[4]).
-LVX_SWEEP_W=fp32: the fp32 parity mode (fp32 weights and KV)."""
+LVX_SWEEP_W=fp32: the fp32 parity mode (fp32 weights and KV).
+LVX_SWEEP_SAMPLE=T,k: every option set is measured twice in the same process, greedy as given and
+then with seeded sampling (temperature T, top-k k) enabled on all B slots (the step then runs the
+defer_select 0 plan with ar_sample_kernel after lm_head: compare with the set 'defer_select=0')."""
 import os, statistics, sys, time
 import torch
 from llmvox_amd.engine import build_engine
@@ -18,10 +21,16 @@ tok = torch.zeros(B, P0 + 256, dtype=torch.int32, device=dev)
 side = torch.cuda.Stream(device=dev) if os.environ.get("LVX_SWEEP_STREAM") == "1" else None
 if side is not None:
     torch.cuda.set_stream(side)
-for spec in sys.argv[3:] or [""]:
+SAMPLE = os.environ.get("LVX_SWEEP_SAMPLE")
+runs = [(spec, smp) for spec in (sys.argv[3:] or [""]) for smp in ([None, SAMPLE] if SAMPLE else [None])]
+for spec, smp in runs:
     opts = [kv.split("=") for kv in spec.split(",") if kv]
     for k, v in opts:
         e.set_option(k, int(v))
+    if smp:
+        T, topk = smp.split(",")
+        for s in range(B):
+            e.set_sampling(s, float(T), int(topk), 1000 + s)
     ts = []
     for rep in range(3):
         for s in range(B):
@@ -38,6 +47,9 @@ for spec in sys.argv[3:] or [""]:
         torch.cuda.synchronize()
         ts.append((time.perf_counter() - t0) / 256 * 1e6)
     us = statistics.median(ts)
-    print(f"B={B} P={P0}.. [{spec}]: {us:7.1f} us/step  {B / us * 1e6:9.0f} tok/s", flush=True)
+    print(f"B={B} P={P0}.. [{spec}]{' +sample ' + smp if smp else ''}: {us:7.1f} us/step  {B / us * 1e6:9.0f} tok/s", flush=True)
+    if smp:
+        for s in range(B):
+            e.set_sampling(s, 0.0, 0, 0)
     for k, v in opts:
         e.set_option(k, {"bt": 1, "defer_select": 1, "fuse_mlp": 1, "codec_g2": 1, "codec_g3": 1, "codec_skinny": 1, "f32b": 1, "ln_max": 8, "l0q": 1}.get(k, 0))
