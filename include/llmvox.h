@@ -250,6 +250,65 @@ int lvx_codec_decode_features(lvx_ctx* ctx, const float* feats_dev, int B, int L
 int lvx_codec_decode_codes(lvx_ctx* ctx, const int32_t* codes_dev, int B, int L, int bandwidth_id,
                            float* pcm_dev, void* stream);
 
+/* ---- PCM output stage ---------------------------------------------------------
+ * The codec writes float32 PCM at 24 kHz (what the reference streams). This stage turns rows of it, on
+ * the device, into what a client asked for: another sample rate and / or 16-bit integers. A stream that
+ * asks for nothing never comes here: 24000 Hz f32le is the codec's own output, and lvx_pcm_convert
+ * launches nothing for it.
+ *
+ * Output sample rates: 24000 (no resampling), 16000, 8000, 48000. Encodings: f32le, s16le.
+ *
+ * Resampling is a rational polyphase FIR with fixed L / M (output rate = 24000 L / M):
+ *   16000: L / M = 2 / 3, N = 72 (145 prototype taps, <= 73 per output);
+ *    8000: L / M = 1 / 3, N = 72 (145 prototype taps, 145 per output);
+ *   48000: L / M = 2 / 1, N = 48 (97 prototype taps, <= 49 per output).
+ * The prototype is a Kaiser-windowed sinc built on the host in double precision, stored as fp32:
+ *   lo = min(1, L / M);  fc = 0.5 lo 0.85 / L;  N = round(24 L / lo);
+ *   h[n] = L 2 fc sinc(2 fc n) kaiser(2 N + 1, beta = 9.0)[n + N],  n = -N .. N,
+ *   sinc(x) = sin(pi x) / (pi x), kaiser(K, beta)[k] = I0(beta sqrt(1 - (2 k / (K - 1) - 1)^2)) / I0(beta).
+ * Its 0.1 dB passband edge is 0.765 of the lower of the two Nyquist frequencies, its stopband
+ * <= -91 dB from that frequency on (float64 design); the DC gain of every phase is 1 within 1e-5.
+ *
+ * One segment is one sentence of one stream. Its input is x[0 .. T), zero outside; its output is
+ *   y[m] = sum over the i with |m M - i L| <= N of x[i] h[m M - i L],   m = 0 .. ceil(T L / M) - 1,
+ * evaluated in fp32 in ONE fixed order: acc = 0, then for i ascending (every i of the range, the ones
+ * outside [0, T) as x[i] = 0) acc = fl(acc + fl(x[i] h[m M - i L])): a rounded product and a rounded sum,
+ * no fused multiply-add. Each output is an independent dot product, so THE CONCATENATED OUTPUTS OF ANY
+ * CHUNKING OF A SEGMENT ARE BIT-IDENTICAL TO ITS ONE-SHOT OUTPUT, and a host evaluation of the same
+ * order in fp32 (llmvox_amd/audio.py: resample_ref) gives the same bits.
+ *
+ * Streaming. After a non-final call that brings the segment's input count to T, the outputs emitted so
+ * far are the m < E(T) = min(floor(((T - 1) L - N) / M) + 1, ceil(T L / M)), E(T) = 0 if (T - 1) L < N;
+ * a final call emits up to ceil(T L / M). The first output of a call reaches back at most 2 N / L =
+ * 144 / 72 / 48 inputs (8 / 16 / 48 kHz) before the call's first input, so the library keeps, per KV
+ * slot, the last 160 inputs of the previous call (two buffers per slot: a launch reads one and writes
+ * the other) and, on the host, the slot's input count and rate (a mirror, as lvx_stream_sampling keeps
+ * one): a slot's calls are issued in order on one stream. A segment is resampled at one rate: another
+ * rate before its final call is LVX_E_ARG.
+ *
+ * s16le: q = rint(clamp(v 32768, -32768, 32767)), round half to even, v the fp32 sample (resampled or
+ * not); NaN -> 0. Exact in fp32. 24000 Hz s16le is the same kernel without a filter: elementwise, stateless. */
+#define LVX_PCM_F32LE 0
+#define LVX_PCM_S16LE 1
+/* host only: L, M, N and the 2 N + 1 fp32 taps h[-N .. N] of a rate (24000: 1, 1, 0 and the tap 1).
+ * taps_host may be NULL (only L, M, N). LVX_E_ARG for an unsupported rate or cap < 2 N + 1. */
+int lvx_pcm_filter(int sample_rate, int* L, int* M, int* N, float* taps_host, int cap);
+/* host only: samples a call emits for a slot that has consumed t0 inputs of its segment
+ * (negative: LVX_E_ARG for an unsupported rate, t0 < 0 or n_in < 0) */
+int lvx_pcm_emitted(int sample_rate, long long t0, int n_in, int final);
+/* forget a slot's history and position (a new segment); stream-ordered */
+int lvx_pcm_reset(lvx_ctx* ctx, int slot, void* stream);
+/* rows b of pcm_dev [B][n_in] f32 continue the segments of slots_host[b]; final_host[b] != 0 flushes and
+ * resets the slot. n_in may be 0 with final (flush only). out row b starts at out_dev + b * out_stride_bytes
+ * (int16 or float32 samples); n_out_host[b] = samples written. Host arrays are consumed before the call
+ * returns. 24000 Hz f32le: nothing is launched and nothing written, the rows of pcm_dev are the output
+ * (n_out_host[b] = n_in; out_dev may be NULL). LVX_E_ARG (and no slot's state changed): a bad rate or
+ * encoding, B < 1, n_in < 0, a slot out of range or named twice, out_dev or out_stride_bytes not a
+ * multiple of 4, out_stride_bytes smaller than a row's output. */
+int lvx_pcm_convert(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
+                    const uint8_t* final_host, int sample_rate, int encoding, void* out_dev,
+                    long long out_stride_bytes, int32_t* n_out_host, void* stream);
+
 /* ---- WavTokenizer encoder, a context of its own (its weights are not needed for TTS).
  * Replaces WavTokenizer.encode_infer (WavTokenizer/decoder/pretrained.py:185-190 ->
  * decoder/feature_extractors.py:122-133): SEANet encoder (encoder/modules/seanet.py:94-143) + the

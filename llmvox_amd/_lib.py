@@ -24,6 +24,8 @@ LVX_E_INDEX = -6
 LVX_DTYPE_F32 = 0
 LVX_DTYPE_BF16 = 1
 LVX_DTYPE_FP8 = 2  # kv_dtype only (OCP e4m3fn)
+LVX_PCM_F32LE = 0
+LVX_PCM_S16LE = 1
 
 DTYPES = {"fp32": LVX_DTYPE_F32, "f32": LVX_DTYPE_F32, "float32": LVX_DTYPE_F32,
           "bf16": LVX_DTYPE_BF16, "bfloat16": LVX_DTYPE_BF16,
@@ -95,6 +97,10 @@ _SIGS = {
     "lvx_set_option": (_I, [_P, ctypes.c_char_p, _I]),
     "lvx_codec_decode_features": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "lvx_codec_decode_codes": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "lvx_pcm_filter": (_I, [_I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _I]),
+    "lvx_pcm_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
+    "lvx_pcm_reset": (_I, [_P, _I, _P]),
+    "lvx_pcm_convert": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, ctypes.c_longlong, _P, _P]),
     "lvx_enc_create": (_I, [_I, ctypes.c_longlong, ctypes.POINTER(_P)]),
     "lvx_enc_set_weight": (_I, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
     "lvx_enc_finalize": (_I, [_P]),

@@ -186,6 +186,54 @@ static uint8_t f32_to_e4m3_host(float x) {
   return sign | (uint8_t)code;
 }
 
+// ---- PCM output stage: the rates, their prototype filters and the streaming counts (llmvox.h) ----
+struct PcmRate {
+  int rate, L, M, N;
+  int tap_off;  // float offset of the rate's taps in lvx_ctx::pcm_taps
+};
+static const PcmRate kPcmRates[] = {{16000, 2, 3, 72, 0}, {8000, 1, 3, 72, 145}, {48000, 2, 1, 48, 290}};
+static const PcmRate kPcmNoFilter = {24000, 1, 1, 0, 0};
+
+static const PcmRate* pcm_rate_of(int sample_rate) {
+  if (sample_rate == 24000) return &kPcmNoFilter;
+  for (const PcmRate& pr : kPcmRates)
+    if (pr.rate == sample_rate) return &pr;
+  return nullptr;
+}
+
+static double bessel_i0(double x) {  // the power series: sum ((x / 2)^k / k!)^2
+  double sum = 1.0, term = 1.0;
+  const double q = x * x / 4.0;
+  for (int k = 1; k < 200; ++k) {
+    term *= q / ((double)k * k);
+    sum += term;
+    if (term < 1e-17 * sum) break;
+  }
+  return sum;
+}
+
+// h[n] = L 2 fc sinc(2 fc n) kaiser(2 N + 1, 9.0)[n + N], n = -N .. N, designed in double, stored as fp32
+static std::vector<float> pcm_design(const PcmRate& pr) {
+  if (pr.N == 0) return {1.f};
+  const double lo = std::min(1.0, (double)pr.L / pr.M), fc = 0.5 * lo * 0.85 / pr.L, beta = 9.0, pi = 3.14159265358979323846;
+  std::vector<float> h(2 * pr.N + 1);
+  for (int n = -pr.N; n <= pr.N; ++n) {
+    const double a = 2.0 * fc * n, sinc = n == 0 ? 1.0 : std::sin(pi * a) / (pi * a);
+    const double u = (double)n / pr.N;
+    const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / bessel_i0(beta);
+    h[n + pr.N] = (float)(pr.L * 2.0 * fc * sinc * w);
+  }
+  return h;
+}
+
+// outputs of a segment emitted once T inputs are consumed
+static long long pcm_emitted_upto(const PcmRate& pr, long long T, bool final) {
+  const long long all = (T * pr.L + pr.M - 1) / pr.M;  // ceil(T L / M)
+  if (final || pr.N == 0) return all;
+  const long long a = (T - 1) * pr.L - pr.N;
+  return a < 0 ? 0 : std::min(a / pr.M + 1, all);
+}
+
 struct lvx_ctx {
   lvx_config cfg{};
   std::map<std::string, std::vector<float>> host;  // staged fp32 weights (released at finalize)
@@ -206,6 +254,13 @@ struct lvx_ctx {
   hipStream_t own_capture_stream = nullptr;  // created for null-stream callers only (cached_graph)
   std::vector<float> smp_temp;  // host mirror of ArState::smp_temp (lvx_stream_sampling, under mu)
   int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
+  // PCM output stage: the device taps of the three resampling rates, the slots' history pool
+  // [2][max_streams][PCM_HIST] and the host mirror of every slot's segment (lvx_pcm_convert, under mu)
+  float* pcm_taps = nullptr;
+  float* pcm_hist = nullptr;
+  std::vector<long long> pcm_t0;  // inputs of the slot's segment consumed so far
+  std::vector<int> pcm_rate;      // rate of the slot's open segment, 0: none open
+  std::vector<uint8_t> pcm_par;   // which of the slot's two history buffers is current
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -640,6 +695,20 @@ int lvx_finalize(lvx_ctx* c) {
     return r;
   HIP_TRY(hipMemset(cs.tick, 0, 4096 * 4));
   cs.err = st.err + 1;  // the codec's own word (it may run on a second stream beside the AR)
+  // ---- PCM output stage (allocated last: every other buffer stays where it was) ----
+  {
+    std::vector<float> taps;
+    for (const PcmRate& pr : kPcmRates) {
+      const std::vector<float> h = pcm_design(pr);
+      taps.insert(taps.end(), h.begin(), h.end());
+    }
+    if ((r = c->dalloc(&c->pcm_taps, taps.size())) || (r = c->dalloc(&c->pcm_hist, (size_t)2 * S * PCM_HIST))) return r;
+    HIP_TRY(hipMemcpy(c->pcm_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->pcm_hist, 0, (size_t)2 * S * PCM_HIST * 4));
+    c->pcm_t0.assign(S, 0);
+    c->pcm_rate.assign(S, 0);
+    c->pcm_par.assign(S, 0);
+  }
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
   c->finalized = true;
@@ -1007,6 +1076,108 @@ int lvx_codec_decode_codes(lvx_ctx* c, const int32_t* codes, int B, int L, int b
   const Opts o = c->opts_snapshot();
   OptScope os(&o);
   codec_launch_decode(c->cw, c->cs, c->cfg.weight_dtype, nullptr, codes, B, L, bw, pcm, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+// ---- PCM output stage ----
+int lvx_pcm_filter(int sample_rate, int* L, int* M, int* N, float* taps_host, int cap) {
+  const PcmRate* pr = pcm_rate_of(sample_rate);
+  if (!pr) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate) + " (24000, 16000, 8000, 48000)");
+  if (L) *L = pr->L;
+  if (M) *M = pr->M;
+  if (N) *N = pr->N;
+  if (taps_host) {
+    if (cap < 2 * pr->N + 1) return fail(LVX_E_ARG, "taps_host holds fewer than 2 N + 1 floats");
+    const std::vector<float> h = pcm_design(*pr);
+    std::memcpy(taps_host, h.data(), h.size() * 4);
+  }
+  return LVX_OK;
+}
+
+int lvx_pcm_emitted(int sample_rate, long long t0, int n_in, int final) {
+  const PcmRate* pr = pcm_rate_of(sample_rate);
+  if (!pr) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate));
+  if (t0 < 0 || n_in < 0) return fail(LVX_E_ARG, "t0 and n_in must be >= 0");
+  return (int)(pcm_emitted_upto(*pr, t0 + n_in, final != 0) - pcm_emitted_upto(*pr, t0, false));
+}
+
+int lvx_pcm_reset(lvx_ctx* c, int slot, void* stream) {
+  NEED_FINAL(c);
+  if (slot < 0 || slot >= c->cfg.max_streams) return fail(LVX_E_ARG, "slot out of range");
+  // the position travels to the kernel as an argument and inputs before it read as zero: forgetting it
+  // here orders the reset behind every call already issued for the slot, on whatever stream
+  (void)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  c->pcm_t0[slot] = 0;
+  c->pcm_rate[slot] = 0;
+  return LVX_OK;
+}
+
+int lvx_pcm_convert(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const uint8_t* final_host,
+                    int sample_rate, int encoding, void* out, long long out_stride, int32_t* n_out_host, void* stream) {
+  NEED_FINAL(c);
+  const PcmRate* pr = pcm_rate_of(sample_rate);
+  if (!pr) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate) + " (24000, 16000, 8000, 48000)");
+  if (encoding != LVX_PCM_F32LE && encoding != LVX_PCM_S16LE) return fail(LVX_E_ARG, "encoding must be LVX_PCM_F32LE or LVX_PCM_S16LE");
+  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
+  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
+  const bool launch = !(pr->N == 0 && encoding == LVX_PCM_F32LE);  // 24000 Hz f32le: the rows are the output
+  const int bps = encoding == LVX_PCM_S16LE ? 2 : 4;
+  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
+    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  const int S = c->cfg.max_streams;
+  std::vector<PcmRow> rows(B);
+  {
+    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
+    // every row is checked before any slot's state changes
+    std::vector<uint8_t> seen(S, 0);
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
+      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
+      seen[s] = 1;
+      if (c->pcm_rate[s] && c->pcm_rate[s] != sample_rate)
+        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at " + std::to_string(c->pcm_rate[s]) + " Hz");
+      const long long t0 = c->pcm_t0[s];
+      const long long m0 = pcm_emitted_upto(*pr, t0, false), m1 = pcm_emitted_upto(*pr, t0 + n_in, final_host[b] != 0);
+      if (m1 - m0 > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
+      if (launch && (m1 - m0) * bps > out_stride)
+        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
+                                   std::to_string((m1 - m0) * bps) + " bytes)");
+      const int cur = (c->pcm_par[s] * S + s) * PCM_HIST, other = ((1 - c->pcm_par[s]) * S + s) * PCM_HIST;
+      const bool keep = pr->N > 0 && n_in > 0 && !final_host[b];  // a history for the segment's next call
+      rows[b] = PcmRow{t0, m0, (int)(m1 - m0), cur, keep ? other : -1, b};
+    }
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      n_out_host[b] = rows[b].n_out;
+      if (final_host[b]) {
+        c->pcm_t0[s] = 0;
+        c->pcm_rate[s] = 0;
+      } else {
+        c->pcm_t0[s] += n_in;
+        c->pcm_rate[s] = sample_rate;
+        if (rows[b].hist_out >= 0) c->pcm_par[s] ^= 1;
+      }
+    }
+  }
+  if (!launch) return LVX_OK;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
+    const int nr = std::min(PCM_ROWS, B - b0);
+    PcmRows pk{};
+    int max_out = 0;
+    bool any = false;
+    for (int k = 0; k < nr; ++k) {
+      pk.r[k] = rows[b0 + k];
+      max_out = std::max(max_out, pk.r[k].n_out);
+      any = any || pk.r[k].n_out > 0 || pk.r[k].hist_out >= 0;
+    }
+    if (!any) continue;  // (a flush with nothing left, or fewer inputs so far than the filter's delay and none to keep)
+    pcm_launch_convert(sample_rate, encoding, pk, nr, max_out, pcm, n_in, c->pcm_taps + pr->tap_off, c->pcm_hist, out,
+                       out_stride, (hipStream_t)stream);
+  }
   HIP_TRY(hipGetLastError());
   return LVX_OK;
 }

@@ -225,4 +225,22 @@ void enc_launch_lstm_step(const float* gin, const float* whh, const float* bhh, 
 void enc_launch_vq(const float* emb, const float* scores, const float* esq, const float* cb, int32_t* codes,
                    float* feats, int B, int T, hipStream_t s);
 
+// ---------------- PCM output stage (pcm_kernels.hip) ----------------
+constexpr int PCM_HIST = 160;  // inputs of history a slot keeps between calls (the filters reach back <= 144)
+constexpr int PCM_ROWS = 32;   // rows of one launch (their descriptors travel as kernel arguments)
+struct PcmRow {
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long m0;  // outputs of the segment emitted before this call = index of the call's first output
+  int n_out;     // outputs of this call
+  int hist_in;   // float offset of the slot's history [PCM_HIST] (inputs t0 - 160 .. t0 - 1) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int row;       // row of pcm / out
+};
+struct PcmRows {
+  PcmRow r[PCM_ROWS];
+};
+// one launch for n_rows <= PCM_ROWS rows; sample_rate 24000 = no filter (elementwise quantisation)
+void pcm_launch_convert(int sample_rate, int enc, const PcmRows& rows, int n_rows, int max_out, const float* pcm,
+                        int n_in, const float* taps, float* hist, void* out, long long out_stride, hipStream_t s);
+
 }  // namespace lvx

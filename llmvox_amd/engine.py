@@ -189,6 +189,53 @@ class Engine:
                                                    self.stream_handle()))
         return pcm
 
+    # ---- PCM output stage ------------------------------------------------------------
+    def pcm_filter(self, sample_rate: int):
+        """(L, M, N, taps float32 [2 N + 1]) of an output rate, as the library designs them (lvx_pcm_filter)."""
+        L, M, N = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(self.lib.lvx_pcm_filter(int(sample_rate), ctypes.byref(L), ctypes.byref(M), ctypes.byref(N), None, 0))
+        taps = np.zeros(2 * N.value + 1, dtype=np.float32)
+        _lib.check(self.lib.lvx_pcm_filter(int(sample_rate), None, None, None, taps.ctypes.data_as(ctypes.c_void_p),
+                                           taps.size))
+        return L.value, M.value, N.value, taps
+
+    def pcm_reset(self, slot: int):
+        """Forget the slot's output-stage history and position: its next ``pcm_convert`` starts a segment."""
+        _lib.check(self.lib.lvx_pcm_reset(self.h, int(slot), self.stream_handle()))
+
+    def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
+        """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
+        segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
+        ``audio.AudioFormat`` (its rate and encoding). Returns (out, counts): a device tensor [B, width] of
+        int16 or float32 whose row b holds counts[b] samples. Asynchronous on the current stream; a slot's
+        calls must be issued in order on one stream (lvx_pcm_convert)."""
+        slots = [int(s) for s in slots]
+        B = len(slots)
+        n_in = 0 if pcm is None else int(pcm.shape[1])
+        if pcm is not None:
+            if pcm.shape[0] != B or pcm.dtype != torch.float32 or pcm.device != self.device:
+                raise ValueError(f"pcm must be a float32 [{B}, n_in] tensor on {self.device}")
+            pcm = pcm.contiguous()
+        s16 = fmt.encoding == "s16le"
+        if not fmt.converts:  # 24 kHz f32le: the rows are the output (nothing is launched)
+            if pcm is None:
+                pcm = torch.empty(B, 0, device=self.device, dtype=torch.float32)
+            out, width = pcm, n_in
+        else:
+            L, M, N = (ctypes.c_int() for _ in range(3))
+            _lib.check(self.lib.lvx_pcm_filter(fmt.sample_rate, ctypes.byref(L), ctypes.byref(M), ctypes.byref(N), None, 0))
+            # a call emits at most (n_in L + L + N) / M + 2 samples (a final call of a segment whose earlier
+            # outputs waited for their right-hand inputs); rows start on 16-byte boundaries
+            width = ((n_in * L.value + L.value + N.value) // M.value + 3 + 7) // 8 * 8
+            out = torch.empty(B, width, device=self.device, dtype=torch.int16 if s16 else torch.float32)
+        sl = (ctypes.c_int32 * B)(*slots)
+        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
+        cnt = (ctypes.c_int32 * B)()
+        _lib.check(self.lib.lvx_pcm_convert(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, fmt.sample_rate,
+                                            _lib.LVX_PCM_S16LE if s16 else _lib.LVX_PCM_F32LE, _ptr(out),
+                                            width * (2 if s16 else 4), cnt, self.stream_handle()))
+        return out, list(cnt)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.lvx_destroy(self.h)

@@ -55,6 +55,7 @@ class _Session:
         self.worker = worker
         self.done = False
         self.error: Optional[BaseException] = None
+        self.audio = None  # the request's audio.AudioFormat (None: headerless f32le at 24 kHz)
 
 
 class _Worker:
@@ -118,6 +119,12 @@ class _Worker:
                     try:
                         self.sched.queue_tail(st, toks)
                     except BaseException as e:  # (serial: decoded now) the request fails, the device stays
+                        s.error = s.error or e
+                elif st.fed and st.audio is not None and st.pcm_open:
+                    # stopped on a dump boundary: the resampler still holds the end of the last dump
+                    try:
+                        self.sched.queue_tail(st, [])
+                    except BaseException as e:
                         s.error = s.error or e
         sched = self.sched
 
@@ -238,9 +245,12 @@ class TTSService:
         G = len(self.workers)
         return [self.workers[(k + i) % G] for i in range(G)]
 
-    def submit(self, text: str, sampling=None) -> _Session:
+    def submit(self, text: str, sampling=None, audio=None) -> _Session:
         """``sampling``: a ``sampling.Sampling`` makes the request's streams draw their tokens (seeded
         temperature / top-k; the replicas and the sentences each from a seed of their own), None: greedy.
+        ``audio``: an ``audio.AudioFormat``: the sample rate and encoding of the request's chunks (converted
+        on the device, every sentence resampled as a signal of its own) and whether ``chunks`` starts with a
+        WAV header; None: headerless f32le at 24 kHz, the reference's stream.
         Open the request's two replica streams on the first device (round robin from k mod G)
         that is in service and has two free KV slots. Requests run for different lengths, so the
         devices fill unevenly: a full device passes the request on instead of refusing it (ADVICE
@@ -254,16 +264,19 @@ class TTSService:
             with w.lock:
                 if w.error is not None or len(w.sched.free_slots) < 2:
                     continue
-                return self._open(w, text, queues, sampling)
+                return self._open(w, text, queues, sampling, audio)
         if not in_service:
             raise RuntimeError("TTS scheduler thread failed") from self.workers[0].error
         raise RuntimeError("no free KV slots: too many concurrent requests")
 
-    def _open(self, w: _Worker, text: str, queues, sampling=None) -> _Session:  # (caller holds w.lock)
+    def _open(self, w: _Worker, text: str, queues, sampling=None, audio=None) -> _Session:  # (caller holds w.lock)
         kw = {} if sampling is None else {"sampling": sampling}
+        if audio is not None and audio.converts:
+            kw["audio"] = audio
         streams = [w.sched.open_stream(index=i, dump_size=self.dumps[i], sink=queues[i], eoa_id=self.eoa_id, **kw)
                    for i in range(2)]
         s = _Session(streams, queues, w)
+        s.audio = audio
 
         class _Feed:  # route_text puts words on "queues"; here they go straight to the streams
             def __init__(self, st):
@@ -306,6 +319,9 @@ class TTSService:
     def chunks(self, session: _Session, timeout: float = 0.05):
         w = session.worker
         try:
+            if session.audio is not None and session.audio.container == "wav":
+                from .audio import wav_header
+                yield wav_header(session.audio)
             for item in audio_chunks(session.queues[0], session.queues[1], timeout=timeout,
                                      stop=lambda: w.error is not None):
                 yield item
@@ -336,27 +352,47 @@ class TTSService:
                 w.sched.close()
 
 
-def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0):
+def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
+               encoding: str = "f32le", container: str = "raw"):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
     (>= 0, finite; 0: greedy), ``top_k`` (>= 0; 0: no crop) and ``seed`` (int >= 0; absent with a
     temperature > 0: drawn from os.urandom), the reference's GPT.generate controls; ``temperature`` /
-    ``top_k`` here are the defaults of requests that name none of the three. Invalid values: 422. The reference's /voicechat,
+    ``top_k`` here are the defaults of requests that name none of the three. Invalid values: 422. A request
+    may also name its audio format: ``sample_rate`` (24000, 16000, 8000, 48000), ``encoding`` ("f32le",
+    "s16le") and ``container`` ("raw", "wav": a 44-byte header of a stream of unknown length first); a
+    field it leaves out takes the default given here; invalid values: 422. The response says what it
+    carries in ``X-Audio-Sample-Rate`` / ``X-Audio-Encoding`` and its media type (audio/wav for the wav
+    container). The reference's /voicechat,
     /multimodalchat and /vlmschat differ from /tts only in the producer (ASR / multimodal LLM,
     out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import StreamingResponse
     from pydantic import BaseModel
 
+    from .audio import AudioFormat
     from .sampling import Sampling
     Sampling(temperature, top_k)  # (the defaults are validated at start-up)
+    default_audio = AudioFormat(sample_rate, encoding, container)
 
     class TTSRequest(BaseModel):
         text: str
         temperature: Optional[float] = None
         top_k: Optional[int] = None
         seed: Optional[int] = None
+        sample_rate: Optional[int] = None
+        encoding: Optional[str] = None
+        container: Optional[str] = None
+
+    def audio_of(request):
+        """The request's AudioFormat (the defaults for the fields it does not name)."""
+        try:
+            return AudioFormat(default_audio.sample_rate if request.sample_rate is None else request.sample_rate,
+                               default_audio.encoding if request.encoding is None else request.encoding,
+                               default_audio.container if request.container is None else request.container)
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
 
     def sampling_of(request):
         """The request's Sampling, or None for a greedy request (then submit gets the text alone)."""
@@ -387,11 +423,16 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     @app.post("/tts")
     def tts(request: TTSRequest):
         sp = sampling_of(request)
+        fmt = audio_of(request)
+        kw = {} if sp is None else {"sampling": sp}
+        if not fmt.is_default:  # (a default request reaches submit exactly as it always did)
+            kw["audio"] = fmt
         try:
-            session = service.submit(request.text) if sp is None else service.submit(request.text, sampling=sp)
+            session = service.submit(request.text, **kw)
         except RuntimeError as e:
             raise HTTPException(status_code=503, detail=str(e))
-        return StreamingResponse(service.chunks(session), media_type="application/octet-stream")
+        return StreamingResponse(service.chunks(session), media_type=fmt.media_type,
+                                 headers={"X-Audio-Sample-Rate": str(fmt.sample_rate), "X-Audio-Encoding": fmt.encoding})
 
     @app.get("/health")
     def health():
@@ -424,6 +465,10 @@ def main(argv=None):
     ap.add_argument("--temperature", type=float, default=0.0,
                     help="sampling temperature of requests that name no sampling field (0: greedy)")
     ap.add_argument("--top-k", type=int, default=0, help="their top-k crop (0: none)")
+    ap.add_argument("--sample-rate", type=int, default=24000, choices=[24000, 16000, 8000, 48000],
+                    help="output sample rate of requests that name none")
+    ap.add_argument("--encoding", default="f32le", choices=["f32le", "s16le"], help="their sample encoding")
+    ap.add_argument("--container", default="raw", choices=["raw", "wav"], help="their container (wav: a header first)")
     a = ap.parse_args(argv)
     from .engine import build_engine
     from . import weights as W
@@ -448,7 +493,8 @@ def main(argv=None):
                           "llm_max_tokens": a.llm_max_tokens}).load()
     svc = TTSService(engines, stream_model=sm)
     import uvicorn
-    uvicorn.run(create_app(svc, temperature=a.temperature, top_k=a.top_k), host=a.host, port=a.port)
+    uvicorn.run(create_app(svc, temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate,
+                           encoding=a.encoding, container=a.container), host=a.host, port=a.port)
 
 
 if __name__ == "__main__":

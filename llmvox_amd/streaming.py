@@ -412,6 +412,8 @@ class FusedStream:
         self.sampling = None             # a sampling.Sampling: the slot draws its tokens (open_stream)
         self.index = 0                   # replica index of the request (enters the segment seeds)
         self.segment = 0                 # sentences ended so far: each one draws from a seed of its own
+        self.audio = None                # an audio.AudioFormat that converts: the dumps pass the PCM output stage
+        self.pcm_open = False            # the sentence has dumps behind it that its filter has not been flushed after
 
     def feed(self, word):
         self.fed = True
@@ -509,6 +511,60 @@ class _Deliverer:
         _LIVE_DELIVERERS.discard(self)
 
 
+class _PcmPass:
+    """The PCM output-stage calls of one chunk's dumps (streams opened with ``audio``). A slot's calls
+    must reach the engine in dump order, whatever order the codec groups are decoded in, and no call may
+    name a slot twice: ``run()`` converts, in rounds, every dump that is the next one of its stream and
+    whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding), and leaves the
+    others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
+
+    def __init__(self, sched, dumps, finals):
+        self.sched, self.dumps, self.finals = sched, dumps, finals
+        self.seq: Dict[FusedStream, Deque[int]] = {}  # stream -> its dumps still to convert, in dump order
+        self.where: Dict[int, tuple] = {}             # dump -> (its codec call's PCM rows or None, its row)
+        for i, (st, toks) in enumerate(dumps):
+            if st is not None and st.audio is not None:
+                self.seq.setdefault(st, deque()).append(i)
+                if not toks:
+                    self.where[i] = (None, 0)
+
+    def converts(self, i) -> bool:
+        st = self.dumps[i][0]
+        return st is not None and st.audio is not None
+
+    def decoded(self, grp, out):
+        for k, i in enumerate(grp):
+            self.where[i] = (out, k)
+
+    def run(self):
+        """Queue (on the current stream) the calls whose turn has come: [(dump indices, out, counts)]."""
+        eng, calls = self.sched.engine, []
+        while True:
+            buckets: Dict[tuple, List[int]] = {}
+            for st, q in self.seq.items():
+                if not q or q[0] not in self.where:
+                    continue
+                i = q.popleft()
+                if st in self.sched.failed:  # a codec error ended it: nothing more is delivered to it
+                    eng.pcm_reset(st.slot)
+                    continue
+                buckets.setdefault((id(self.where[i][0]), st.audio.sample_rate, st.audio.encoding), []).append(i)
+            if not buckets:
+                return calls
+            for idx in buckets.values():
+                out = self.where[idx[0]][0]
+                rows = [self.where[i][1] for i in idx]
+                if out is None:
+                    pcm = None
+                elif rows == list(range(rows[0], rows[0] + len(rows))):
+                    pcm = out[rows[0]:rows[0] + len(rows)]
+                else:
+                    pcm = out[rows]
+                o, counts = eng.pcm_convert(pcm, [self.dumps[i][0].slot for i in idx],
+                                            [i in self.finals for i in idx], self.dumps[idx[0]][0].audio)
+                calls.append((idx, o, counts))
+
+
 class FusedScheduler:
     """Continuous batching of many replica streams on one Engine.
 
@@ -593,21 +649,33 @@ class FusedScheduler:
                 "tok_h": torch.zeros((R, n), dtype=torch.int32, pin_memory=pin),
                 "err_h": torch.zeros((1,), dtype=torch.int32, pin_memory=pin)}
 
-    def open_stream(self, index=0, dump_size=C.INITIAL_DUMP_SIZE_1, sink=None, sampling=None, **kw) -> FusedStream:
+    def open_stream(self, index=0, dump_size=C.INITIAL_DUMP_SIZE_1, sink=None, sampling=None, audio=None,
+                    **kw) -> FusedStream:
         """sampling: a ``sampling.Sampling`` (temperature > 0) makes the stream draw its tokens, every
         sentence from ``segment_seed(seed, index, sentence)``; None (or temperature 0): greedy, and the
-        engine's ``set_sampling`` is never called."""
+        engine's ``set_sampling`` is never called.
+        audio: an ``audio.AudioFormat`` with another rate or encoding than f32le at 24 kHz: every dump of
+        the stream is converted on the device (``Engine.pcm_convert``), behind its codec call on the same
+        stream, each sentence as a signal of its own, and the stream's items are those samples (int16 /
+        float32 arrays with ``to_bytes=False``). None (or 24 kHz f32le): today's items, and the engine's
+        ``pcm_*`` are never called."""
         if sampling is not None and not sampling.temperature > 0:
             sampling = None
         if sampling is not None and not hasattr(self.engine, "set_sampling"):
             raise RuntimeError("this engine cannot sample (it has no set_sampling): open the stream without `sampling`")
+        if audio is not None and not audio.converts:
+            audio = None
+        if audio is not None and not hasattr(self.engine, "pcm_convert"):
+            raise RuntimeError("this engine has no PCM output stage (no pcm_convert): open the stream without `audio`")
         if not self.free_slots:
             raise RuntimeError("no free KV slot")
         slot = self.free_slots.pop()
         st = FusedStream(self, slot, SegmentMachine(index=index, dump_size=dump_size, **kw), sink)
-        st.sampling, st.index = sampling, index
+        st.sampling, st.index, st.audio = sampling, index, audio
         with self._on_ar():
             self.engine.reset_slot(slot)  # (stream-ordered behind any chunk in flight on the slot)
+            if audio is not None:
+                self.engine.pcm_reset(slot)
             self._seed_segment(st)
         self.streams.append(st)
         return st
@@ -625,6 +693,8 @@ class FusedScheduler:
         if st.sampling is not None:  # the slot's next stream starts greedy (behind this one's chunks in flight)
             with self._on_ar():
                 self.engine.set_sampling(st.slot, 0.0, 0, 0)
+        if st.audio is not None:  # (an unfinished sentence's filter state goes with it)
+            self.engine.pcm_reset(st.slot)
 
     def close(self):
         """Stop the delivery thread (after delivering what is queued)."""
@@ -826,10 +896,11 @@ class FusedScheduler:
         # position 0 by the end of audio: it continues, as the reference would
         at_cap -= ended
         codec_err = None
+        finals = self._mark_finals(dumps, order)  # (None: no stream of the chunk converts its audio)
         if self.overlap:
-            self._launch_decode(dumps, order, ch.ready)
+            self._launch_decode(dumps, order, ch.ready, finals)
         else:
-            pcm, codec_err = self._decode(dumps)
+            pcm, codec_err = self._decode(dumps, finals)
             self._deliver(pcm, order, ch.ready)
         if err is not None:
             if self.deliverer is not None:
@@ -881,24 +952,72 @@ class FusedScheduler:
         """Dump indices batched by length (one codec call per group, within max_codec_frames)."""
         by_len: Dict[int, List[int]] = {}
         for i, (_, toks) in enumerate(dumps):
-            by_len.setdefault(len(toks), []).append(i)
+            if toks:  # (no tokens: a flush of the PCM output stage, _mark_finals)
+                by_len.setdefault(len(toks), []).append(i)
         for L, idx in by_len.items():
             cap = max(1, self.engine.max_codec_frames // L)
             for s in range(0, len(idx), cap):
                 yield L, idx[s:s + cap]
 
-    def _decode(self, dumps):
+    def _mark_finals(self, dumps, order):
+        """The PCM output stage's view of a chunk's (or a tail's) items: the dumps that end a sentence, for
+        the streams that convert their audio. A dump is final when the stream's next item is a signal; a
+        sentence that ends with no dump behind its last audio (the max_audio_length reset drops its
+        outputs) gets a flush appended to ``dumps`` (no tokens) and queued in front of its signal, so every
+        sentence delivers exactly ceil(T L / M) samples. Returns the set of final dump indices, or None
+        when no stream with items converts (the caller then takes today's path, call for call)."""
+        finals = None
+        for st, items in order.items():
+            if st.audio is None or not items:
+                continue
+            finals = set() if finals is None else finals
+            k = 0
+            while k < len(items):
+                kind, v = items[k]
+                if kind == "audio":
+                    st.pcm_open = not (k + 1 < len(items) and items[k + 1][0] == "signal")
+                    if not st.pcm_open:
+                        finals.add(v)
+                elif st.pcm_open:
+                    dumps.append((st, []))
+                    items.insert(k, ("audio", len(dumps) - 1))
+                    finals.add(len(dumps) - 1)
+                    st.pcm_open = False
+                    k += 1
+                k += 1
+        return finals
+
+    def _host_item(self, a):
+        return a.tobytes() if self.to_bytes else a.copy()
+
+    def _decode(self, dumps, finals=None):
         """Every dump decoded now (one call per length group), host-synchronous. Returns (PCM per dump,
         None or the LvxStreamError naming the streams of the groups whose codec error word was set:
-        the other groups' PCM is valid and delivered)."""
+        the other groups' PCM is valid and delivered). ``finals`` (_mark_finals; None: no dump is
+        converted): the dumps of streams with an audio format go through the PCM output stage behind their
+        codec call, and only their converted rows are copied to the host."""
         torch = self.torch
         res: List[object] = [None] * len(dumps)
         first, bad = None, []
+        pp = _PcmPass(self, dumps, finals) if finals is not None else None
+
+        def converted():
+            for idx, o, counts in pp.run():
+                host = o.cpu().numpy()
+                for r, i in enumerate(idx):
+                    res[i] = self._host_item(host[r, :counts[r]])
+
         for L, grp in self._groups(dumps):
             codes = torch.tensor([dumps[i][1] for i in grp], dtype=torch.int32, device=self.engine.device)
-            out = self.engine.decode_codes(codes).cpu().numpy()
-            for k, i in enumerate(grp):
-                res[i] = out[k].astype("float32").tobytes() if self.to_bytes else out[k]
+            dev_out = self.engine.decode_codes(codes)
+            plain = [k for k, i in enumerate(grp) if pp is None or not pp.converts(i)]
+            if plain:  # (the rows delivered as the codec wrote them; all of them without an audio format)
+                out = (dev_out if len(plain) == len(grp) else dev_out[plain]).cpu().numpy()
+                for r, k in enumerate(plain):
+                    res[grp[k]] = out[r].astype("float32").tobytes() if self.to_bytes else out[r]
+            if pp is not None:
+                pp.decoded(grp, dev_out)
+                converted()
             if self.codec_take:  # the codec's own error word, per group
                 from . import _lib
                 e = torch.zeros((1,), dtype=torch.int32, device=self.engine.device)
@@ -908,6 +1027,8 @@ class FusedScheduler:
                 except _lib.LvxError as exc:
                     first = first or exc
                     bad += [dumps[i][0] for i in grp]
+        if pp is not None:
+            converted()  # (flushes of streams without a dump in the chunk)
         return res, (self._codec_failure(first, bad) if first is not None else None)
 
     def decode_now(self, tokens: List[int]):
@@ -923,11 +1044,28 @@ class FusedScheduler:
     def queue_tail(self, st: FusedStream, tokens: List[int]):
         """The stream's undumped tail decoded as one last dump and delivered AFTER every item already
         queued for it (the service's end of a request). Overlap: queued on the codec stream, delivered by
-        the delivery thread behind its event (the caller never waits for the device); serial: now."""
+        the delivery thread behind its event (the caller never waits for the device); serial: now.
+        A stream with an audio format: the tail ends its sentence (a final dump of the PCM output stage);
+        no tokens: only the flush of the dumps already delivered."""
+        dumps, order = [(st, tokens)], {st: [("audio", 0)]}
+        if st.audio is not None:
+            if not tokens and not st.pcm_open:
+                return
+            st.pcm_open = False
+            if self.deliverer is None:
+                with (self.torch.cuda.stream(self.codec_stream) if self.codec_stream is not None
+                      else contextlib.nullcontext()):
+                    res, err = self._decode(dumps, {0})
+                if err is not None:
+                    raise err
+                st._out(res[0])
+            else:
+                self._launch_decode(dumps, order, [st], {0})
+            return
         if self.deliverer is None:
             st._out(self.decode_now(tokens))
             return
-        self._launch_decode([(st, tokens)], {st: [("audio", 0)]}, [st])
+        self._launch_decode(dumps, order, [st])
 
     def after_delivered(self, fn):
         """fn() once every item queued so far has been delivered (in the delivery order)."""
@@ -936,21 +1074,25 @@ class FusedScheduler:
         else:
             self.deliverer.put(None, fn)
 
-    def _launch_decode(self, dumps, order, ready):
+    def _launch_decode(self, dumps, order, ready, finals=None):
         """Queue the chunk's decodes on the codec stream (codes from the host: no wait on the AR
         stream), one call per dump length, shortest first, each with its PCM copied into pinned host
         memory and a delivery job behind its own event: a stream's items go out with the job of its
         (last) dump as soon as that call ends; a 10-frame first dump does not wait for a 1,280-frame one
-        of the same chunk. Streams without a dump in the chunk are served by the first job."""
+        of the same chunk. Streams without a dump in the chunk are served by the first job.
+        ``finals`` (_mark_finals): some stream converts its audio, see _launch_decode_audio."""
         torch = self.torch
         if not self.cuda:  # a stand-in engine: decode now, deliver in order through the same thread
-            pcm, err = self._decode(dumps)
+            pcm, err = self._decode(dumps, finals)
 
             def job():
                 self._deliver(pcm, order, ready)
                 if err is not None:
                     raise err
             self.deliverer.put(None, job)
+            return
+        if finals is not None:
+            self._launch_decode_audio(dumps, order, ready, finals)
             return
         groups = sorted(self._groups(dumps), key=lambda g: g[0])
         if not groups:
@@ -996,6 +1138,85 @@ class FusedScheduler:
                     raise exc
 
             self.deliverer.put(ev, deliver)
+
+    def _launch_decode_audio(self, dumps, order, ready, finals):
+        """_launch_decode for a chunk in which some stream converts its audio: the same codec calls in the
+        same order; behind each, on the codec stream, the PCM output-stage calls whose turn has come
+        (_PcmPass), and the copies to pinned host memory of exactly what is delivered: the f32 rows of the
+        streams without a format, the converted rows of the others. The job behind a call's event hands out
+        the rows that are on the host by then and serves every stream all of whose dumps are."""
+        torch = self.torch
+        from . import _lib
+        dev = self.engine.device
+        groups = sorted(self._groups(dumps), key=lambda g: g[0])
+        pp = _PcmPass(self, dumps, finals)
+        nd = len(dumps)
+        pcm: List[object] = [None] * nd  # filled by the jobs, in order
+        on_host = set()                  # dumps whose rows' copies are queued (known when a job is put)
+        served = set()
+
+        def convert(fills, keep):
+            for idx, o, counts in pp.run():
+                h = torch.empty(o.shape, dtype=o.dtype, pin_memory=True)
+                h.copy_(o, non_blocking=True)
+                keep.append(o)
+                for r, i in enumerate(idx):
+                    fills.append((i, h, r, counts[r]))
+                    on_host.add(i)
+
+        def put(ev, fills, err_h, grp, keep):
+            sts = [st for st in ready if st not in served
+                   and all(v in on_host for kind, v in order[st] if kind == "audio")]
+            served.update(sts)
+
+            def deliver():  # (keep: the device rows and the codes, alive until their copies have run)
+                exc = None
+                if err_h is not None:
+                    try:
+                        _lib.check_bits(int(err_h[0]))
+                    except _lib.LvxError as e:
+                        exc = self._codec_failure(e, [dumps[i][0] for i in grp])
+                for i, h, r, n in fills:
+                    if dumps[i][0] not in self.failed:
+                        pcm[i] = self._host_item(h[r, :n].numpy())
+                self._deliver(pcm, order, sts)
+                keep.clear()
+                if exc is not None:
+                    raise exc
+
+            self.deliverer.put(ev, deliver)
+
+        for L, grp in groups:
+            fills, keep = [], []
+            err_h = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
+            codes = torch.tensor([dumps[i][1] for i in grp], dtype=torch.int32).pin_memory()
+            keep.append(codes)
+            with torch.cuda.stream(self.codec_stream):
+                out = self.engine.decode_codes(codes.to(dev, non_blocking=True))
+                plain = [k for k, i in enumerate(grp) if not pp.converts(i)]
+                if plain:
+                    sub = out if len(plain) == len(grp) else out[plain]
+                    h = torch.empty(sub.shape, dtype=torch.float32, pin_memory=True)
+                    h.copy_(sub, non_blocking=True)
+                    keep.append(sub)
+                    for r, k in enumerate(plain):
+                        fills.append((grp[k], h, r, 320 * L))
+                        on_host.add(grp[k])
+                err_d = torch.zeros((1,), dtype=torch.int32, device=dev)
+                self.engine.take_errors(_lib.ERRW_CODEC, err_d)
+                err_h.copy_(err_d, non_blocking=True)
+                pp.decoded(grp, out)
+                convert(fills, keep)
+                ev = torch.cuda.Event()
+                ev.record(self.codec_stream)
+            put(ev, fills, err_h, grp, keep)
+        if not groups or len(served) < len(ready):  # flushes (and signals) of streams without a dump in the chunk
+            fills, keep = [], []
+            with torch.cuda.stream(self.codec_stream):
+                convert(fills, keep)
+                ev = torch.cuda.Event()
+                ev.record(self.codec_stream)
+            put(ev, fills, None, [], keep)
 
     def flush(self):
         """Complete every chunk in flight and deliver everything queued."""
