@@ -309,6 +309,63 @@ int lvx_pcm_convert(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const i
                     const uint8_t* final_host, int sample_rate, int encoding, void* out_dev,
                     long long out_stride_bytes, int32_t* n_out_host, void* stream);
 
+/* ---- PCM time stretch ---------------------------------------------------------
+ * The speaking-rate control. LLMVoX has no model-side handle for speed (one speech token per decode
+ * step, the length decided by end-of-audio), so a stream that asks for another speed has the codec's
+ * f32 rows time-stretched on the device, pitch preserved, BEFORE the resampling and quantisation above:
+ * waveform-similarity overlap-add (WSOLA) at 24 kHz. A stream at speed 100 never comes here. Everything
+ * is integer or fp32 arithmetic in ONE fixed order, so the device output is bit-identical to a host
+ * evaluation of the same order (llmvox_amd/audio.py: stretch_ref) and INDEPENDENT OF CHUNKING.
+ *
+ * Constants: H = 240 (the output hop, 10 ms), D = 240 (the search radius), C = 480 (the correlation
+ * length); speed_pct an integer in [50, 200], 100 = no stretch. The nominal analysis position of hop j
+ * is a_j = (j H speed_pct) / 100 in integer (floor) arithmetic.
+ *
+ * Windows, built on the host in double and stored as fp32 (lvx_pcm_stretch_window):
+ *   wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / H), n = 0 .. H - 1;  wf[n] = 1 - wr[n] (subtracted in double;
+ *   each table rounded once).
+ *
+ * One segment is one sentence of one stream: x[0 .. T), zero outside. p_{-1} = -H. Hop j writes
+ * y[j H .. j H + H); e_j = p_{j-1} + H is where the previous frame would naturally continue.
+ *   j = 0: d_0 = 0, p_0 = 0.
+ *   j >= 1: for every d in [-D, D], c = a_j + d:
+ *     corr_d = sum for k = 0 .. C - 1, ascending, of fl(x[c + k] x[e_j + k]),
+ *     en_d   = the same sequential sum of fl(x[c + k] x[c + k])
+ *     (acc = 0, then acc = fl(acc + fl(product)): every product and every sum rounded to fp32, no fused
+ *     multiply-add),
+ *     score_d = fl(fl(corr_d |corr_d|) / fl(en_d + 1e-9f)), IEEE division; a NaN score counts as -inf.
+ *     d_j = the d with the largest score; among equal scores (+0 and -0 are equal) the smallest |d|, of
+ *     +-d the negative one; all scores equal (silence) gives d_j = 0. p_j = a_j + d_j.
+ *   y[j H + n] = fl(fl(x[e_j + n] wf[n]) + fl(x[p_j + n] wr[n])), n = 0 .. H - 1.
+ * Every output hop is complete when written: there is no overlap-add tail to carry.
+ *
+ * Counts. The segment delivers ceil(T 100 / speed_pct) samples; the last hop is cut there. With
+ *   need_0 = 2 H,  need_j = max(a_j + D + 2 H, a_{j-1} + D + 3 H)  (j >= 1),
+ * hop j reads no input at or after need_j. After a non-final call that brings the consumed input to T
+ * the emitted hops are exactly the j with need_j <= T, each as H whole samples; a final call emits the
+ * rest, up to the total. A hop reaches back at most 1199 inputs before need_j - 1, so the library keeps,
+ * per KV slot, the last 1280 inputs of the previous call (two buffers per slot: a launch reads one and
+ * writes the other) and d_{j-1}, one int that stays on the device; on the host, a mirror of the slot's
+ * consumed input, emitted hops and speed_pct: a slot's calls are issued in order on one stream. A
+ * segment has one speed: another speed_pct before its final call is LVX_E_ARG. */
+/* host only: the fp32 window tables wr[0 .. 240) and wf[0 .. 240). LVX_E_ARG: a null table, cap < 240. */
+int lvx_pcm_stretch_window(float* wr_host, float* wf_host, int cap);
+/* host only: samples a stretch call emits for a slot that has consumed t0 inputs of its segment
+ * (speed_pct 100: n_in; negative: LVX_E_ARG for speed_pct outside [50, 200], t0 < 0 or n_in < 0) */
+int lvx_pcm_stretch_emitted(int speed_pct, long long t0, int n_in, int final);
+/* lvx_pcm_convert's conventions: rows b of pcm_dev [B][n_in] f32 continue the stretch segments of
+ * slots_host[b]; final_host[b] != 0 emits the rest and resets the slot; n_in may be 0 with final (flush
+ * only). out row b (f32) starts at out_dev + b * out_stride_bytes; n_out_host[b] = samples written.
+ * d_out_dev (optional, may be NULL): row b's chosen d_j of the hops this call emits, int32 at
+ * d_out_dev + b * d_stride. speed_pct 100: nothing is launched and nothing written, the rows of pcm_dev
+ * are the output (n_out_host[b] = n_in; out_dev may be NULL). LVX_E_ARG (and no slot's state changed):
+ * speed_pct outside [50, 200] or another than the slot's open segment has, B < 1, n_in < 0, a slot out
+ * of range or named twice, out_dev or out_stride_bytes not a multiple of 4, out_stride_bytes smaller than
+ * a row's output, d_stride smaller than a row's hops. lvx_pcm_reset also forgets a slot's stretch state. */
+int lvx_pcm_stretch(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
+                    const uint8_t* final_host, int speed_pct, float* out_dev, long long out_stride_bytes,
+                    int32_t* n_out_host, int32_t* d_out_dev, int d_stride, void* stream);
+
 /* ---- WavTokenizer encoder, a context of its own (its weights are not needed for TTS).
  * Replaces WavTokenizer.encode_infer (WavTokenizer/decoder/pretrained.py:185-190 ->
  * decoder/feature_extractors.py:122-133): SEANet encoder (encoder/modules/seanet.py:94-143) + the

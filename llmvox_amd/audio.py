@@ -1,7 +1,9 @@
 """Audio output formats of the service and the numpy reference of the PCM output stage's rule
 (include/llmvox.h, "PCM output stage": the rates, the prototype filter, the streaming counts, the fixed
 fp32 summation order and the s16le quantisation). The device stage is ``Engine.pcm_convert``; everything
-here runs on the host and is what the tests and the documentation compare it with."""
+here runs on the host and is what the tests and the documentation compare it with. The speaking-rate
+control ("PCM time stretch" in the same header: WSOLA on the 24 kHz rows, before the resampler) is stated
+here too: ``stretch_ref``."""
 from __future__ import annotations
 
 import struct
@@ -15,6 +17,11 @@ RATES = {24000: (1, 1, 0), 16000: (2, 3, 72), 8000: (1, 3, 72), 48000: (2, 1, 48
 ENCODINGS = ("f32le", "s16le")
 CONTAINERS = ("raw", "wav")
 HISTORY = 160  # inputs of history a slot keeps between calls
+SPEED_MIN, SPEED_MAX = 50, 200  # speed_pct of a stream (100: no stretch)
+STRETCH_H = 240         # output hop of the time stretch (10 ms)
+STRETCH_D = 240         # its search radius
+STRETCH_C = 480         # its correlation length
+STRETCH_HISTORY = 1280  # inputs of history a slot keeps between stretch calls
 
 
 @dataclass(frozen=True)
@@ -23,6 +30,7 @@ class AudioFormat:
     sample_rate: int = BASE_RATE
     encoding: str = "f32le"
     container: str = "raw"
+    speed_pct: int = 100  # speaking rate in percent (pitch-preserving time stretch of the PCM; 100: none)
 
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
@@ -31,15 +39,20 @@ class AudioFormat:
             raise ValueError(f"encoding must be one of {ENCODINGS}, got {self.encoding!r}")
         if self.container not in CONTAINERS:
             raise ValueError(f"container must be one of {CONTAINERS}, got {self.container!r}")
+        if isinstance(self.speed_pct, bool) or not isinstance(self.speed_pct, int) \
+                or not SPEED_MIN <= self.speed_pct <= SPEED_MAX:
+            raise ValueError(f"speed_pct must be an integer in [{SPEED_MIN}, {SPEED_MAX}], got {self.speed_pct!r}")
 
     @property
     def is_default(self) -> bool:
-        return self.sample_rate == BASE_RATE and self.encoding == "f32le" and self.container == "raw"
+        return (self.sample_rate == BASE_RATE and self.encoding == "f32le" and self.container == "raw"
+                and self.speed_pct == 100)
 
     @property
     def converts(self) -> bool:
-        """The samples differ from the codec's (another rate or encoding): the stream needs the device stage."""
-        return self.sample_rate != BASE_RATE or self.encoding != "f32le"
+        """The samples differ from the codec's (another rate, encoding or speed): the stream needs the device
+        stage."""
+        return self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
 
     @property
     def sample_bytes(self) -> int:
@@ -145,25 +158,153 @@ def encode_ref(y, fmt: AudioFormat) -> np.ndarray:
     return quantize_s16(y) if fmt.encoding == "s16le" else np.asarray(y, dtype=np.float32)
 
 
-def convert_ref(x, fmt: AudioFormat, taps=None) -> np.ndarray:
-    """A whole segment x (float32 at 24 kHz) in the format's rate and encoding (int16 or float32 array)."""
+# ---- the time stretch's rule (include/llmvox.h, "PCM time stretch"), in numpy -------------------------
+
+def stretch_window() -> Tuple[np.ndarray, np.ndarray]:
+    """(wr, wf) float32 [H]: the rising half-Hann window and its complement, built in double, each rounded
+    once (the library's own: ``lvx_pcm_stretch_window``)."""
+    n = np.arange(STRETCH_H, dtype=np.float64)
+    wr = 0.5 - 0.5 * np.cos(np.pi * (n + 0.5) / STRETCH_H)
+    return wr.astype(np.float32), (1.0 - wr).astype(np.float32)
+
+
+def _stretch_a(j: int, speed_pct: int) -> int:
+    return (j * STRETCH_H * speed_pct) // 100
+
+
+def _stretch_need(j: int, speed_pct: int) -> int:
+    """Inputs of the segment hop j reads (the exclusive upper end of what its search and output touch)."""
+    if j == 0:
+        return 2 * STRETCH_H
+    return max(_stretch_a(j, speed_pct) + STRETCH_D + 2 * STRETCH_H,
+               _stretch_a(j - 1, speed_pct) + STRETCH_D + 3 * STRETCH_H)
+
+
+def _stretch_hops(speed_pct: int, T: int) -> int:
+    """How many hops j have need_j <= T (need_j does not decrease with j)."""
+    n = max(0, (T - 3 * STRETCH_H) * 100 // (STRETCH_H * speed_pct)) + 2
+    while n > 0 and _stretch_need(n - 1, speed_pct) > T:
+        n -= 1
+    while _stretch_need(n, speed_pct) <= T:
+        n += 1
+    return n
+
+
+def stretch_emitted_upto(speed_pct: int, T: int, final: bool) -> int:
+    """Samples of a segment the stretch has emitted once T inputs are consumed (after a non-final / a final
+    call). speed_pct 100 is no stretch: T."""
+    if speed_pct == 100:
+        return T
+    if final:
+        return -((-T * 100) // speed_pct)
+    return STRETCH_H * _stretch_hops(speed_pct, T)
+
+
+def stretch_emitted(speed_pct: int, t0: int, n_in: int, final: bool) -> int:
+    """Samples a stretch call emits for a slot that has consumed t0 inputs of its segment
+    (``lvx_pcm_stretch_emitted``)."""
+    return stretch_emitted_upto(speed_pct, t0 + n_in, final) - stretch_emitted_upto(speed_pct, t0, False)
+
+
+def _stretch_run(x, speed_pct: int, wr, wf, j0: int, j1: int, p_prev: int, force_d0: bool = False):
+    """Hops j0 .. j1 - 1 of the segment x[0 .. T) (zero outside), continuing from p_{j0 - 1} = p_prev:
+    (samples float32 [(j1 - j0) H], d int32 [j1 - j0], p_{j1 - 1}). Every product, sum and quotient is an fp32
+    operation in the rule's order: the bits the device computes."""
+    H, D, C = STRETCH_H, STRETCH_D, STRETCH_C
+    x = np.asarray(x, dtype=np.float32).reshape(-1)
+    lo = D + H  # the lowest input a hop reads is a_1 - D >= -D
+    hi = _stretch_need(max(j1 - 1, 0), speed_pct) + H
+    xp = np.zeros(lo + max(x.size, hi), dtype=np.float32)
+    xp[lo:lo + x.size] = x
+    y = np.zeros((j1 - j0) * H, dtype=np.float32)
+    ds = np.zeros(j1 - j0, dtype=np.int32)
+    eps = np.float32(1e-9)
+    zero = np.zeros((2 * D + 1, 1), dtype=np.float32)
+    for j in range(j0, j1):
+        a = _stretch_a(j, speed_pct)
+        e = p_prev + H
+        d = 0
+        if j >= 1 and not force_d0:
+            span = xp[lo + a - D:lo + a + D + C]  # the candidates' inputs: 2 D + C of them
+            tmpl = xp[lo + e:lo + e + C]
+            cand = np.lib.stride_tricks.sliding_window_view(span, C)  # [2 D + 1, C]
+            with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
+                # acc = 0, then acc = fl(acc + fl(product)) for k ascending: what an fp32 accumulate does
+                corr = np.add.accumulate(np.concatenate([zero, cand * tmpl], axis=1), axis=1, dtype=np.float32)[:, -1]
+                en = np.add.accumulate(np.concatenate([zero, cand * cand], axis=1), axis=1, dtype=np.float32)[:, -1]
+                score = (corr * np.abs(corr)) / (en + eps)
+            score = np.where(np.isnan(score), np.float32(-np.inf), score)
+            best = np.nonzero(score == score.max())[0].astype(np.int64) - D
+            d = int(best[np.lexsort((best, np.abs(best)))[0]])  # the smallest |d|; of +-d the negative one
+        p = a + d
+        with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+            y[(j - j0) * H:(j - j0 + 1) * H] = xp[lo + e:lo + e + H] * wf + xp[lo + p:lo + p + H] * wr
+        ds[j - j0] = d
+        p_prev = p
+    return y, ds, p_prev
+
+
+def stretch_ref(x, speed_pct: int, windows=None, force_d0: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """A whole segment x (float32 at 24 kHz) time-stretched to ceil(T 100 / speed_pct) samples: (samples
+    float32, the chosen d_j of every hop int32). ``windows``: (wr, wf) fp32 tables (default: built here; the
+    device tests pass the library's). ``force_d0``: plain overlap-add at the nominal positions (every
+    d_j = 0), the yardstick of what the search buys. speed_pct 100: x itself and no hops."""
+    x = np.asarray(x, dtype=np.float32).reshape(-1)
+    if speed_pct == 100:
+        return x.copy(), np.zeros(0, dtype=np.int32)
+    wr, wf = windows if windows is not None else stretch_window()
+    total = stretch_emitted_upto(speed_pct, x.size, True)
+    hops = -(-total // STRETCH_H)
+    y, ds, _ = _stretch_run(x, speed_pct, np.asarray(wr, np.float32), np.asarray(wf, np.float32), 0, hops,
+                            -STRETCH_H, force_d0)
+    return y[:total], ds
+
+
+def convert_ref(x, fmt: AudioFormat, taps=None, windows=None) -> np.ndarray:
+    """A whole segment x (float32 at 24 kHz) at the format's speed, rate and encoding (int16 or float32
+    array): stretched, then resampled, then encoded."""
+    if fmt.speed_pct != 100:
+        x = stretch_ref(x, fmt.speed_pct, windows)[0]
     return encode_ref(resample_ref(x, fmt.sample_rate, taps), fmt)
 
 
 class StreamRef:
     """The streaming form of the rule for one slot, on the host: ``push(x, final)`` returns the samples the
-    call emits (``lvx_pcm_convert`` for one row). Keeps the whole segment; for tests and stand-in engines."""
+    call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_stretch`` when the format has a speed, then
+    ``lvx_pcm_convert``). Keeps the whole segment; for tests and stand-in engines. ``last_d``: the d_j of the
+    hops the last push emitted."""
 
-    def __init__(self, fmt: AudioFormat, taps=None):
+    def __init__(self, fmt: AudioFormat, taps=None, windows=None):
         self.fmt, self.taps = fmt, taps
-        self.seg: List[np.ndarray] = []
-        self.t0 = 0
+        if fmt.speed_pct != 100:
+            wr, wf = windows if windows is not None else stretch_window()
+            self.windows = (np.asarray(wr, dtype=np.float32), np.asarray(wf, dtype=np.float32))
+        self.last_d = np.zeros(0, dtype=np.int32)
+        self.reset()
 
     def reset(self):
-        self.seg, self.t0 = [], 0
+        self.seg: List[np.ndarray] = []
+        self.t0 = 0
+        self.raw: List[np.ndarray] = []  # the stretch's view: the segment's input, its count, hops and p_{j-1}
+        self.raw_t0, self.hops, self.p_prev = 0, 0, -STRETCH_H
+
+    def _stretch(self, x, final: bool) -> np.ndarray:
+        pct = self.fmt.speed_pct
+        self.raw.append(x)
+        self.raw_t0 += x.size
+        m0 = self.hops * STRETCH_H
+        m1 = stretch_emitted_upto(pct, self.raw_t0, final)
+        j1 = -(-m1 // STRETCH_H)
+        whole = np.concatenate(self.raw)
+        y, self.last_d, self.p_prev = _stretch_run(whole, pct, self.windows[0], self.windows[1], self.hops, j1,
+                                                   self.p_prev)
+        self.hops = j1
+        return y[:max(0, m1 - m0)]
 
     def push(self, x, final: bool) -> np.ndarray:
         x = np.asarray(x, dtype=np.float32).reshape(-1)
+        if self.fmt.speed_pct != 100:
+            x = self._stretch(x, final)
         rate = self.fmt.sample_rate
         m0 = emitted_upto(rate, self.t0, False)
         m1 = emitted_upto(rate, self.t0 + x.size, final)
@@ -177,4 +318,6 @@ class StreamRef:
 
 
 __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "resample_ref", "quantize_s16",
-           "convert_ref", "StreamRef", "RATES", "ENCODINGS", "CONTAINERS", "BASE_RATE", "HISTORY"]
+           "convert_ref", "StreamRef", "RATES", "ENCODINGS", "CONTAINERS", "BASE_RATE", "HISTORY",
+           "stretch_window", "stretch_ref", "stretch_emitted", "stretch_emitted_upto", "SPEED_MIN", "SPEED_MAX",
+           "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY"]

@@ -234,6 +234,40 @@ static long long pcm_emitted_upto(const PcmRate& pr, long long T, bool final) {
   return a < 0 ? 0 : std::min(a / pr.M + 1, all);
 }
 
+// ---- PCM time stretch: the window tables and the streaming counts (llmvox.h) ----
+// wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / H), wf[n] = 1 - wr[n] (in double), each rounded to fp32 once
+static void stretch_design(float* wr, float* wf) {
+  const double pi = 3.14159265358979323846;
+  for (int n = 0; n < STR_H; ++n) {
+    const double r = 0.5 - 0.5 * std::cos(pi * (n + 0.5) / STR_H);
+    wr[n] = (float)r;
+    wf[n] = (float)(1.0 - r);
+  }
+}
+
+static long long stretch_a(long long j, int pct) { return (j * STR_H * pct) / 100; }
+
+// inputs of the segment hop j reads: the exclusive upper end of its search and its output
+static long long stretch_need(long long j, int pct) {
+  if (j == 0) return 2 * STR_H;
+  return std::max(stretch_a(j, pct) + STR_D + 2 * STR_H, stretch_a(j - 1, pct) + STR_D + 3 * STR_H);
+}
+
+// how many hops j have need_j <= T (need_j does not decrease with j)
+static long long stretch_hops(int pct, long long T) {
+  long long n = std::max(0ll, (T - 3 * STR_H) * 100 / ((long long)STR_H * pct)) + 2;
+  while (n > 0 && stretch_need(n - 1, pct) > T) --n;
+  while (stretch_need(n, pct) <= T) ++n;
+  return n;
+}
+
+// samples of a segment emitted once T inputs are consumed
+static long long stretch_emitted_upto(int pct, long long T, bool final) {
+  if (pct == 100) return T;
+  if (final) return (T * 100 + pct - 1) / pct;
+  return STR_H * stretch_hops(pct, T);
+}
+
 struct lvx_ctx {
   lvx_config cfg{};
   std::map<std::string, std::vector<float>> host;  // staged fp32 weights (released at finalize)
@@ -261,6 +295,16 @@ struct lvx_ctx {
   std::vector<long long> pcm_t0;  // inputs of the slot's segment consumed so far
   std::vector<int> pcm_rate;      // rate of the slot's open segment, 0: none open
   std::vector<uint8_t> pcm_par;   // which of the slot's two history buffers is current
+  // PCM time stretch: the device window tables (wr then wf), the slots' history pool
+  // [2][max_streams][STR_HIST], their d_{j-1} (one int per slot, device only) and the host mirror of every
+  // slot's segment (lvx_pcm_stretch, under mu)
+  float* str_win = nullptr;
+  float* str_hist = nullptr;
+  int* str_d = nullptr;
+  std::vector<long long> str_t0;  // inputs of the slot's segment consumed so far
+  std::vector<long long> str_hops;  // hops of it emitted so far
+  std::vector<int> str_pct;       // speed of the slot's open segment, 0: none open
+  std::vector<uint8_t> str_par;   // which of the slot's two history buffers is current
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -708,6 +752,18 @@ int lvx_finalize(lvx_ctx* c) {
     c->pcm_t0.assign(S, 0);
     c->pcm_rate.assign(S, 0);
     c->pcm_par.assign(S, 0);
+    float win[2 * STR_H];
+    stretch_design(win, win + STR_H);
+    if ((r = c->dalloc(&c->str_win, 2 * STR_H)) || (r = c->dalloc(&c->str_hist, (size_t)2 * S * STR_HIST)) ||
+        (r = c->dalloc(&c->str_d, (size_t)S)))
+      return r;
+    HIP_TRY(hipMemcpy(c->str_win, win, sizeof(win), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->str_hist, 0, (size_t)2 * S * STR_HIST * 4));
+    HIP_TRY(hipMemset(c->str_d, 0, (size_t)S * 4));
+    c->str_t0.assign(S, 0);
+    c->str_hops.assign(S, 0);
+    c->str_pct.assign(S, 0);
+    c->str_par.assign(S, 0);
   }
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
@@ -1111,6 +1167,9 @@ int lvx_pcm_reset(lvx_ctx* c, int slot, void* stream) {
   std::lock_guard<std::mutex> lk(c->mu);
   c->pcm_t0[slot] = 0;
   c->pcm_rate[slot] = 0;
+  c->str_t0[slot] = 0;
+  c->str_hops[slot] = 0;
+  c->str_pct[slot] = 0;
   return LVX_OK;
 }
 
@@ -1177,6 +1236,95 @@ int lvx_pcm_convert(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t
     if (!any) continue;  // (a flush with nothing left, or fewer inputs so far than the filter's delay and none to keep)
     pcm_launch_convert(sample_rate, encoding, pk, nr, max_out, pcm, n_in, c->pcm_taps + pr->tap_off, c->pcm_hist, out,
                        out_stride, (hipStream_t)stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+// ---- PCM time stretch ----
+int lvx_pcm_stretch_window(float* wr_host, float* wf_host, int cap) {
+  if (!wr_host || !wf_host) return fail(LVX_E_ARG, "null wr_host / wf_host");
+  if (cap < STR_H) return fail(LVX_E_ARG, "wr_host / wf_host hold fewer than 240 floats");
+  stretch_design(wr_host, wf_host);
+  return LVX_OK;
+}
+
+int lvx_pcm_stretch_emitted(int speed_pct, long long t0, int n_in, int final) {
+  if (speed_pct < 50 || speed_pct > 200) return fail(LVX_E_ARG, "speed_pct must be in [50, 200]");
+  if (t0 < 0 || n_in < 0) return fail(LVX_E_ARG, "t0 and n_in must be >= 0");
+  return (int)(stretch_emitted_upto(speed_pct, t0 + n_in, final != 0) - stretch_emitted_upto(speed_pct, t0, false));
+}
+
+int lvx_pcm_stretch(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const uint8_t* final_host,
+                    int speed_pct, float* out, long long out_stride, int32_t* n_out_host, int32_t* d_out, int d_stride,
+                    void* stream) {
+  NEED_FINAL(c);
+  if (speed_pct < 50 || speed_pct > 200) return fail(LVX_E_ARG, "speed_pct must be in [50, 200], got " + std::to_string(speed_pct));
+  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
+  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
+  const bool launch = speed_pct != 100;  // 100: the rows of pcm_dev are the output
+  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
+    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  if (launch && d_out && ((reinterpret_cast<uintptr_t>(d_out) & 3) || d_stride < 0))
+    return fail(LVX_E_ARG, "d_out_dev must be a multiple of 4 and d_stride >= 0");
+  const int S = c->cfg.max_streams;
+  std::vector<StretchRow> rows(B);
+  {
+    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
+    // every row is checked before any slot's state changes
+    std::vector<uint8_t> seen(S, 0);
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
+      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
+      seen[s] = 1;
+      if (c->str_pct[s] && c->str_pct[s] != speed_pct)
+        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at speed_pct " + std::to_string(c->str_pct[s]));
+      if (!launch) {
+        rows[b] = StretchRow{0, 0, 0, n_in, 0, -1, s, b};
+        continue;
+      }
+      const long long t0 = c->str_t0[s], j0 = c->str_hops[s];
+      const long long m1 = stretch_emitted_upto(speed_pct, t0 + n_in, final_host[b] != 0);
+      const long long n_out = std::max(0ll, m1 - j0 * STR_H), hops = (n_out + STR_H - 1) / STR_H;
+      if (n_out > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
+      if (n_out * 4 > out_stride)
+        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
+                                   std::to_string(n_out * 4) + " bytes)");
+      if (d_out && hops > d_stride)
+        return fail(LVX_E_ARG, "d_stride " + std::to_string(d_stride) + " is smaller than a row's hops (" + std::to_string(hops) + ")");
+      const int cur = (c->str_par[s] * S + s) * STR_HIST, other = ((1 - c->str_par[s]) * S + s) * STR_HIST;
+      const bool keep = n_in > 0 && !final_host[b];  // a history for the segment's next call
+      rows[b] = StretchRow{t0, j0, (int)hops, (int)n_out, cur, keep ? other : -1, s, b};
+    }
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      n_out_host[b] = rows[b].n_out;
+      if (final_host[b]) {
+        c->str_t0[s] = 0;
+        c->str_hops[s] = 0;
+        c->str_pct[s] = 0;
+      } else if (launch) {
+        c->str_t0[s] += n_in;
+        c->str_hops[s] += rows[b].n_hops;
+        c->str_pct[s] = speed_pct;
+        if (rows[b].hist_out >= 0) c->str_par[s] ^= 1;
+      }
+    }
+  }
+  if (!launch) return LVX_OK;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
+    const int nr = std::min(PCM_ROWS, B - b0);
+    StretchRows pk{};
+    bool any = false;
+    for (int k = 0; k < nr; ++k) {
+      pk.r[k] = rows[b0 + k];
+      any = any || pk.r[k].n_hops > 0 || pk.r[k].hist_out >= 0;
+    }
+    if (!any) continue;  // (a flush with nothing left)
+    pcm_launch_stretch(pk, nr, speed_pct, pcm, n_in, c->str_win, c->str_hist, c->str_d, out, out_stride, d_out, d_stride,
+                       (hipStream_t)stream);
   }
   HIP_TRY(hipGetLastError());
   return LVX_OK;

@@ -243,4 +243,28 @@ struct PcmRows {
 void pcm_launch_convert(int sample_rate, int enc, const PcmRows& rows, int n_rows, int max_out, const float* pcm,
                         int n_in, const float* taps, float* hist, void* out, long long out_stride, hipStream_t s);
 
+// ---------------- PCM time stretch (pcm_kernels.hip; llmvox.h "PCM time stretch") ----------------
+constexpr int STR_H = 240;      // output hop
+constexpr int STR_D = 240;      // search radius
+constexpr int STR_C = 480;      // correlation length
+constexpr int STR_HIST = 1280;  // inputs of history a slot keeps between calls (a hop reaches back <= 1199)
+struct StretchRow {
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long j0;  // hops of the segment emitted before this call = index of the call's first hop
+  int n_hops;    // hops of this call
+  int n_out;     // samples of this call: n_hops * STR_H, less where a final call cuts the last hop
+  int hist_in;   // float offset of the slot's history [STR_HIST] (inputs t0 - 1280 .. t0 - 1) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int slot;      // the slot's word of the d_{j-1} state
+  int row;       // row of pcm / out / d_out
+};
+struct StretchRows {
+  StretchRow r[PCM_ROWS];
+};
+// one launch for n_rows <= PCM_ROWS rows, one block per row; win: wr [STR_H] then wf [STR_H]; dstate: the
+// slots' d_{j-1} (int per slot); d_out (optional): row b's chosen d_j at d_out + b * d_stride
+void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, const float* pcm, int n_in,
+                        const float* win, float* hist, int* dstate, float* out, long long out_stride, int* d_out,
+                        int d_stride, hipStream_t s);
+
 }  // namespace lvx

@@ -1,6 +1,8 @@
 // PCM output stage (include/llmvox.h, "PCM output stage"): rational polyphase resampling of the codec's
 // 24 kHz fp32 rows to 16 / 8 / 48 kHz and the s16le quantisation, one kernel family templated on
 // (L, M, N, encoding). Launched only for a stream that asked for another format than f32le at 24 kHz.
+// And the speaking-rate control in front of it ("PCM time stretch"): WSOLA on the 24 kHz rows, one block
+// per row, launched only for a stream that asked for another speed.
 #include <algorithm>
 
 #include "lvx_internal.h"
@@ -122,7 +124,163 @@ void launch_enc(const PcmRows& rows, int n_rows, int max_out, int enc, const flo
                                                                             (unsigned char*)out, out_stride);
 }
 
+// ---- PCM time stretch (llmvox.h, "PCM time stretch"): WSOLA on the 24 kHz rows ----
+constexpr int STR_THREADS = 256;             // two adjacent candidates d per thread: 2 D + 1 = 481 of them
+constexpr int STR_CAND = 2 * STR_D + 1;
+constexpr int STR_SPAN = 2 * STR_D + STR_C;  // inputs the candidates of one hop cover
+static_assert(STR_CAND <= 2 * STR_THREADS && STR_H <= STR_THREADS, "two candidates per thread");
+typedef float str_f2 __attribute__((ext_vector_type(2)));
+
+// fp32 -> unsigned with the same order (no NaN comes here; -0 has been made +0)
+__device__ __forceinline__ unsigned str_ordered(float s) {
+  const unsigned u = __float_as_uint(s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// One block per row walks the row's hops in order (hop j starts from p_{j-1}). Per hop: the candidate span
+// x[a_j - D .. a_j + D + C) and the template x[e_j .. e_j + C) go to LDS; thread i runs the two
+// sequential sums of the candidates d = 2 i - D and d + 1 side by side, as the two halves of packed fp32
+// multiplies and adds (each half is the candidate's own rounded product and rounded sum, in the rule's
+// order; the template word is a broadcast); a block arg-max on (score, -rank), rank = 2 |d| + (d > 0);
+// then the H outputs.
+__global__ __launch_bounds__(STR_THREADS) void pcm_stretch_kernel(StretchRows rows, int pct,
+                                                                  const float* __restrict__ pcm, int n_in,
+                                                                  const float* __restrict__ win, float* hist,
+                                                                  int* dstate, unsigned char* __restrict__ out,
+                                                                  long long out_stride, int* __restrict__ d_out,
+                                                                  int d_stride) {
+  const StretchRow r = rows.r[blockIdx.x];
+  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
+  const int tid = threadIdx.x;
+  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
+  // segment input g from the call's row or the slot's history; zero outside the segment. Without a
+  // branch (an input outside loads a word of the window table and drops it), so that the loads of a hop's
+  // staging are all in flight together: a hop waits for one memory latency, not for six in turn.
+  auto input = [&](long long g) -> float {
+    const long long back = r.t0 - g;
+    const bool in_row = g >= r.t0 && g < t1, in_hist = g >= 0 && back >= 1 && back <= STR_HIST;
+    const float* src = in_row ? x + (g - r.t0) : in_hist ? hist + (r.hist_in + STR_HIST - back) : win;
+    const float v = *src;
+    return (in_row || in_hist) ? v : 0.f;
+  };
+  if (r.hist_out >= 0)
+    for (int i = tid; i < STR_HIST; i += STR_THREADS) hist[r.hist_out + i] = input(t1 - STR_HIST + i);
+  if (r.n_hops <= 0) return;
+
+  // both padded to whole rounds of the block's staging (the pad holds the inputs that follow; the 482nd,
+  // unused, candidate's last step reads s_c[STR_SPAN])
+  constexpr int SC = (STR_SPAN + STR_THREADS) / STR_THREADS * STR_THREADS, ST = (STR_C + STR_THREADS - 1) / STR_THREADS * STR_THREADS;
+  __shared__ float s_c[SC];
+  __shared__ float s_t[ST];
+  __shared__ float s_wr[STR_H], s_wf[STR_H];
+  __shared__ unsigned s_hi[STR_THREADS / 64], s_lo[STR_THREADS / 64];
+  if (tid < STR_H) {
+    s_wr[tid] = win[tid];
+    s_wf[tid] = win[STR_H + tid];
+  }
+  // p_{j0 - 1} = a_{j0 - 1} + d_{j0 - 1}: the slot keeps the d (a new segment starts from p_{-1} = -H)
+  long long p_prev = r.j0 == 0 ? -STR_H : ((r.j0 - 1) * STR_H * pct) / 100 + dstate[r.slot];
+  float* __restrict__ orow = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride);
+  int d = 0;
+  for (int h = 0; h < r.n_hops; ++h) {
+    const long long j = r.j0 + h;
+    const long long a = (j * STR_H * pct) / 100, e = p_prev + STR_H;
+    float vc[SC / STR_THREADS], vt[ST / STR_THREADS];
+#pragma unroll
+    for (int u = 0; u < SC / STR_THREADS; ++u) vc[u] = input(a - STR_D + tid + u * STR_THREADS);
+#pragma unroll
+    for (int u = 0; u < ST / STR_THREADS; ++u) vt[u] = input(e + tid + u * STR_THREADS);
+#pragma unroll
+    for (int u = 0; u < SC / STR_THREADS; ++u) s_c[tid + u * STR_THREADS] = vc[u];
+#pragma unroll
+    for (int u = 0; u < ST / STR_THREADS; ++u) s_t[tid + u * STR_THREADS] = vt[u];
+    __syncthreads();
+    d = 0;
+    if (j >= 1) {
+      unsigned hi = 0, lo = 0;  // (below every candidate's key)
+      if (2 * tid < STR_CAND) {
+        str_f2 corr = {0.f, 0.f}, en = {0.f, 0.f};
+        const float* c = s_c + 2 * tid;
+        // k ascending, each product and each sum rounded to fp32 (no fused multiply-add): the rule's order
+#pragma unroll 8
+        for (int k = 0; k < STR_C; ++k) {
+#pragma clang fp contract(off)
+          const str_f2 xc = {c[k], c[k + 1]};
+          const float t = s_t[k];
+          const str_f2 tt = {t, t};
+          const str_f2 pc = xc * tt;
+          corr = corr + pc;
+          const str_f2 pe = xc * xc;
+          en = en + pe;
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const int dd = 2 * tid + q - STR_D;
+          if (dd > STR_D) break;  // (the last thread has one candidate)
+          float score;
+          {
+#pragma clang fp contract(off)
+            const float num = corr[q] * fabsf(corr[q]);
+            const float den = en[q] + 1e-9f;
+            score = __fdiv_rn(num, den);
+          }
+          if (score != score) score = -INFINITY;
+          if (score == 0.f) score = 0.f;  // (-0 and +0 are equal scores)
+          const unsigned qhi = str_ordered(score), qlo = 0xFFFFFFFFu - (unsigned)(2 * abs(dd) + (dd > 0 ? 1 : 0));
+          if (qhi > hi || (qhi == hi && qlo > lo)) {
+            hi = qhi;
+            lo = qlo;
+          }
+        }
+      }
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned ohi = __shfl_xor(hi, m), olo = __shfl_xor(lo, m);
+        if (ohi > hi || (ohi == hi && olo > lo)) {
+          hi = ohi;
+          lo = olo;
+        }
+      }
+      if ((tid & 63) == 0) {
+        s_hi[tid >> 6] = hi;
+        s_lo[tid >> 6] = lo;
+      }
+      __syncthreads();
+      hi = s_hi[0];
+      lo = s_lo[0];
+#pragma unroll
+      for (int w = 1; w < STR_THREADS / 64; ++w) {
+        const unsigned ohi = s_hi[w], olo = s_lo[w];
+        if (ohi > hi || (ohi == hi && olo > lo)) {
+          hi = ohi;
+          lo = olo;
+        }
+      }
+      const int rank = (int)(0xFFFFFFFFu - lo);
+      d = (rank & 1) ? (rank >> 1) : -(rank >> 1);
+    }
+    const int m = h * STR_H + tid;
+    if (tid < STR_H && m < r.n_out) {
+#pragma clang fp contract(off)
+      const float fall = s_t[tid] * s_wf[tid];
+      const float rise = s_c[d + STR_D + tid] * s_wr[tid];
+      orow[m] = fall + rise;
+    }
+    if (d_out && tid == 0) d_out[(size_t)r.row * (size_t)d_stride + h] = d;
+    p_prev = a + d;
+    __syncthreads();  // (the next hop overwrites the span, the template and the wave maxima)
+  }
+  if (tid == 0) dstate[r.slot] = d;
+}
+
 }  // namespace
+
+void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, const float* pcm, int n_in,
+                        const float* win, float* hist, int* dstate, float* out, long long out_stride, int* d_out,
+                        int d_stride, hipStream_t s) {
+  pcm_stretch_kernel<<<dim3((unsigned)n_rows), STR_THREADS, 0, s>>>(rows, speed_pct, pcm, n_in, win, hist, dstate,
+                                                                    (unsigned char*)out, out_stride, d_out, d_stride);
+}
 
 void pcm_launch_convert(int sample_rate, int enc, const PcmRows& rows, int n_rows, int max_out, const float* pcm,
                         int n_in, const float* taps, float* hist, void* out, long long out_stride, hipStream_t s) {

@@ -203,12 +203,89 @@ class Engine:
         """Forget the slot's output-stage history and position: its next ``pcm_convert`` starts a segment."""
         _lib.check(self.lib.lvx_pcm_reset(self.h, int(slot), self.stream_handle()))
 
+    def pcm_stretch_window(self):
+        """(wr, wf) float32 [240]: the time stretch's window tables as the library builds them
+        (lvx_pcm_stretch_window)."""
+        wr, wf = np.zeros(240, dtype=np.float32), np.zeros(240, dtype=np.float32)
+        _lib.check(self.lib.lvx_pcm_stretch_window(wr.ctypes.data_as(ctypes.c_void_p),
+                                                   wf.ctypes.data_as(ctypes.c_void_p), 240))
+        return wr, wf
+
+    def _pcm_rows(self, pcm: Optional[torch.Tensor], B: int):
+        n_in = 0 if pcm is None else int(pcm.shape[1])
+        if pcm is not None:
+            if pcm.shape[0] != B or pcm.dtype != torch.float32 or pcm.device != self.device:
+                raise ValueError(f"pcm must be a float32 [{B}, n_in] tensor on {self.device}")
+            pcm = pcm.contiguous()
+        return pcm, n_in
+
+    def pcm_stretch(self, pcm: Optional[torch.Tensor], slots, finals, speed_pct: int, want_d: bool = False):
+        """The time stretch alone (lvx_pcm_stretch): rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None
+        or n_in 0: flush only) continue the stretch segments of ``slots`` at ``speed_pct``; a true
+        ``finals[b]`` emits the rest of row b's segment and ends it. Returns (out, counts, d): a device
+        float32 tensor [B, width] whose row b holds counts[b] samples, and (``want_d``) a device int32 tensor
+        whose row b holds the chosen d_j of the hops the call emitted (else None). speed_pct 100: the rows
+        themselves. Asynchronous on the current stream; a slot's calls must be issued in order on one stream."""
+        slots = [int(s) for s in slots]
+        B = len(slots)
+        pcm, n_in = self._pcm_rows(pcm, B)
+        speed_pct = int(speed_pct)
+        out = d = None
+        width = dw = 0
+        if speed_pct == 100:
+            out = pcm if pcm is not None else torch.empty(B, 0, device=self.device, dtype=torch.float32)
+        elif 50 <= speed_pct <= 200:
+            # a call emits at most the hops that waited for their right-hand inputs (<= 960 inputs' worth)
+            # and its own inputs' worth, cut to whole hops; rows start on 16-byte boundaries
+            width = ((n_in * 100 + 96000) // speed_pct + 2 * 240 + 7) // 8 * 8
+            out = torch.empty(B, width, device=self.device, dtype=torch.float32)
+            if want_d:
+                dw = width // 240 + 1
+                d = torch.zeros(B, dw, device=self.device, dtype=torch.int32)
+        sl = (ctypes.c_int32 * B)(*slots)
+        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
+        cnt = (ctypes.c_int32 * B)()
+        _lib.check(self.lib.lvx_pcm_stretch(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, speed_pct, _ptr(out),
+                                            width * 4, cnt, _ptr(d), dw, self.stream_handle()))
+        return out, list(cnt), d
+
     def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
-        ``audio.AudioFormat`` (its rate and encoding). Returns (out, counts): a device tensor [B, width] of
-        int16 or float32 whose row b holds counts[b] samples. Asynchronous on the current stream; a slot's
-        calls must be issued in order on one stream (lvx_pcm_convert)."""
+        ``audio.AudioFormat`` (its speed, rate and encoding). Returns (out, counts): a device tensor
+        [B, width] of int16 or float32 whose row b holds counts[b] samples. A format with a speed has its rows
+        time-stretched first (lvx_pcm_stretch); the stretched rows, which may hold different counts, then pass
+        the resampling / quantisation grouped by count. Asynchronous on the current stream; a slot's calls
+        must be issued in order on one stream (lvx_pcm_convert)."""
+        if fmt.speed_pct == 100:
+            return self._pcm_resample(pcm, slots, finals, fmt)
+        slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
+        st, cnt, _ = self.pcm_stretch(pcm, slots, finals, fmt.speed_pct)
+        if fmt.sample_rate == 24000 and fmt.encoding == "f32le":
+            return st, cnt
+        groups: Dict[int, list] = {}
+        for b, n in enumerate(cnt):
+            if n or finals[b]:  # (nothing stretched and no end: nothing to hand on)
+                groups.setdefault(n, []).append(b)
+        parts = []
+        for n, rows in groups.items():
+            sub = None if n == 0 else st[:, :n] if len(rows) == len(slots) else st[rows, :n]
+            o, c = self._pcm_resample(sub, [slots[b] for b in rows], [finals[b] for b in rows], fmt)
+            parts.append((rows, o, c))
+        if len(parts) == 1 and len(parts[0][0]) == len(slots):
+            return parts[0][1], parts[0][2]
+        width = max([o.shape[1] for _, o, _ in parts], default=0)
+        out = torch.zeros(len(slots), width, device=self.device,
+                          dtype=torch.int16 if fmt.encoding == "s16le" else torch.float32)
+        counts = [0] * len(slots)
+        for rows, o, c in parts:
+            out[rows, :o.shape[1]] = o
+            for b, n in zip(rows, c):
+                counts[b] = n
+        return out, counts
+
+    def _pcm_resample(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
+        """pcm_convert without the speed: the rate and the encoding (lvx_pcm_convert)."""
         slots = [int(s) for s in slots]
         B = len(slots)
         n_in = 0 if pcm is None else int(pcm.shape[1])
@@ -217,7 +294,7 @@ class Engine:
                 raise ValueError(f"pcm must be a float32 [{B}, n_in] tensor on {self.device}")
             pcm = pcm.contiguous()
         s16 = fmt.encoding == "s16le"
-        if not fmt.converts:  # 24 kHz f32le: the rows are the output (nothing is launched)
+        if fmt.sample_rate == 24000 and not s16:  # 24 kHz f32le: the rows are the output (nothing is launched)
             if pcm is None:
                 pcm = torch.empty(B, 0, device=self.device, dtype=torch.float32)
             out, width = pcm, n_in

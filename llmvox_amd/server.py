@@ -39,6 +39,7 @@ Differences, on purpose:
     out of service (its requests end with the error; new requests go to the other devices).
 """
 
+import math
 import os
 import threading
 from queue import Queue
@@ -248,8 +249,8 @@ class TTSService:
     def submit(self, text: str, sampling=None, audio=None) -> _Session:
         """``sampling``: a ``sampling.Sampling`` makes the request's streams draw their tokens (seeded
         temperature / top-k; the replicas and the sentences each from a seed of their own), None: greedy.
-        ``audio``: an ``audio.AudioFormat``: the sample rate and encoding of the request's chunks (converted
-        on the device, every sentence resampled as a signal of its own) and whether ``chunks`` starts with a
+        ``audio``: an ``audio.AudioFormat``: the speed, sample rate and encoding of the request's chunks (converted
+        on the device, every sentence stretched and resampled as a signal of its own) and whether ``chunks`` starts with a
         WAV header; None: headerless f32le at 24 kHz, the reference's stream.
         Open the request's two replica streams on the first device (round robin from k mod G)
         that is in service and has two free KV slots. Requests run for different lengths, so the
@@ -352,8 +353,19 @@ class TTSService:
                 w.sched.close()
 
 
+def speed_pct_of(speed) -> int:
+    """A speaking rate (a float in 0.5 .. 2.0) as the integer percentage the PCM time stretch takes
+    (``audio.AudioFormat.speed_pct``); ValueError for anything else."""
+    if isinstance(speed, bool) or not isinstance(speed, (int, float)) or not math.isfinite(speed):
+        raise ValueError(f"speed must be a number in 0.5 .. 2.0, got {speed!r}")
+    pct = int(round(speed * 100))
+    if not 50 <= pct <= 200:
+        raise ValueError(f"speed must be in 0.5 .. 2.0, got {speed!r}")
+    return pct
+
+
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
-               encoding: str = "f32le", container: str = "raw"):
+               encoding: str = "f32le", container: str = "raw", speed: float = 1.0):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -364,7 +376,9 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     "s16le") and ``container`` ("raw", "wav": a 44-byte header of a stream of unknown length first); a
     field it leaves out takes the default given here; invalid values: 422. The response says what it
     carries in ``X-Audio-Sample-Rate`` / ``X-Audio-Encoding`` and its media type (audio/wav for the wav
-    container). The reference's /voicechat,
+    container). ``speed`` (a float in 0.5 .. 2.0; 1.0: as spoken) is the speaking rate: the PCM is
+    time-stretched on the device, pitch preserved, to round(speed * 100) percent (``audio.AudioFormat.speed_pct``);
+    out of range: 422; the response carries it in ``X-Audio-Speed``. The reference's /voicechat,
     /multimodalchat and /vlmschat differ from /tts only in the producer (ASR / multimodal LLM,
     out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
@@ -374,7 +388,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     from .audio import AudioFormat
     from .sampling import Sampling
     Sampling(temperature, top_k)  # (the defaults are validated at start-up)
-    default_audio = AudioFormat(sample_rate, encoding, container)
+    default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed))
 
     class TTSRequest(BaseModel):
         text: str
@@ -384,13 +398,15 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         sample_rate: Optional[int] = None
         encoding: Optional[str] = None
         container: Optional[str] = None
+        speed: Optional[float] = None
 
     def audio_of(request):
         """The request's AudioFormat (the defaults for the fields it does not name)."""
         try:
             return AudioFormat(default_audio.sample_rate if request.sample_rate is None else request.sample_rate,
                                default_audio.encoding if request.encoding is None else request.encoding,
-                               default_audio.container if request.container is None else request.container)
+                               default_audio.container if request.container is None else request.container,
+                               default_audio.speed_pct if request.speed is None else speed_pct_of(request.speed))
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -432,7 +448,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         except RuntimeError as e:
             raise HTTPException(status_code=503, detail=str(e))
         return StreamingResponse(service.chunks(session), media_type=fmt.media_type,
-                                 headers={"X-Audio-Sample-Rate": str(fmt.sample_rate), "X-Audio-Encoding": fmt.encoding})
+                                 headers={"X-Audio-Sample-Rate": str(fmt.sample_rate), "X-Audio-Encoding": fmt.encoding,
+                                          "X-Audio-Speed": f"{fmt.speed_pct / 100:.2f}"})
 
     @app.get("/health")
     def health():
@@ -469,6 +486,8 @@ def main(argv=None):
                     help="output sample rate of requests that name none")
     ap.add_argument("--encoding", default="f32le", choices=["f32le", "s16le"], help="their sample encoding")
     ap.add_argument("--container", default="raw", choices=["raw", "wav"], help="their container (wav: a header first)")
+    ap.add_argument("--speed", type=float, default=1.0,
+                    help="speaking rate of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
     a = ap.parse_args(argv)
     from .engine import build_engine
     from . import weights as W
@@ -494,7 +513,7 @@ def main(argv=None):
     svc = TTSService(engines, stream_model=sm)
     import uvicorn
     uvicorn.run(create_app(svc, temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate,
-                           encoding=a.encoding, container=a.container), host=a.host, port=a.port)
+                           encoding=a.encoding, container=a.container, speed=a.speed), host=a.host, port=a.port)
 
 
 if __name__ == "__main__":
