@@ -188,6 +188,40 @@ int lvx_probe_kernel(lvx_ctx* ctx, int which, int B, const int32_t* slots_dev, i
 int lvx_select_probe(lvx_ctx* ctx, int path, int B, const int32_t* slots_dev, const float* logits_dev,
                      const int32_t* text_plan_dev, int plan_stride, int32_t* rowstep_dev, int32_t* tok_plan_dev,
                      float* margin_plan_dev, void* stream);
+/* Test hooks (tests/test_gpu_attn_probe.py, tests/test_gpu_kv_append.py): direct access to the KV cache
+ * rows of one (slot, layer) and to the decode attention. They add no kernel to a decode step and are
+ * never captured into a graph.
+ * lvx_kv_write: k_dev / v_dev float32 [n][768] (head-major, as c_attn produces k and v; either may be
+ *   null) are stored as positions pos0 .. pos0 + n - 1 with the conversion of the step's own appends
+ *   (fp32 copy, bf16 round-to-nearest-even, or saturated e4m3fn). Rows up to the end of the slot's last
+ *   allocated 64-position chunk may be written (LVX_E_CAPACITY beyond).
+ * lvx_kv_write_raw: the same with caller-given bit patterns: the low 32 / 16 / 8 bits of each uint32
+ *   become the stored element (NaN encodings, for instance).
+ * lvx_kv_read: the inverse: the stored elements widened exactly to float32. */
+int lvx_kv_write(lvx_ctx* ctx, int slot, int layer, int pos0, int n, const float* k_dev, const float* v_dev,
+                 void* stream);
+int lvx_kv_write_raw(lvx_ctx* ctx, int slot, int layer, int pos0, int n, const uint32_t* k_dev, const uint32_t* v_dev,
+                     void* stream);
+int lvx_kv_read(lvx_ctx* ctx, int slot, int layer, int pos0, int n, float* k_dev, float* v_dev, void* stream);
+/* Test hook: the production decode attention of the step plan at this B under the context's options
+ * (its split count, output form and block shape; the non-K-split kernel, no layer-0 record copy), plus
+ * the plan's merge kernel where it has one, at `layer`, over q_dev float32 [B][768] and the KV rows of
+ * slots_dev (-1: idle row). Row b attends over keys [0, P_b], P_b the slot's current position
+ * (lvx_stream_set): what a step at that position sees after its append.
+ * form_out is int[4]: {form, nsplit, attn_direct, attn8} of the plan that ran.
+ *   form 0: the plan leaves normalised rows (the attention's own bf16 / fp32 rows or the merge kernel's);
+ *           they are widened exactly into out_dev float32 [B][768] (an idle row: whatever the kernels
+ *           left in the scratch row).
+ *   form 1: the plan merges the splits inside c_proj's prologue (the GEMV family, fp32 FIN_MERGE): the
+ *           partials are copied out as the attention left them, part_o_dev float32 [B][8][16][96] and
+ *           part_ml_dev float32 [B][8][16][2] (running max, sum); row b has min(nsplit, ceil((P_b + 1)
+ *           / 64)) valid splits, the others are not written. The prologue merges themselves are not
+ *           run by this hook: they stay covered at the logit level only.
+ * LVX_E_STATE where the plan's attention takes no q rows (the fp32 K-split c_attn; option "exp" 1024
+ * selects the one-launch form). form_out is written before the call returns; the device buffers are
+ * written in stream order. */
+int lvx_attn_probe(lvx_ctx* ctx, int B, const int32_t* slots_dev, int layer, const float* q_dev, float* out_dev,
+                   float* part_o_dev, float* part_ml_dev, int* form_out, void* stream);
 /* Host-side view of a slot's position (synchronises the stream). */
 int lvx_stream_position(lvx_ctx* ctx, int slot, int* pos_out, void* stream);
 /* Cross-check switches between two correct implementations of the same step, per context (round 4:

@@ -91,6 +91,10 @@ _SIGS = {
     "lvx_stream_set": (_I, [_P, _I, _I, _I, _P]),
     "lvx_stream_sampling": (_I, [_P, _I, ctypes.c_float, _I, ctypes.c_uint64, _P]),
     "lvx_select_probe": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "lvx_kv_write": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "lvx_kv_write_raw": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "lvx_kv_read": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "lvx_attn_probe": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, ctypes.POINTER(_I), _P]),
     "lvx_stream_position": (_I, [_P, _I, ctypes.POINTER(_I), _P]),
     "lvx_set_graphs": (_I, [_P, _I]),
     "lvx_set_capture_stream": (_I, [_P, _P]),

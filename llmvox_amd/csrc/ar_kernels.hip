@@ -3409,6 +3409,104 @@ int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipS
   return 0;
 }
 
+// Test hooks (lvx_kv_write / lvx_kv_write_raw / lvx_kv_read): rows pos0 .. pos0 + n - 1 of one (slot, layer)
+// of the KV cache, addressed through kv_at. src / dst are [n][768] head-major, as c_attn produces k and v.
+// Write: the conversion of store_kv, or (raw) the low 32 / 16 / 8 bits of each uint32 as the stored
+// element. Read: the stored element widened exactly to fp32. Plain per-element vector stores.
+__global__ __launch_bounds__(256) void kv_write_kernel(ArState st, int kvdtype, int slot, int layer, int pos0, int n,
+                                                       const float* __restrict__ k, const float* __restrict__ v, int raw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * D) return;
+  const int e = i % D, head = e / HD, d = e % HD;
+  const size_t idx = kv_at(layer, st.kv_chunks, st.max_streams, slot, head, pos0 + i / D) + d;
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    const float* src = which ? v : k;
+    void* base = which ? st.vc : st.kc;
+    if (!src) continue;
+    const float f = src[i];
+    const uint32_t u = __float_as_uint(f);
+    if (kvdtype == LVX_DTYPE_BF16) reinterpret_cast<bf16_t*>(base)[idx] = raw ? (bf16_t)u : f32_to_bf16(f);
+    else if (kvdtype == LVX_DTYPE_FP8) reinterpret_cast<fp8_t*>(base)[idx] = raw ? (fp8_t)u : f32_to_fp8(f);
+    else reinterpret_cast<float*>(base)[idx] = f;
+  }
+}
+
+__global__ __launch_bounds__(256) void kv_read_kernel(ArState st, int kvdtype, int slot, int layer, int pos0, int n,
+                                                      float* __restrict__ k, float* __restrict__ v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * D) return;
+  const int e = i % D, head = e / HD, d = e % HD;
+  const size_t idx = kv_at(layer, st.kv_chunks, st.max_streams, slot, head, pos0 + i / D) + d;
+#pragma unroll
+  for (int which = 0; which < 2; ++which) {
+    float* dst = which ? v : k;
+    const void* base = which ? st.vc : st.kc;
+    if (!dst) continue;
+    if (kvdtype == LVX_DTYPE_BF16) dst[i] = bf16_to_f32(reinterpret_cast<const bf16_t*>(base)[idx]);
+    else if (kvdtype == LVX_DTYPE_FP8) dst[i] = __builtin_amdgcn_cvt_pk_f32_fp8(reinterpret_cast<const fp8_t*>(base)[idx], false)[0];
+    else dst[i] = reinterpret_cast<const float*>(base)[idx];
+  }
+}
+
+void ar_launch_kv_write(const ArState& st, int kvdtype, int slot, int layer, int pos0, int n, const float* k,
+                        const float* v, bool raw, hipStream_t s) {
+  hipLaunchKernelGGL(kv_write_kernel, dim3((n * D + 255) / 256), dim3(256), 0, s, st, kvdtype, slot, layer, pos0, n, k, v,
+                     raw ? 1 : 0);
+}
+
+void ar_launch_kv_read(const ArState& st, int kvdtype, int slot, int layer, int pos0, int n, float* k, float* v,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(kv_read_kernel, dim3((n * D + 255) / 256), dim3(256), 0, s, st, kvdtype, slot, layer, pos0, n, k, v);
+}
+
+// Test hook (lvx_attn_probe): the normalised attention rows of B batch rows, widened exactly to fp32, from
+// where the plan's attention (or its merge kernel) left them. src 0: st.xn row-major; 1: st.xn
+// fragment-packed (xfrag); 2: split 0 of st.part_o (ATTN_F32_ROWS)
+__global__ __launch_bounds__(256) void attn_probe_rows_kernel(ArState st, int B, int src, float* __restrict__ out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * D) return;
+  const int b = i / D, e = i % D;
+  if (src == 2) out[i] = st.part_o[(size_t)(b * N_HEAD + e / HD) * NSPLIT * HD + e % HD];
+  else out[i] = bf16_to_f32(st.xn[src == 1 ? xfrag(b, e, D) : (size_t)i]);
+}
+
+// The production attention of the plan at this B under the bound options, over the q rows in st.q and the
+// slots' current positions (row b attends over keys [0, pos]: what a step at that position sees after its
+// append): the step's own launch (launch_op OP_ATTN) without the layer-0 record copy, then the plan's merge
+// kernel where it has one. The merges inside c_proj's prologue (GIN_MERGE, FIN_MERGE) are NOT run: for
+// those plans the caller gets the partials and merges them itself, so the prologue merges stay covered
+// at the logit level only. info: {form, nsplit, attn_direct, attn8}; form 0: rows in `out`, 1: partials
+// left in st.part_o / st.part_ml. Returns 1 where the plan's attention takes no st.q (qsplit).
+int ar_attn_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int layer, float* out,
+                  int info[4], hipStream_t s) {
+  ArStepPlan p = ar_plan_step(opts(), wdtype, kvdtype, B, false, false);
+  if (p.qsplit) return 1;
+  p.sel = SEL_ARGMAX;
+  p.selcopy = false;
+  GemvArgs a = make_args<float>(w, st, kvdtype, B, nullptr);
+  hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
+  if (p.bf16) launch_op<bf16_t>(OP_ATTN, a, w, layer, p, s);
+  else launch_op<float>(OP_ATTN, a, w, layer, p, s);
+  const bool mf = p.path == PATH_MFMA_LN || p.path == PATH_MFMA_ROWS;
+  int src = -1;  // as launch_op's OP_CPROJ runs the merge kernel
+  if (p.path == PATH_BT) {
+    launch_merge_bf16(st, B, p.nsplit, s);
+    src = 0;
+  } else if (mf && p.nsplit > 1) {
+    launch_merge_bf16(st, B, p.nsplit, s, p.xpk);
+    src = p.xpk ? 1 : 0;
+  } else if (p.attn_direct != ATTN_PARTIALS) {
+    src = p.attn_direct == ATTN_F32_ROWS ? 2 : p.attn_direct == ATTN_XN_PACKED ? 1 : 0;
+  }
+  if (src >= 0) hipLaunchKernelGGL(attn_probe_rows_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, st, B, src, out);
+  info[0] = src >= 0 ? 0 : 1;
+  info[1] = p.nsplit;
+  info[2] = p.attn_direct;
+  info[3] = p.attn8 ? 1 : 0;
+  return 0;
+}
+
 void ar_launch_steps_end(const ArState& st, const ArStepPlan& p, hipStream_t s) {
   if (p.end == END_SELECT_FINAL) hipLaunchKernelGGL(ar_select_final_kernel, dim3(p.B), dim3(64), 0, s, st);
   else if (p.end == END_ARGMAX) hipLaunchKernelGGL(ar_argmax_kernel, dim3(p.B), dim3(256), 0, s, st);

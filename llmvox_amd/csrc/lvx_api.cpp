@@ -1102,6 +1102,66 @@ int lvx_select_probe(lvx_ctx* c, int path, int B, const int32_t* slots, const fl
   return LVX_OK;
 }
 
+static int kv_hook_check(lvx_ctx* c, int slot, int layer, int pos0, int n) {
+  if (slot < 0 || slot >= c->cfg.max_streams) return fail(LVX_E_ARG, "slot out of range");
+  if (layer < 0 || layer >= N_LAYER) return fail(LVX_E_ARG, "layer out of range");
+  if (pos0 < 0 || n < 1 || (long long)pos0 + n > (long long)c->st.kv_chunks * KV_CHUNK)
+    return fail(LVX_E_CAPACITY, "rows outside the slot's allocated KV rows");
+  return 0;
+}
+
+static int kv_write(lvx_ctx* c, int slot, int layer, int pos0, int n, const void* k, const void* v, bool raw, void* stream) {
+  NEED_FINAL(c);
+  if (int r = kv_hook_check(c, slot, layer, pos0, n)) return r;
+  if (!k && !v) return fail(LVX_E_ARG, "null k and v");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  ar_launch_kv_write(c->st, c->cfg.kv_dtype, slot, layer, pos0, n, (const float*)k, (const float*)v, raw, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+int lvx_kv_write(lvx_ctx* c, int slot, int layer, int pos0, int n, const float* k, const float* v, void* stream) {
+  return kv_write(c, slot, layer, pos0, n, k, v, false, stream);
+}
+
+int lvx_kv_write_raw(lvx_ctx* c, int slot, int layer, int pos0, int n, const uint32_t* k, const uint32_t* v, void* stream) {
+  return kv_write(c, slot, layer, pos0, n, k, v, true, stream);
+}
+
+int lvx_kv_read(lvx_ctx* c, int slot, int layer, int pos0, int n, float* k, float* v, void* stream) {
+  NEED_FINAL(c);
+  if (int r = kv_hook_check(c, slot, layer, pos0, n)) return r;
+  if (!k && !v) return fail(LVX_E_ARG, "null k and v");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  ar_launch_kv_read(c->st, c->cfg.kv_dtype, slot, layer, pos0, n, k, v, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+int lvx_attn_probe(lvx_ctx* c, int B, const int32_t* slots, int layer, const float* q, float* out, float* part_o,
+                   float* part_ml, int* form_out, void* stream) {
+  NEED_FINAL(c);
+  if (B < 1 || B > c->cfg.max_streams) return fail(LVX_E_ARG, "B out of range");
+  if (layer < 0 || layer >= N_LAYER) return fail(LVX_E_ARG, "layer out of range");
+  if (!slots || !q || !out || !part_o || !part_ml || !form_out) return fail(LVX_E_ARG, "null argument");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  ArState st = c->st;  // no plan bound: text_plan / rowstep / tok_plan stay null
+  st.slots = const_cast<int32_t*>(slots);
+  const Opts o = c->opts_snapshot();
+  OptScope os(&o);
+  HIP_TRY(hipMemcpyAsync(st.q, q, (size_t)B * D * 4, hipMemcpyDeviceToDevice, s));
+  // launched kernel by kernel, never captured into a graph
+  if (ar_attn_probe(c->arw, st, c->cfg.weight_dtype, c->cfg.kv_dtype, B, layer, out, form_out, s))
+    return fail(LVX_E_STATE, "the plan's attention at this B takes its q from the K-split c_attn (fp32: set option exp 1024)");
+  HIP_TRY(hipGetLastError());
+  if (form_out[0] == 1) {  // merged in c_proj's prologue: the partials as the kernel left them
+    HIP_TRY(hipMemcpyAsync(part_o, st.part_o, (size_t)B * N_HEAD * NSPLIT * HD * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(part_ml, st.part_ml, (size_t)B * N_HEAD * NSPLIT * 2 * 4, hipMemcpyDeviceToDevice, s));
+  }
+  return LVX_OK;
+}
+
 static int codec_check(lvx_ctx* c, int B, int L, int bw) {
   if (B < 1 || L < 1) return fail(LVX_E_ARG, "B and L must be >= 1");
   if ((long long)B * L > c->cfg.max_codec_frames)

@@ -150,6 +150,13 @@ int ar_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int
 void ar_launch_rowinfo_init(const ArState& st, int B, hipStream_t s);
 void ar_launch_steps_end(const ArState& st, const ArStepPlan& p, hipStream_t s);  // deferred select: commit the last step
 int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipStream_t s);  // test hook
+// test hooks (lvx_kv_write / lvx_kv_read / lvx_attn_probe; none is part of a step)
+void ar_launch_kv_write(const ArState& st, int kvdtype, int slot, int layer, int pos0, int n, const float* k,
+                        const float* v, bool raw, hipStream_t s);
+void ar_launch_kv_read(const ArState& st, int kvdtype, int slot, int layer, int pos0, int n, float* k, float* v,
+                       hipStream_t s);
+int ar_attn_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int layer, float* out,
+                  int info[4], hipStream_t s);
 // ArWeights::q0_text / q0_code / q0_pos from the bf16 c_attn weight of layer 0 (lvx_finalize)
 void ar_launch_q0_tables(const ArWeights& w, int max_pos, float* text, float* code, float* pos, hipStream_t s);
 void launch_set_slot(int32_t* pos, int32_t* prev, int slot, int p, int tok, hipStream_t s);

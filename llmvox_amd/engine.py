@@ -125,6 +125,53 @@ class Engine:
         _lib.check(self.lib.lvx_select_probe(self.h, path, B, _ptr(slots), _ptr(logits), _ptr(text_plan), stride,
                                              _ptr(rowstep), _ptr(tok_plan), _ptr(margin_plan), self.stream_handle()))
 
+    def kv_write(self, slot: int, layer: int, pos0: int, k: Optional[torch.Tensor], v: Optional[torch.Tensor],
+                 raw: bool = False):
+        """Test hook: store rows ``pos0 ..`` of one (slot, layer) of the KV cache from device tensors [n, 768]
+        (head-major). float32 values are converted as a step's append converts them; ``raw``: int32 tensors
+        whose low 32 / 16 / 8 bits are the stored elements (lvx_kv_write / lvx_kv_write_raw)."""
+        want = torch.int32 if raw else torch.float32
+        n = None
+        for t in (k, v):
+            if t is not None:
+                if t.dtype != want or t.device != self.device or t.dim() != 2 or t.shape[1] != 768 or not t.is_contiguous():
+                    raise ValueError(f"k / v must be contiguous {want} [n, 768] tensors on {self.device}")
+                if n is not None and t.shape[0] != n:
+                    raise ValueError("k and v must hold the same number of rows")
+                n = int(t.shape[0])
+        fn = self.lib.lvx_kv_write_raw if raw else self.lib.lvx_kv_write
+        _lib.check(fn(self.h, int(slot), int(layer), int(pos0), n or 0, _ptr(k), _ptr(v), self.stream_handle()))
+
+    def kv_read(self, slot: int, layer: int, pos0: int, n: int):
+        """Test hook: rows ``pos0 .. pos0 + n - 1`` of one (slot, layer) of the KV cache, widened exactly to
+        float32: (k, v) device tensors [n, 768] (lvx_kv_read)."""
+        k = torch.empty(n, 768, device=self.device, dtype=torch.float32)
+        v = torch.empty(n, 768, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.lvx_kv_read(self.h, int(slot), int(layer), int(pos0), int(n), _ptr(k), _ptr(v),
+                                        self.stream_handle()))
+        return k, v
+
+    def attn_probe(self, slots: torch.Tensor, layer: int, q: torch.Tensor, out: Optional[torch.Tensor] = None):
+        """Test hook: the plan's production decode attention (and its merge kernel, if it has one) at
+        B = len(slots) over ``q`` float32 [B, 768] and the slots' KV rows up to their current positions
+        (lvx_attn_probe). Returns (form, out, part_o, part_ml, (nsplit, attn_direct, attn8)): form 0: the
+        normalised rows in ``out`` [B, 768] (``out`` given: written in place, so an untouched row keeps
+        the caller's values only where no kernel wrote the scratch row); form 1: the split partials
+        part_o [B, 8, 16, 96] and part_ml [B, 8, 16, 2] for the caller to merge. Synchronises the stream."""
+        B = int(slots.numel())
+        q = q.to(self.device, torch.float32).contiguous()
+        if q.shape != (B, 768):
+            raise ValueError(f"q must be [{B}, 768]")
+        if out is None:
+            out = torch.zeros(B, 768, device=self.device, dtype=torch.float32)
+        po = torch.zeros(B, 8, 16, 96, device=self.device, dtype=torch.float32)
+        pml = torch.zeros(B, 8, 16, 2, device=self.device, dtype=torch.float32)
+        info = (ctypes.c_int * 4)()
+        _lib.check(self.lib.lvx_attn_probe(self.h, B, _ptr(slots), int(layer), _ptr(q), _ptr(out), _ptr(po), _ptr(pml),
+                                           info, self.stream_handle()))
+        torch.cuda.current_stream(self.device).synchronize()
+        return info[0], out, po, pml, (info[1], info[2], info[3])
+
     def last_logits(self, B: int) -> torch.Tensor:
         out = torch.empty(B, 4096, device=self.device, dtype=torch.float32)
         _lib.check(self.lib.lvx_ar_logits(self.h, B, _ptr(out), self.stream_handle()))
