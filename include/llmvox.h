@@ -262,7 +262,11 @@ int lvx_stream_position(lvx_ctx* ctx, int slot, int* pos_out, void* stream);
  *                     the step's first launch reads three table rows instead of weight slices; the
  *                     operand is not rounded to bf16, so the sums differ from the GEMM's in the last
  *                     bits: tests/test_gpu_batched.py, test_gpu_select.py); 0: the c_attn GEMM / GEMV
- *                     (B > 8 after the embedding + select kernel; B <= 8 with the granule select). */
+ *                     (B > 8 after the embedding + select kernel; B <= 8 with the granule select);
+ *   "l0a"          1: "l0q" steps whose attention is one split per (row, head) in 4-wave blocks (bf16 KV
+ *                     9 <= B <= 32, fp8 KV 17 <= B <= 32): the select and layer 0's q / k / v from the
+ *                     tables run inside attention layer 0, one launch less per step; 0: the select +
+ *                     table launch, then the attention (bit-identical: tests/test_gpu_l0_fused.py). */
 int lvx_set_option(lvx_ctx* ctx, const char* name, int value);
 /* The stream the decode graphs are captured on (then replayed on the caller's stream). NULL (default):
  * the caller's stream. Name another one when something may query, from another thread, an event

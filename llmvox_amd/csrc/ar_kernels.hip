@@ -1159,28 +1159,109 @@ __device__ __forceinline__ float slot_fold_wave(float m, float& l, float (&o)[24
 
 // (round 4, measured slower: the per-key-slot form for fp32 KV too, B = 32 t = 384-639 214.1 vs
 // 210.7 us/step; the fp32 parity mode keeps the wave-uniform form)
-template <typename TKV, int DEPTH, int NW, bool QKV = false>
-__global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int layer, int ns_max, int direct,
-                                                         int selcopy) {
+// L0 (bf16 weights, SEL_Q0_ROWS with one split per (row, head) in 4-wave blocks: ArStepPlan::l0_fused): layer 0's
+// attention that also runs ar_q0_rows_kernel's work for its own (row, head), so the step has no launch of
+// that kernel. The block issues the old control record, the row's logits and its head's 288 columns of
+// G / Tt[t] / Tp[p] at entry, the first KV tiles of the history (keys below the new one: they do not
+// depend on the select) as soon as the record gives (slot, position), then runs the select (the same
+// four-wave reduce, softmax_ties and clamp), loads Tc[c], wave 0 builds the embedding row's statistics
+// (q0_row_stats) and threads 0-287 form q / k / v with ar_q0_rows_kernel's expression. q goes through LDS,
+// k / v are rounded as store_kv rounds them, appended to the cache and kept in LDS: after the history's
+// tile loop the lane quad that owns key t - 1 takes them from there (the last key its slot sees, as in the
+// two-launch form, so the slot states have the same bits; the block's own store is not read back). The
+// head-0 block of a row commits the select (ar_q0_rows_kernel's cx == 0 stores, records into the shadow
+// arrays since the row's other blocks read the old ones in this launch); layer 1's ar_rows_kernel copies
+// the records back (RMODE_LN_Y_COPY). Ordering inside the block is by LDS barriers alone.
+__device__ __forceinline__ float4 q0_row_stats(const GemvArgs& a, int4 rn, int b, int lane, bool store_x);
+// plan_tok(st, b, jn + 1) from the plan element loaded at min(jn + 1, plan_stride - 1) (384 when no plan is bound)
+__device__ __forceinline__ int l0_next_tok(const ArState& st, int jn, int loaded) {
+  if (!st.text_plan) return 384;
+  return (jn + 1 < st.plan_stride) ? min(max(loaded, 0), TEXT_VOCAB - 1) : -1;
+}
+// LDS hand-off without draining the vector loads in flight (__syncthreads would wait for the KV tiles)
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+template <typename TKV, int DEPTH, int NW, bool QKV, bool L0>
+__device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns_max, int direct, int selcopy,
+                                             const GemvArgs* a0) {
   // NW waves: a tile is NW x 16 keys (4 lanes per key); NW = 8 doubles the bytes in flight per
   // block for long splits (batched steps)
   constexpr int TK = NW * 16;
   constexpr bool SLOT = sizeof(TKV) < 4;  // per-key-slot online softmax (bf16 / fp8 KV)
   static_assert(!QKV || (NW == 4 && sizeof(TKV) == 4), "the K-split c_attn: the fp32 parity mode's 4-wave blocks");
-  constexpr int QH = QKV ? (3 * HD + NW * 64 - 1) / (NW * 64) : 1;  // q / k / v elements per thread (2 at 4 waves, 1 at 8)
+  static_assert(!L0 || (NW == 4 && SLOT && !QKV), "the fused layer-0 form: bf16 / fp8 KV in 4-wave blocks");
+  constexpr bool NEWKV = QKV || L0;  // the block computes the new key's q / k / v itself
+  constexpr int QH = NEWKV ? (3 * HD + NW * 64 - 1) / (NW * 64) : 1;  // q / k / v elements per thread (2 at 4 waves, 1 at 8)
   __shared__ float wm_s[NW], wl_s[NW];
   __shared__ float wo_s[NW][4][HD];  // [wave][16-lane row][part * 24 + i]
-  __shared__ float qs_s[QKV ? HD : 1];
-  __shared__ __attribute__((aligned(16))) TKV kvh_s[QKV ? 2 : 1][QKV ? HD : 1];  // QKV: the new key's K, V
+  __shared__ float qs_s[NEWKV ? HD : 1];
+  __shared__ __attribute__((aligned(16))) TKV kvh_s[NEWKV ? 2 : 1][NEWKV ? HD : 1];  // the new key's K, V
+  __shared__ float sv_s[L0 ? 4 : 1], sv2_s[L0 ? 4 : 1];  // L0: the select's wave partials, the row statistics
+  __shared__ int si_s[L0 ? 4 : 1];
+  __shared__ float4 sst_s;
   const int sp = blockIdx.x, head = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   TS_DECL;
   TS_MARK(0);
+  // L0: the old records, the logits, then this head's table columns (thread tid: elements e = tid and
+  // tid + 256 (tid < 32) of (q, k, v), clamped: no load under a branch), in that order: vmcnt retires in
+  // issue order, so the wait for the record does not wait for the logits
+  int4 rold = make_int4(-1, 0, 0, 0);
+  int2 rx = make_int2(0, 0);
+  bool tk = false;
+  float4 lgv[L0 ? VOCAB / 1024 : 1];
+  int zn[L0 ? QH : 1];
+  float zg[L0 ? QH : 1], zt[L0 ? QH : 1], zp[L0 ? QH : 1];
+  int jnx = 0, tnext = 384;
+  int4 ri0 = make_int4(-1, 0, 0, 0);
+  if constexpr (L0) {
+    rold = st.rowinfo[b];
+    rx = st.rowx[b];
+    const unsigned pend = st.selrow[b];
+    const float4* lg = reinterpret_cast<const float4*>(st.logits + (size_t)b * VOCAB);
+#pragma unroll
+    for (int k = 0; k < VOCAB / 1024; ++k) lgv[k] = lg[k * 256 + tid];
+#pragma unroll
+    for (int h = 0; h < QH; ++h) {
+      const int e = min(tid + NW * 64 * h, 3 * HD - 1);
+      zn[h] = (e / HD) * D + head * HD + e % HD;
+      zg[h] = a0->q0_g[zn[h]];
+    }
+    // this step's (text id, position) as the commit sets them (from the records, not the select)
+    tk = pend && rold.x >= 0;
+    const int p1 = min(max(tk ? rold.y + 1 : rold.y, 0), st.max_pos - 1);
+    const int t1 = tk ? rx.y : rold.z;
+#pragma unroll
+    for (int h = 0; h < QH; ++h) {
+      zt[h] = a0->q0_text[(size_t)(t1 < 0 ? 384 : t1) * (3 * D) + zn[h]];
+      zp[h] = a0->q0_pos[(size_t)p1 * (3 * D) + zn[h]];
+    }
+    // the text id of the step after this one (plan_tok of step jn + 1, for rowx): it follows from the old
+    // records too, so its plan load goes out here (every thread, clamped: no load under a branch) and the
+    // copy-back in layer 1's rows kernel is a plain copy
+    jnx = tk ? rx.x + 1 : rx.x;
+    if (st.text_plan) tnext = st.text_plan[(size_t)b * st.plan_stride + min(jnx + 1, st.plan_stride - 1)];
+    ri0 = make_int4(rold.x, p1, 0, 0);  // (slot, position of the new key): all the tile loop needs
+    if (rold.x < 0) {  // idle row: the head-0 block hands the record on and zeroes x, as ar_q0_rows_kernel
+      if (head == 0) {
+        if (tid == 0) {
+          st.rowinfo_n[b] = rold;
+          st.rowx_n[b] = make_int2(jnx, l0_next_tok(st, jnx, tnext));
+        }
+        if (tid < D / 4) reinterpret_cast<float4*>(st.x + (size_t)b * D)[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      return;
+    }
+  }
   // selcopy (layer 0 of a deferred-select step): the records c_attn just built are in the shadow
   // arrays; one block per row copies them back for the rest of the step and clears the flag
   // (the next text id, a dependent plan load, is looked up at the end of the block, when every
   // other load has landed)
-  const int4 ri = selcopy ? st.rowinfo_n[b] : st.rowinfo[b];
+  const int4 ri = L0 ? ri0 : selcopy ? st.rowinfo_n[b] : st.rowinfo[b];
   // QKV: thread tid owns elements e = tid and tid + 256 (tid < 32) of this head's (q, k, v) (element
   // e % 96 of q / k / v for e / 96 = 0 / 1 / 2); their four K-slice partials are issued with the
   // control record (clamped element: no load under a branch)
@@ -1219,7 +1300,8 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
   // lane's key address is the chunk base (wave-uniform) + a fixed lane offset (a trailing split
   // may be empty: it writes m = -inf, l = 0). fp32 KV keeps the unrounded ranges of the parity mode.
   const int chunk = SLOT ? (((t + ns - 1) / ns + ATK - 1) / ATK) * ATK : (t + ns - 1) / ns;
-  const int k0 = sp * chunk, k1 = min(t, k0 + chunk);
+  // (L0, one split: the tile loop runs over the history, keys 0 .. t - 2; key t - 1 comes from LDS after it)
+  const int k0 = sp * chunk, k1 = L0 ? t - 1 : min(t, k0 + chunk);
   // key k of this (slot, head): chunk k / KV_CHUNK (cstride elements apart), row k % KV_CHUNK
   const size_t base = kv_at(layer, st.kv_chunks, st.max_streams, s, head, 0);
   const size_t cstride = (size_t)st.max_streams * N_HEAD * KV_CHUNK * HD;
@@ -1228,7 +1310,7 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
   auto krow = [&](int k) { return (size_t)(k / KV_CHUNK) * cstride + (size_t)(k % KV_CHUNK) * HD; };
   const int part = tid & 3, kq = tid >> 2;  // key slot within the TK-key tile
   float q[24];
-  if constexpr (!QKV) {
+  if constexpr (!NEWKV) {
     const float* qg = st.q + (size_t)b * D + head * HD + part * 24;
 #pragma unroll
     for (int i = 0; i < 24; i += 4) {
@@ -1348,6 +1430,74 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
 #pragma unroll
     for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
   }
+  if constexpr (L0) {
+    // the history's first tiles are in flight; the select chain of ar_q0_rows_kernel, same code and order
+    const GemvArgs& a = *a0;
+    Best bt{-INFINITY, -INFINITY, 0x7fffffff};
+#pragma unroll
+    for (int k = 0; k < VOCAB / 1024; ++k) {
+      const int i0 = (k * 256 + tid) * 4;
+      bt = best_merge(bt, Best{lgv[k].x, -INFINITY, i0});
+      bt = best_merge(bt, Best{lgv[k].y, -INFINITY, i0 + 1});
+      bt = best_merge(bt, Best{lgv[k].z, -INFINITY, i0 + 2});
+      bt = best_merge(bt, Best{lgv[k].w, -INFINITY, i0 + 3});
+    }
+    bt = best_wave(bt);
+    if (lane == 0) { sv_s[wave] = bt.v; sv2_s[wave] = bt.v2; si_s[wave] = bt.i; }
+    lds_barrier();
+    int4 rn = rold;
+    if (tk) {  // (block-uniform) every wave merges the four partials; the row's head-0 block commits
+      Best r{sv_s[0], sv2_s[0], si_s[0]};
+#pragma unroll
+      for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv_s[w], sv2_s[w], si_s[w]});
+      r = softmax_ties(st.logits + (size_t)b * VOCAB, r, lane);
+      const int sl = rold.x, p = rold.y + 1, j = rx.x;
+      rn = make_int4(sl, min(p, st.max_pos - 1), rx.y, min(max(r.i, 0), VOCAB - 1));
+      if (head == 0 && tid == 0) {  // argmax_commit, with the records into the shadow arrays
+        if (p >= st.max_pos) atomicOr(st.err, 1);
+        if (j < st.plan_stride) {
+          st.tok_plan[(size_t)b * st.plan_stride + j] = r.i;
+          if (st.margin_plan) st.margin_plan[(size_t)b * st.plan_stride + j] = r.v - r.v2;
+        }
+        st.prev[sl] = r.i;
+        st.pos[sl] = p;
+        st.rowstep[b] = j + 1;
+      }
+    }
+    if (head == 0 && tid == 0) {
+      st.rowinfo_n[b] = rn;
+      st.rowx_n[b] = make_int2(jnx, l0_next_tok(st, jnx, tnext));  // {this step, the next text id}: rowx as it is copied back
+    }
+    float zc[QH];
+#pragma unroll
+    for (int h = 0; h < QH; ++h) zc[h] = a.q0_code[(size_t)min(max(rn.w, 0), VOCAB - 1) * (3 * D) + zn[h]];
+    if (wave == 0) {
+      const float4 s4 = q0_row_stats(a, rn, b, lane, head == 0);
+      if (lane == 0) sst_s = s4;
+    }
+    lds_barrier();
+    const float4 ss = sst_s;
+    const float cz = rn.y == 0 ? 0.f : 1.f;  // position 0: the codebook half of the input is zero
+#pragma unroll
+    for (int h = 0; h < QH; ++h) {
+      const int e = tid + NW * 64 * h;
+      const float v = ss.z * (((zt[h] + cz * zc[h]) * ss.x + zp[h]) - ss.y * zg[h]);
+      if (e < HD) {
+        qs_s[e] = v;
+      } else if (e < 3 * HD) {  // K / V of the new key: appended at (slot, position), kept in LDS
+        const int which = e / HD - 1, d = e % HD;
+        TKV hv;  // the value store_kv stores
+        if constexpr (sizeof(TKV) == 2) hv = f32_to_bf16(v);
+        else hv = f32_to_fp8(v);
+        kvh_s[which][d] = hv;
+        reinterpret_cast<TKV*>(which ? st.vc : st.kc)[base + krow(ri.y) + d] = hv;
+      }
+    }
+    lds_barrier();
+#pragma unroll
+    for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
+    TS_MARK(1);
+  }
   if constexpr (BF) qsplit_make(q, qsp);
   // DEPTH 2 (few tiles per block, the B <= 2 step): leave after the last valid tile. DEPTH >= 4
   // (long splits, batched steps): whole groups of DEPTH tiles with no exit inside a group (a tile
@@ -1361,6 +1511,29 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
       issue(kb + (d + DEPTH) * TK, kpr[d], vpr[d]);
       if (DEPTH > 2) __builtin_amdgcn_sched_barrier(0);  // keep the refill right behind its tile
     }
+  }
+  if constexpr (L0) {
+    // key t - 1 from LDS, by the lane quad that owns it in the tile holding it (tiles start at multiples
+    // of TK): the step the two-launch form takes last in that slot, with the bits its store holds
+    const bool mine = kq == (t - 1) % TK;
+    KvPiece<TKV> kx[3], vx[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {  // (fp8: uint2, bf16: uint4)
+      kx[i].load(kvh_s[0] + part * 24 + i * 8);
+      vx[i].load(kvh_s[1] + part * 24 + i * 8);
+    }
+    if constexpr (BF) {
+      uint4 ku[3], vu[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { ku[i] = reinterpret_cast<const uint4&>(kx[i]); vu[i] = reinterpret_cast<const uint4&>(vx[i]); }
+      slot_softmax_step_bf16(m, l, o2, qsp, ku, vu, mine);
+    } else {
+      float kf[24], vf[24];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { kx[i].get(kf + 8 * i); vx[i].get(vf + 8 * i); }
+      slot_softmax_step(m, l, o, q, kf, vf, mine);
+    }
+    TS_SAVE(9, layer, head + N_HEAD * b);  // (entry, q ready, end of the KV loop); tag 2 keeps (entry, loop end, exit)
   }
   if constexpr (BF) {
 #pragma unroll
@@ -1414,6 +1587,18 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
       ml[1] = lv;
     }
   }
+}
+
+template <typename TKV, int DEPTH, int NW, bool QKV = false>
+__global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int layer, int ns_max, int direct,
+                                                         int selcopy) {
+  attn_v2_body<TKV, DEPTH, NW, QKV, false>(st, layer, ns_max, direct, selcopy, nullptr);
+}
+
+// the fused layer-0 form (L0 above): grid (1, 8 heads, B), the launch in ar_q0_rows_kernel's place
+template <typename TKV>
+__global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArgs a, int direct) {
+  attn_v2_body<TKV, 2, 4, false, true>(a.st, 0, 1, direct, 0, &a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1719,12 +1904,45 @@ __device__ __forceinline__ void embed_row(const GemvArgs& a, int4 ri, int lane, 
     v[j] = make_float4(v[j].x / den + pe[j].x, v[j].y / den + pe[j].y, v[j].z / den + pe[j].z, v[j].w / den + pe[j].w);
 }
 
+// One wave: {1 / den, mean, rstd} of row b's embedding row for record rn, the statistics that layer 0's
+// c_attn from the q0 tables needs (mean, rstd as wave_ln_regs computes them); store_x: the row goes to
+// st.x (one block per row). Shared by ar_q0_rows_kernel and the fused layer-0 attention: one reduction order.
+__device__ __forceinline__ float4 q0_row_stats(const GemvArgs& a, int4 rn, int b, int lane, bool store_x) {
+  float4 v[3];
+  float rden = 0.f;
+  embed_row(a, rn, lane, v, &rden);
+  if (store_x) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = v[j];
+  }
+  float sm = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) sm += (v[j].x + v[j].y) + (v[j].z + v[j].w);
+  const float mean = wave_sum(sm) * (1.0f / D);
+  float qs = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const float4 d = make_float4(v[j].x - mean, v[j].y - mean, v[j].z - mean, v[j].w - mean);
+    qs += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
+  }
+  const float rstd = 1.0f / sqrtf(wave_sum(qs) * (1.0f / D) + 1e-5f);
+  return make_float4(rden, mean, rstd, 0.f);
+}
+
 
 // MODE: RMODE_* (ar_plan.h). The fp32 output rows of the _F32 modes go to st.h ([B][768]; the batched
 // fp32 parity mode's c_attn / lm_head operand, ar_qkv_ksplit_f32_kernel / ar_f32b_kernel FIN_LN_ROWS:
 // h is free between mlp c_proj and the next c_fc)
-template <int MODE>
+template <int MODE_>
 __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_rows_kernel(GemvArgs a) {
+  // RMODE_LN_Y_COPY (layer 1 of a step whose layer-0 attention is the fused form, ArStepPlan::l0_fused): LN_Y,
+  // and the wave copies its row's control records back from the shadow arrays, where the fused attention's
+  // head-0 block committed them (the row's other head blocks were reading the old ones). This launch is the
+  // first after it that may write rowinfo and runs before its next reader, this layer's c_attn epilogue. As
+  // the attention's selcopy, without its plan lookup: the fused block left the next text id in rowx_n. The two
+  // records are loaded with the row (every lane, the same address: no load under a branch) and stored last.
+  constexpr bool COPY = MODE_ == RMODE_LN_Y_COPY;
+  constexpr int MODE = COPY ? RMODE_LN_Y : MODE_;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int b = blockIdx.x * (blockDim.x >> 6) + wave;
   if (b >= a.B) return;
@@ -1733,9 +1951,15 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_rows_kernel(GemvArgs a
   float4 g[3], v[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) g[j] = *reinterpret_cast<const float4*>(a.ln_w + j * 256 + lane * 4);
+  int4 rcp = make_int4(0, 0, 0, 0);
+  int2 rxcp = make_int2(0, 0);
   if (MODE == RMODE_LN || MODE == RMODE_LN_Y || MODE == RMODE_LN_Y_F32) {
     XRow<MODE == RMODE_LN_Y_F32 ? GIN_LN_Y : MODE> r;
     xrow_issue(a, b, lane, r);
+    if constexpr (COPY) {
+      rcp = a.st.rowinfo_n[b];
+      rxcp = a.st.rowx_n[b];
+    }
     __builtin_amdgcn_sched_barrier(0);  // gamma and the rows issued up front (the scheduler sank a
                                         // gamma load behind the variance: one more round trip)
     xrow_sum(r, v);
@@ -1760,6 +1984,14 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_rows_kernel(GemvArgs a
   for (int j = 0; j < 3; ++j) {
     if (a.xpk) *reinterpret_cast<uint2*>(a.st.xn + xfrag(b, j * 256 + lane * 4, D)) = pack4_bf16(v[j]);
     else dst[j * 64 + lane] = pack4_bf16(v[j]);
+  }
+  if constexpr (COPY) {
+    if (lane == 0) {
+      a.st.rowinfo[b] = rcp;
+      a.st.rowx[b] = rxcp;
+      a.st.selrow[b] = 1u;  // (ar_q0_rows_kernel's / the fused attention's pending select of the next step)
+      if (b == 0) *a.st.selp = 0u;
+    }
   }
   TS_SAVE(a.N == VOCAB ? 8 : 0, a.layer, blockIdx.x);
 }
@@ -1966,6 +2198,9 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_gran_kernel(GemvArg
 // which attention layer 0 copies back (it also sets the row's pending flag). Round 6: one block per row
 // (ar_embed_select_kernel<false, true>) spent 4.7 us of the B = 32 step in this launch, its blocks
 // each loading the 27 KB of table rows with the 16 KB of logits.
+// (Where the plan sets l0_fused, bf16 KV at 9 <= B <= 32 and fp8 KV at 17 <= B <= 32 by default, this launch
+// is gone: ar_attn_l0_kernel does the same work per (row, head) ahead of its tile loop. Option l0a 0, the
+// 8-wave attention cells and 4 <= B <= 8 run this kernel.)
 __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_rows_kernel(GemvArgs a) {
   __shared__ float sv[4], sv2[4];
   __shared__ int si[4];
@@ -2026,25 +2261,8 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_rows_kernel(GemvArg
   }
   const float tc = a.q0_code[(size_t)min(max(rn.w, 0), VOCAB - 1) * (3 * D) + n];
   if (wave == 0) {
-    float4 v[3];
-    float rden = 0.f;
-    embed_row(a, rn, lane, v, &rden);
-    if (cx == 0) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = v[j];
-    }
-    float sm = 0.f;  // (mean, rstd) as wave_ln_regs computes them
-#pragma unroll
-    for (int j = 0; j < 3; ++j) sm += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-    const float mean = wave_sum(sm) * (1.0f / D);
-    float qs = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float4 d = make_float4(v[j].x - mean, v[j].y - mean, v[j].z - mean, v[j].w - mean);
-      qs += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(qs) * (1.0f / D) + 1e-5f);
-    if (lane == 0) sst = make_float4(rden, mean, rstd, 0.f);
+    const float4 s4 = q0_row_stats(a, rn, b, lane, cx == 0);
+    if (lane == 0) sst = s4;
   }
   __syncthreads();
   const float4 st = sst;
@@ -3183,7 +3401,8 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
       if (!(p.sel == SEL_ARGMAX || (mf ? p.sel == SEL_EMBED || p.sel == SEL_Q0_ROWS || (ln && p.sel == SEL_LN_GRAN)
                                        : p.sel == SEL_GRAN)))
         ar_plan_bug(p, "c_attn");
-      if (l == 0 && p.sel == SEL_LN_GRAN) {  // select + embedding in c_attn's prologue
+      if (l == 0 && p.l0_fused) {  // no launch: attention layer 0 runs the select and the q0 tables itself
+      } else if (l == 0 && p.sel == SEL_LN_GRAN) {  // select + embedding in c_attn's prologue
         launch_mfma_ln<MLOUT_QKV, MLMODE_EMBED_SELECT>(a, s);
       } else if (l == 0 && p.sel == SEL_Q0_ROWS) {  // select + c_attn from the q0 tables, 9 slices per row
         hipLaunchKernelGGL(ar_q0_rows_kernel, dim3(3 * D / 256, B), dim3(256), 0, s, a);
@@ -3195,6 +3414,7 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
         else launch_mfma_ln<MLOUT_QKV, MLMODE_LN_Y>(a, s);
       } else if (mf) {  // rows kernel: LayerNorm (layer 0: of the embedding; else of x + the MLP copies)
         if (l == 0) hipLaunchKernelGGL((ar_rows_kernel<RMODE_EMBED>), dim3(B), dim3(64), 0, s, a);
+        else if (l == 1 && p.l0_fused) hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y_COPY>), dim3(B), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y>), dim3(B), dim3(64), 0, s, a);
         launch_mfma2<768, M2OUT_QKV>(a, s);
       } else if (l == 0 && p.q0_gran) {  // B <= 2: select + c_attn from the q0 tables
@@ -3210,6 +3430,14 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
       }
       break;
     case OP_ATTN:
+      if (l == 0 && p.l0_fused) {  // select + layer 0's q / k / v + attention (ar_plan_step: bf16 / fp8 KV, 4 waves, one split)
+        if (p.kv_dtype == LVX_DTYPE_BF16)
+          hipLaunchKernelGGL(ar_attn_l0_kernel<bf16_t>, dim3(1, N_HEAD, B), dim3(256), 0, s, a, p.attn_direct);
+        else if (p.kv_dtype == LVX_DTYPE_FP8)
+          hipLaunchKernelGGL(ar_attn_l0_kernel<fp8_t>, dim3(1, N_HEAD, B), dim3(256), 0, s, a, p.attn_direct);
+        else ar_plan_bug(p, "fused layer-0 attention");
+        break;
+      }
       launch_attn(a.st, p.kv_dtype, B, l, s, p.nsplit, p.attn_direct, p.selcopy && l == 0, false, p.attn8);
       break;
     case OP_CPROJ:

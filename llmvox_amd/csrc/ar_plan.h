@@ -24,8 +24,9 @@ enum { GIN_LN = 0, GIN_H = 1, GIN_MERGE = 2, GIN_EMBED = 3, GIN_LN_Y = 4, GIN_EM
 // | split-K partial into a pending copy (ar_f32b_kernel) | logits + per-block top-1 / top-2 granules
 enum { GOUT_QKV = 0, GOUT_RESID = 1, GOUT_GELU = 2, GOUT_LOGITS = 3, GOUT_SPLITK = 6, GOUT_LOGITS_GRAN = 9 };
 // ar_rows_kernel MODE (-> bf16 operand rows xn): LayerNorm(x) | embedding (stores x) then LayerNorm |
-// LayerNorm(x + pending copies), x made final | as LN_Y / EMBED with fp32 output rows in st.h
-enum { RMODE_LN = 0, RMODE_EMBED = 3, RMODE_LN_Y = 4, RMODE_LN_Y_F32 = 5, RMODE_EMBED_F32 = 6 };
+// LayerNorm(x + pending copies), x made final | as LN_Y / EMBED with fp32 output rows in st.h | LN_Y that
+// also copies the fused layer-0 attention's shadow control records back (layer 1 of an l0_fused step)
+enum { RMODE_LN = 0, RMODE_EMBED = 3, RMODE_LN_Y = 4, RMODE_LN_Y_F32 = 5, RMODE_EMBED_F32 = 6, RMODE_LN_Y_COPY = 7 };
 // ar_mfma2_kernel OUT: as GOUT, plus h (bf16) = gelu(out) | split-K partial into a pending copy |
 // x += out with the bf16 copy x * ln_2.weight and the row statistics (c_fc's operand). XM: LayerNorm
 // applied after the GEMM from those statistics (c_fc)
@@ -59,7 +60,8 @@ enum ArPath { PATH_GEMV, PATH_MFMA_LN, PATH_MFMA_ROWS, PATH_BT, PATH_F32B };
 //   SEL_GRAN     B <= 2 GEMV: lm_head publishes per-block granules, the next step's c_attn layer 0 reduces them
 //   SEL_EMBED    batched: the next step's ar_embed_select_kernel reduces the logits, then c_attn
 //   SEL_LN_GRAN  4 <= B <= 8: granules reduced in the prologue of c_attn layer 0 (MLMODE_EMBED_SELECT)
-//   SEL_Q0_ROWS  bf16, 4 <= B <= 32: select + layer 0's c_attn from the q0 tables (ar_q0_rows_kernel)
+//   SEL_Q0_ROWS  bf16, 4 <= B <= 32: select + layer 0's c_attn from the q0 tables (ar_q0_rows_kernel; where the
+//                plan sets l0_fused, inside attention layer 0 instead: ar_attn_l0_kernel)
 //   SEL_SAMPLE   ar_sample_kernel after lm_head: the seeded temperature / top-k draw of the slots that
 //                sample, the greedy select for the others (not deferred: the step's other kernels run
 //                as under SEL_ARGMAX, and GemvArgs::defer_sel carries SEL_ARGMAX)
@@ -76,7 +78,11 @@ struct ArStepPlan {
   // layer 0 copies the select's shadow records back
   int nsplit, attn_direct;
   bool attn8, selcopy;
-  bool fused_mlp;  // c_fc + gelu + mlp c_proj in ar_mlp_fused_kernel (mlp c_proj has no kernel of its own)
+  // SEL_Q0_ROWS with a one-split 4-wave attention (option l0a): no ar_q0_rows_kernel launch, attention layer 0
+  // runs the select and the q0 tables for its own (row, head) (ar_attn_l0_kernel), and the shadow records are
+  // copied back by layer 1's ar_rows_kernel instead of attention layer 0
+  bool l0_fused;
+  bool fused_mlp; // c_fc + gelu + mlp c_proj in ar_mlp_fused_kernel (mlp c_proj has no kernel of its own)
   bool q0_gran;    // SEL_GRAN with layer 0's c_attn from the q0 tables (ar_q0_gran_kernel)
   int xpk;         // bf16 operand rows kept fragment-packed (GemvArgs::xpk)
   bool ksplit, qsplit;  // PATH_F32B: mlp c_proj / c_attn as K slices
@@ -176,6 +182,11 @@ inline ArStepPlan ar_plan_step(const Opts& o_, int wdtype, int kvdtype, int B, b
   // option exp bits 32 / 64 / 128, were removed in round 6.)
   p.attn8 = mf && B >= 5 && (B <= 8 || (kvdtype == LVX_DTYPE_FP8 && B <= 16));
   p.nsplit = p.path == PATH_GEMV ? NSPLIT : (mf && (B > 8 || p.attn8)) ? 1 : attn_ns_max(B);
+  // The fused layer-0 form where the step has ar_q0_rows_kernel and its attention is one split per (row, head) in
+  // 4-wave blocks: bf16 KV at 9 <= B <= 32, fp8 KV at 17 <= B <= 32 (the 8-wave cells keep the two launches).
+  // Every block then has the select chain ahead of its tile loop, with the history's first tiles in flight under it.
+  // (fp32 KV under bf16 weights keeps the two launches: the fused form has the per-key-slot kernels only)
+  p.l0_fused = o.l0a && p.sel == SEL_Q0_ROWS && p.nsplit == 1 && !p.attn8 && B >= 9 && kvdtype != LVX_DTYPE_F32;
   // fragment-packed operand rows on the v2 steps with the rows kernel at B <= 32
   p.xpk = (p.path == PATH_MFMA_ROWS && B <= 32) ? 1 : 0;
   p.attn_direct = p.nsplit > 1 || !(mf || p.path == PATH_F32B) ? ATTN_PARTIALS

@@ -45,6 +45,9 @@ struct Opts {
   int l0q = 1;           // bf16 GEMV / MFMA steps with a deferred select, B <= 32 (not 3): layer 0's q / k / v from
                          // the precomputed tables (ArWeights q0_*) in the kernel that commits the select
                          // (ar_q0_gran_kernel, ar_q0_rows_kernel); 0: the path's other select form + c_attn
+  int l0a = 1;           // SEL_Q0_ROWS steps whose attention is one split in 4-wave blocks (bf16 KV 9 <= B <= 32, fp8 KV
+                         // 17 <= B <= 32): ar_q0_rows_kernel's work inside attention layer 0 (ar_attn_l0_kernel);
+                         // 0: the two launches (bit-identical: tests/test_gpu_l0_fused.py)
 };
 const Opts& opts();  // the calling thread's bound options (the defaults when none is bound)
 struct OptScope {    // binds `o` to this thread until the scope ends

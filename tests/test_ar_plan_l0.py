@@ -1,0 +1,75 @@
+"""The fused layer-0 field of the decode step's plan (llmvox_amd/csrc/ar_plan.h, ArStepPlan::l0_fused)
+without a GPU: tests/ar_plan_l0_dump.cpp, built like tests/ar_plan_dump.cpp, prints it for every weight
+dtype, KV dtype, B = 1..66, row mode, table presence and sample flag under the option sets below.
+Checked: the field is set exactly on bf16 weights with the tables, default options, no sampling, and a
+one-split 4-wave attention: bf16 KV at 9 <= B <= 32 and fp8 KV at 17 <= B <= 32; it is clear for sampling,
+fp32, bt 2, l0q 0, defer_select 0, l0a 0, B <= 8 and B > 32; and where it is set the step still has the
+select form, the split count and the record copy-back it has with option l0a 0."""
+import os
+import subprocess
+from collections import namedtuple
+
+import pytest
+
+from tests.test_ar_plan import CSRC, ROOT, _hipcc
+
+SETS = ["-", "l0a=0", "l0q=0", "defer_select=0", "defer_select=2", "bt=2", "bt=0", "f32b=0", "ln_max=4",
+        "l0a=0,l0q=0", "bt=2,l0a=1"]
+Row = namedtuple("Row", "opts wd kv B row q0 sample path sel nsplit attn8 selcopy l0_fused")
+
+
+@pytest.fixture(scope="module")
+def plans(tmp_path_factory):
+    cc = _hipcc()
+    if cc is None:
+        pytest.skip("no hipcc to build the plan program with")
+    exe = str(tmp_path_factory.mktemp("ar_plan_l0") / "ar_plan_l0_dump")
+    subprocess.run([cc, "-O1", "-std=c++17", "-x", "hip", "--offload-host-only", "-Wall", "-Werror",
+                    "-I", os.path.join(ROOT, "include"), "-I", CSRC, os.path.join(ROOT, "tests", "ar_plan_l0_dump.cpp"),
+                    "-o", exe], check=True)
+    out = subprocess.run([exe] + SETS, check=True, capture_output=True, text=True).stdout
+    rows = {}
+    for line in out.splitlines():
+        f = line.split()
+        r = Row(f[0], f[1], f[2], int(f[3]), int(f[4]), int(f[5]), int(f[6]), f[7], f[8], *map(int, f[9:]))
+        rows[(r.opts, r.wd, r.kv, r.B, r.row, r.q0, r.sample)] = r
+    assert len(rows) == len(SETS) * 2 * 3 * 67 * 2 * 2
+    return rows
+
+
+def _cell(r):
+    """the cells the fused form is built for"""
+    return (r.wd == "bf16" and r.q0 and not r.row and not r.sample and r.B <= 32
+            and ((r.kv == "bf16" and r.B >= 9) or (r.kv == "fp8" and r.B >= 17)))
+
+
+def test_fused_field_is_set_exactly_on_its_cells(plans):
+    n = 0
+    for r in plans.values():
+        want = _cell(r) and r.opts in ("-", "defer_select=2", "bt=0", "f32b=0", "ln_max=4")
+        assert bool(r.l0_fused) == want, r
+        n += want
+    assert n == 5 * ((32 - 9 + 1) + (32 - 17 + 1))
+
+
+def test_fused_field_is_clear_elsewhere(plans):
+    for r in plans.values():
+        if (r.sample or r.wd == "fp32" or r.kv == "fp32" or r.row or not r.q0 or r.B <= 8 or r.B > 32
+                or r.opts in ("l0a=0", "l0q=0", "defer_select=0", "bt=2", "l0a=0,l0q=0", "bt=2,l0a=1")):
+            assert not r.l0_fused, r
+        if r.kv == "fp8" and r.B <= 16:  # the 8-wave cells keep the two launches
+            assert not r.l0_fused, r
+        if r.l0_fused:
+            assert (r.path, r.sel, r.nsplit, r.attn8, r.selcopy) == ("mfma_rows", "q0_rows", 1, 0, 1), r
+
+
+def test_option_l0a_changes_nothing_else(plans):
+    """l0a 0 is the same plan without the field: the independent form the fused one is held to."""
+    n = 0
+    for key, r in plans.items():
+        if r.opts != "-":
+            continue
+        off = plans[("l0a=0",) + key[1:]]
+        assert off._replace(opts="-", l0_fused=r.l0_fused) == r, (r, off)
+        n += 1
+    assert n == 2 * 3 * 67 * 2 * 2
