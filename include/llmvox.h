@@ -170,6 +170,68 @@ int lvx_stream_set(lvx_ctx* ctx, int slot, int pos, int prev_token, void* stream
  * then comes from the GEMM instead of the table rows, and the logits differ in the last bits. With no
  * slot sampling, plans, kernels and ids are exactly those of a context that never sampled. */
 int lvx_stream_sampling(lvx_ctx* ctx, int slot, float temperature, int top_k, uint64_t seed, void* stream);
+/* lvx_stream_sampling with a nucleus (top_p), a min-p crop and a repetition penalty over the slot's recent
+ * tokens. lvx_stream_sampling is this call with the neutral values top_p 1, min_p 0, repetition_penalty 1,
+ * repetition_window 64: with those the kernel skips every phase below and draws today's tokens, bit for bit.
+ * LVX_E_ARG: a null p, a value that is not finite or outside: temperature >= 0, top_k >= 0, top_p in (0, 1],
+ * min_p in [0, 1), repetition_penalty > 0, repetition_window in [1, 256]. A slot with temperature 0 decodes
+ * greedily and ignores every other field, as it ignores top_k: penalised or cropped greedy decoding is not
+ * offered.
+ *
+ * The rule of a sampled step (T > 0, p the position of the step being decided; fp32 unless it says integer):
+ *   1. penalty. R = repetition_penalty (1: off), W = repetition_window. The window set is the tokens decided
+ *      by the steps at positions max(hist_from, p - W) .. p - 1 (empty at p = 0 or when hist_from >= p; see
+ *      "history" below); a token that occurs several times is penalised once. For i in the set
+ *        l'[i] = logits[i] > 0 ? logits[i] / R : logits[i] * R    (IEEE division / product; +-0 take the product),
+ *      otherwise l'[i] = logits[i]. Exact.
+ *   2. temperature. z[i] = l'[i] / T, zmax = max z: taken after the penalty, which can move the maximum.
+ *   3. top_k on z as above, ties at the threshold kept.
+ *   4. top_p (1: off, the step is skipped), over integers, so that no summation order enters:
+ *        w[i] = exp(z[i] - zmax) for the i kept so far, else 0;   q[i] = floor(w[i] * 2^24) (integer);
+ *        Sq = sum q;   Aq(v) = sum of q[i] over z[i] > v;   P = round(top_p * 2^24) clamped to [1, 2^24]
+ *        (P = 2^24 counts as off);
+ *        i stays kept iff Aq(z[i]) * 2^24 < P * Sq   (64-bit integers; the largest product is below 2^61).
+ *      The mass strictly above a token decides it: equal z are kept or dropped together, the maximum always stays.
+ *   5. min_p (0: off). lnminp = (float)log((double)min_p), computed once by this call;
+ *        i stays kept iff fl(z[i] - zmax) >= lnminp. Exact.
+ *   6. the draw, as above, over the final kept set: the same w, running sums, u, first crossing and fallback.
+ *   7. margin_plan keeps its meaning: top-1 minus top-2 of the raw logits.
+ * Every crop is a threshold on z: the kept set is {i : z[i] >= v} for one v, which lvx_sample_kept reports.
+ * The result is a function of (logits, parameters, seed, position, history) alone, the same in any row of any
+ * batch and in any run.
+ *
+ * History. While any slot of the context samples, the select of every step stores the token it decides at
+ * position p into a per-slot record hist[slot][p] (uint16, max_streams * max_positions * 2 bytes), for the rows
+ * of greedy slots beside sampling ones too; a context with no sampling slot runs today's kernels and records
+ * nothing. Entries are written by absolute position, so a speculative run-ahead followed by a rewind only
+ * rewrites entries at and above the rewind point. hist_from[slot], the first position whose entry is known,
+ * is kept on the device in stream order: lvx_stream_reset sets it to 0; lvx_stream_set(slot, pos, prev) stores
+ * prev at hist[slot][pos - 1] (pos > 0) and then, for pos <= the slot's old position, hist_from =
+ * min(hist_from, max(pos - 1, 0)), otherwise (a jump over positions never decoded) hist_from = max(pos - 1, 0);
+ * a call of this function that takes the slot's temperature from 0 to > 0 sets hist_from to the slot's
+ * current position (plans that do not record may have decided its earlier tokens).
+ * lvx_ar_forward_row (the drop-in row mode) moves a slot's position without recording a token or touching
+ * hist_from: call lvx_stream_set or lvx_stream_reset on the slot before sampled steps with a penalty follow
+ * row-mode calls, or the window reaches entries that were never recorded. */
+typedef struct {
+  float temperature;
+  int top_k;
+  float top_p;
+  float min_p;
+  float repetition_penalty;
+  int repetition_window;
+  uint64_t seed;
+} lvx_sampling;
+int lvx_stream_sampling_ex(lvx_ctx* ctx, int slot, const lvx_sampling* p, void* stream);
+/* Test hook: read (write = 0) or write (write != 0) the history entries hist[slot][pos0 .. pos0 + n) from / to
+ * tokens_dev int32 [n] (written values are clamped to [0, 4096)); a write also lowers hist_from to pos0.
+ * LVX_E_ARG for a slot out of range or null tokens_dev, LVX_E_CAPACITY for pos0 < 0, n < 1 or
+ * pos0 + n > max_positions. */
+int lvx_stream_history(lvx_ctx* ctx, int slot, int pos0, int n, int32_t* tokens_dev, int write, void* stream);
+/* Test hook: per batch row b of the last sampled select (a row of a slot with temperature > 0), dst_dev int32
+ * [B][4] = {number of kept tokens, the fp32 bits of the lowest kept z, number of distinct penalised tokens, 0}.
+ * The kernel leaves them with one 16-byte store beside its commit. */
+int lvx_sample_kept(lvx_ctx* ctx, int B, int32_t* dst_dev, void* stream);
 /* Measurement hook (bench.py): launch one kernel class of the decode step `iters` times for the
  * batch rows `slots` at their current positions (0 c_attn, 1 attention, 2 c_proj+merge,
  * 3 c_fc (with the bf16 fused MLP at B <= 2: c_fc + gelu + mlp c_proj), 4 mlp c_proj, 5 lm_head).

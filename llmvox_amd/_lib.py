@@ -38,6 +38,12 @@ class LvxConfig(ctypes.Structure):
                 ("max_codec_frames", ctypes.c_int), ("codec_dtype", ctypes.c_int)]
 
 
+class LvxSampling(ctypes.Structure):  # lvx_sampling
+    _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int), ("top_p", ctypes.c_float),
+                ("min_p", ctypes.c_float), ("repetition_penalty", ctypes.c_float),
+                ("repetition_window", ctypes.c_int), ("seed", ctypes.c_uint64)]
+
+
 class LvxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"[lvx {code}] {msg}")
@@ -90,6 +96,9 @@ _SIGS = {
     "lvx_probe_kernel": (_I, [_P, _I, _I, _P, _I, _P]),
     "lvx_stream_set": (_I, [_P, _I, _I, _I, _P]),
     "lvx_stream_sampling": (_I, [_P, _I, ctypes.c_float, _I, ctypes.c_uint64, _P]),
+    "lvx_stream_sampling_ex": (_I, [_P, _I, ctypes.POINTER(LvxSampling), _P]),
+    "lvx_stream_history": (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    "lvx_sample_kept": (_I, [_P, _I, _P, _P]),
     "lvx_select_probe": (_I, [_P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
     "lvx_kv_write": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "lvx_kv_write_raw": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),

@@ -1606,6 +1606,13 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArg
 // margin, then the slot's prev token / position / plan step advance.
 // ---------------------------------------------------------------------------------
 // one block of 256 threads per batch row b (ri = its live rowinfo record); sv / sv2 / si: 4 LDS words each
+// the token history of the sampling plans (ArState::hist): the token decided by the step at position p
+__device__ __forceinline__ void hist_store(const ArState& st, int s, int p, int tok) {
+  if (st.rowstep && p < st.max_pos) st.hist[(size_t)s * st.max_pos + p] = (uint16_t)tok;
+}
+
+// HIST: a greedy row of a sampling plan (ar_sample_kernel) also records its token
+template <bool HIST = false>
 __device__ __forceinline__ void argmax_row(const ArState& st, int b, int4 ri, float* sv, float* sv2, int* si) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float4* lg = reinterpret_cast<const float4*>(st.logits + (size_t)b * VOCAB);
@@ -1626,7 +1633,10 @@ __device__ __forceinline__ void argmax_row(const ArState& st, int b, int4 ri, fl
     Best r{sv[0], sv2[0], si[0]};
     for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
     r = softmax_ties(st.logits + (size_t)b * VOCAB, r, lane);
-    if (lane == 0) argmax_commit(st, b, ri, r);
+    if (lane == 0) {
+      argmax_commit(st, b, ri, r);
+      if constexpr (HIST) hist_store(st, ri.x, ri.y, r.i);
+    }
   }
 }
 
@@ -1692,21 +1702,48 @@ __device__ __forceinline__ int wave_min_i32(int v) {
              min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
 
+__device__ __forceinline__ unsigned long long wave_scan_u64(unsigned long long v, int lane) {  // inclusive
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long up = __shfl_up(v, o);
+    if (lane >= o) v += up;
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v, int lane) {
+  return __builtin_amdgcn_readlane(wave_scan_i32(v, lane), 63);
+}
+
+// The extended rule (lvx_stream_sampling_ex; include/llmvox.h has it in full, tests/sampling_ex_ref.py
+// recomputes it). Each phase runs only for a slot that asks for it (block-uniform branches); with the
+// neutral parameters the kernel is the one above.
+//   repetition penalty: thread t < n loads history entry p - 1 - t (ArState::hist) and sets the token's bit
+//     in a 4,096-bit LDS bitmap; the 16 logits a thread owns are half a word of it, tested before the division
+//     by T. The penalised logits' maximum is reduced again: the penalty can move it.
+//   nucleus: q[i] = floor(w[i] 2^24) as integers, Sq their sum; a second 4-pass radix select over the same
+//     keys whose 256 LDS bins accumulate q in 64 bits (ds_add_u64): digit by digit, the lowest bin whose
+//     mass strictly above it, A, satisfies A 2^24 < P Sq. Integer sums: no summation order enters.
+//   min-p: fl(z - zmax) >= lnminp, per element.
+// The commit also stores the token at hist[slot][p] and leaves {kept, lowest kept z, penalised, 0} per row.
 __global__ __launch_bounds__(256) void ar_sample_kernel(ArState st) {
-  __shared__ float sv[4], sv2[4], wsum[4];
-  __shared__ int si[4], wcnt[4], wfirst[4], wlast[4];
-  __shared__ unsigned hist[256], pick[2];
+  __shared__ float sv[4], sv2[4], wsum[4], wmax[4], wlow[4];
+  __shared__ int si[4], wcnt[4], wfirst[4], wlast[4], wkept[4], wpen[4];
+  __shared__ unsigned hist[256], pick[2], pen[VOCAB / 32];
+  __shared__ unsigned long long qh[256], wq[4], qpick;
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int4 ri = st.rowinfo[b];
   const int s = ri.x;
   if (s < 0) return;
-  const float T = st.smp_temp[s];
+  const uint4 par = st.smp[2 * s], ex = st.smp[2 * s + 1];  // one round trip for every parameter
+  const float T = __uint_as_float(par.x);
   if (!(T > 0.f)) {  // a greedy slot beside sampling ones: ar_argmax_kernel's code (block-uniform branch)
-    argmax_row(st, b, ri, sv, sv2, si);
+    argmax_row<true>(st, b, ri, sv, sv2, si);
     return;
   }
-  const int K = st.smp_topk[s];
-  const uint2 seed = st.smp_seed[s];
+  const int K = (int)par.y;
+  const uint2 seed = make_uint2(par.z, par.w);
+  const unsigned P24 = ex.x;
+  const float lnminp = __uint_as_float(ex.y), R = __uint_as_float(ex.z);
   // 16 consecutive logits per thread; top-1 / top-2 of the raw logits for the margin
   const float4* lg = reinterpret_cast<const float4*>(st.logits + (size_t)b * VOCAB) + tid * 4;
   float z[16];
@@ -1726,9 +1763,35 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState st) {
   __syncthreads();
   Best r{sv[0], sv2[0], si[0]};
   for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
+  float lmax = r.v;
+  int npen = 0;
+  if (R != 1.0f) {  // repetition penalty over the tokens of positions max(hist_from, p - W) .. p - 1
+    const int p = ri.y;
+    const int n = min(min(max((int)ex.w, 0), 256), max(p - max(st.hist_from[s], 0), 0));
+    if (tid < VOCAB / 32) pen[tid] = 0u;
+    __syncthreads();
+    if (tid < n) {
+      const unsigned tk = st.hist[(size_t)s * st.max_pos + (p - 1 - tid)] & (unsigned)(VOCAB - 1);
+      atomicOr(&pen[tk >> 5], 1u << (tk & 31u));
+    }
+    __syncthreads();
+    const unsigned bits = (pen[tid >> 1] >> ((tid & 1) * 16)) & 0xffffu;
+    float lm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if ((bits >> j) & 1u) z[j] = z[j] > 0.f ? z[j] / R : z[j] * R;
+      lm = fmaxf(lm, z[j]);
+    }
+    lm = wave_max(lm);
+    const int c = wave_sum_i32(__popc(bits), lane);
+    if (lane == 0) { wmax[wave] = lm; wpen[wave] = c; }
+    __syncthreads();
+    lmax = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    npen = (wpen[0] + wpen[1]) + (wpen[2] + wpen[3]);
+  }
 #pragma unroll
   for (int j = 0; j < 16; ++j) z[j] = z[j] / T;
-  const float zmax = r.v / T;  // = max z: the division is monotone
+  const float zmax = lmax / T;  // = max z: the division is monotone
 
   // top-k threshold: the K-th largest z, digit by digit from the top byte of the keys. Thread t owns bin
   // 255 - t, so that the scan in thread order counts the keys in this bin and every higher one; the bin
@@ -1764,20 +1827,74 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState st) {
     thr = key_z(prefix);
   }
 
+  // nucleus: the lowest z whose integer mass strictly above, A, has A 2^24 < P Sq. Thread t owns bin 255 - t
+  // as above: its inclusive scan is the mass in this bin and every higher one of the current prefix.
+  if (P24 < (1u << 24)) {
+    unsigned q[16];
+    unsigned long long qs = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      q[j] = z[j] >= thr ? (unsigned)(expf(z[j] - zmax) * 16777216.f) : 0u;  // floor: w >= 0
+      qs += q[j];
+    }
+    qs = wave_scan_u64(qs, lane);
+    if (lane == 63) wq[wave] = qs;
+    __syncthreads();
+    const unsigned long long lim = (unsigned long long)P24 * ((wq[0] + wq[1]) + (wq[2] + wq[3]));  // < 2^61
+    unsigned prefix = 0;
+    unsigned long long above = 0;  // mass of the keys above every key of the current prefix
+#pragma unroll
+    for (int pass = 0; pass < 4; ++pass) {
+      const int sh = 24 - 8 * pass;
+      __syncthreads();  // (wq, qpick of the pass before are read)
+      qh[tid] = 0ull;
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const unsigned key = z_key(z[j]);
+        if (q[j] && (pass == 0 || (key >> ((sh + 8) & 31)) == prefix))
+          atomicAdd(&qh[(key >> sh) & 255u], (unsigned long long)q[j]);
+      }
+      __syncthreads();
+      const unsigned long long c = qh[255 - tid];
+      unsigned long long sc = wave_scan_u64(c, lane);
+      if (lane == 63) wq[wave] = sc;
+      __syncthreads();
+      for (int w = 0; w < wave; ++w) sc += wq[w];
+      const unsigned long long a_here = above + (sc - c), a_next = above + sc;  // mass above this bin, above the next
+      if (((a_here << 24) < lim) && (tid == 255 || !((a_next << 24) < lim))) {  // exactly one thread
+        pick[0] = (unsigned)(255 - tid);
+        qpick = a_here;
+      }
+      __syncthreads();
+      prefix = (prefix << 8) | pick[0];
+      above = qpick;
+    }
+    thr = fmaxf(thr, key_z(prefix));  // (a key that carries mass: a finite z)
+  }
+
   // weights and the thread's inclusive running sums
-  float run[16], acc = 0.f;
-  int last = -1;
+  float run[16], acc = 0.f, low = INFINITY;
+  int last = -1, cnt = 0;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
-    const bool kept = z[j] >= thr;
+    const bool kept = z[j] >= thr && z[j] - zmax >= lnminp;
     acc += kept ? expf(z[j] - zmax) : 0.f;
     run[j] = acc;
-    if (kept) last = tid * 16 + j;
+    if (kept) { last = tid * 16 + j; low = fminf(low, z[j]); ++cnt; }
   }
   float excl, wtot;
   wave_scan_f32(acc, lane, excl, wtot);
-  if (lane == 0) wsum[wave] = wtot;
+  cnt = wave_sum_i32(cnt, lane);
+  low = -wave_max(-low);
+  if (lane == 0) { wsum[wave] = wtot; wkept[wave] = cnt; wlow[wave] = low; }
   __syncthreads();
+  // the kept record leaves here, from a wave that does not commit: one 16-byte store (lvx_sample_kept) whose
+  // completion the draw below covers; issued with the commit it was waited for at the end of the kernel
+  if (tid == 64)
+    st.smp_kept()[b] = make_uint4((unsigned)((wkept[0] + wkept[1]) + (wkept[2] + wkept[3])),
+                                  __float_as_uint(fminf(fminf(wlow[0], wlow[1]), fminf(wlow[2], wlow[3]))),
+                                  (unsigned)npen, 0u);
   float base = 0.f;
   for (int w = 0; w < wave; ++w) base += wsum[w];
   const float S = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
@@ -1799,6 +1916,9 @@ __global__ __launch_bounds__(256) void ar_sample_kernel(ArState st) {
     first = min(min(wfirst[0], wfirst[1]), min(wfirst[2], wfirst[3]));
     last = max(max(wlast[0], wlast[1]), max(wlast[2], wlast[3]));
     r.i = first != 0x7fffffff ? first : max(last, 0);
+    // the history entry first: its store is then in flight under the commit's dependent load of the row's plan
+    // step instead of behind it
+    hist_store(st, s, ri.y, r.i);
     argmax_commit(st, b, ri, r);
   }
 }
@@ -3767,28 +3887,63 @@ __global__ void codes_to_features_kernel(const float* __restrict__ cb, const int
   }
 }
 
-__global__ void set_slot_kernel(int32_t* pos, int32_t* prev, int slot, int p, int tok) {
-  pos[slot] = p;
-  prev[slot] = tok;
+// The slots' token history (ArState::hist / hist_from) is kept by these one-thread kernels, in stream order.
+// A set records prev as the token of position p - 1; a rewind (p <= the old position) keeps what is known
+// below it, a forward jump over positions never decoded leaves only that entry known.
+__global__ void set_slot_kernel(ArState st, int slot, int p, int tok) {
+  const int old = st.pos[slot], lo = max(p - 1, 0);
+  if (p > 0) st.hist[(size_t)slot * st.max_pos + (p - 1)] = (uint16_t)tok;
+  st.hist_from[slot] = p <= old ? min(st.hist_from[slot], lo) : lo;
+  st.pos[slot] = p;
+  st.prev[slot] = tok;
 }
 
-__global__ void set_sampling_kernel(float* temp, int32_t* topk, uint2* seed, int slot, float t, int k, uint2 sd) {
-  temp[slot] = t;
-  topk[slot] = k;
-  seed[slot] = sd;
+__global__ void reset_slot_kernel(ArState st, int slot) {
+  st.pos[slot] = 0;
+  st.hist_from[slot] = 0;
+}
+
+// fresh: the slot's temperature goes from 0 to > 0: plans that do not record may have decided its earlier tokens
+__global__ void set_sampling_kernel(ArState st, int slot, float t, int k, uint2 sd, uint4 ex, int fresh) {
+  st.smp[2 * slot] = make_uint4(__float_as_uint(t), (unsigned)k, sd.x, sd.y);
+  st.smp[2 * slot + 1] = ex;
+  if (fresh) st.hist_from[slot] = st.pos[slot];
+}
+
+// Test hook (lvx_stream_history): entries pos0 .. pos0 + n - 1 of a slot's history; a write lowers hist_from to pos0
+__global__ __launch_bounds__(256) void history_kernel(ArState st, int slot, int pos0, int n, int32_t* __restrict__ tokens,
+                                                      int write) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint16_t* h = st.hist + (size_t)slot * st.max_pos + pos0;
+  if (write) {
+    h[i] = (uint16_t)min(max(tokens[i], 0), VOCAB - 1);
+    if (i == 0) st.hist_from[slot] = min(st.hist_from[slot], pos0);
+  } else {
+    tokens[i] = (int32_t)h[i];
+  }
 }
 
 void ar_launch_rowinfo_init(const ArState& st, int B, hipStream_t s) {
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
 }
 
-void launch_set_slot(int32_t* pos, int32_t* prev, int slot, int p, int tok, hipStream_t s) {
-  hipLaunchKernelGGL(set_slot_kernel, dim3(1), dim3(1), 0, s, pos, prev, slot, p, tok);
+void launch_set_slot(const ArState& st, int slot, int p, int tok, hipStream_t s) {
+  hipLaunchKernelGGL(set_slot_kernel, dim3(1), dim3(1), 0, s, st, slot, p, tok);
 }
 
-void launch_set_sampling(const ArState& st, int slot, float temperature, int top_k, uint64_t seed, hipStream_t s) {
-  hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(1), 0, s, st.smp_temp, st.smp_topk, st.smp_seed, slot,
-                     temperature, top_k, make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
+void launch_reset_slot(const ArState& st, int slot, hipStream_t s) {
+  hipLaunchKernelGGL(reset_slot_kernel, dim3(1), dim3(1), 0, s, st, slot);
+}
+
+void launch_set_sampling(const ArState& st, int slot, float temperature, int top_k, uint64_t seed, uint4 ex, bool fresh,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(set_sampling_kernel, dim3(1), dim3(1), 0, s, st, slot, temperature, top_k,
+                     make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)), ex, fresh ? 1 : 0);
+}
+
+void launch_history(const ArState& st, int slot, int pos0, int n, int32_t* tokens, bool write, hipStream_t s) {
+  hipLaunchKernelGGL(history_kernel, dim3((n + 255) / 256), dim3(256), 0, s, st, slot, pos0, n, tokens, write ? 1 : 0);
 }
 
 // Take (read and clear, one atomic per word) the masked bits of the AR word words[0] and the codec

@@ -268,6 +268,10 @@ static long long stretch_emitted_upto(int pct, long long T, bool final) {
   return STR_H * stretch_hops(pct, T);
 }
 
+// the second record of ArState::smp for a slot that asks for none of the extended controls: top_p 1, min_p 0 (lnminp -inf),
+// repetition_penalty 1.0f, repetition_window 64
+static const uint4 kSamplingNeutral{1u << 24, 0xff800000u, 0x3f800000u, 64u};
+
 struct lvx_ctx {
   lvx_config cfg{};
   std::map<std::string, std::vector<float>> host;  // staged fp32 weights (released at finalize)
@@ -286,7 +290,7 @@ struct lvx_ctx {
   unsigned graph_epoch = 0;  // opt_epoch when the cached graphs were captured
   hipStream_t capture_stream = nullptr;  // lvx_set_capture_stream (not owned); null: capture on the caller's
   hipStream_t own_capture_stream = nullptr;  // created for null-stream callers only (cached_graph)
-  std::vector<float> smp_temp;  // host mirror of ArState::smp_temp (lvx_stream_sampling, under mu)
+  std::vector<float> smp_temp;  // host mirror of the slots' temperatures (lvx_stream_sampling, under mu)
   int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
   // PCM output stage: the device taps of the three resampling rates, the slots' history pool
   // [2][max_streams][PCM_HIST] and the host mirror of every slot's segment (lvx_pcm_convert, under mu)
@@ -687,10 +691,15 @@ int lvx_finalize(lvx_ctx* c) {
   st.max_pos = P;
   st.max_streams = S;
   st.kv_chunks = (P + KV_CHUNK - 1) / KV_CHUNK;
-  if ((r = c->dalloc(&st.smp_temp, S)) || (r = c->dalloc(&st.smp_topk, S)) || (r = c->dalloc(&st.smp_seed, S))) return r;
-  HIP_TRY(hipMemset(st.smp_temp, 0, S * 4));  // every slot greedy
-  HIP_TRY(hipMemset(st.smp_topk, 0, S * 4));
-  HIP_TRY(hipMemset(st.smp_seed, 0, S * 8));
+  {  // the slots' sampling state: every slot greedy with the neutral extended record
+    char* blk;
+    if ((r = c->dalloc(&blk, ArState::smp_bytes(S)))) return r;
+    st.smp = reinterpret_cast<uint4*>(blk);
+    HIP_TRY(hipMemset(blk, 0, ArState::smp_bytes(S)));
+    std::vector<uint4> rec((size_t)2 * S, uint4{0u, 0u, 0u, 0u});
+    for (int s = 0; s < S; ++s) rec[2 * s + 1] = kSamplingNeutral;
+    HIP_TRY(hipMemcpy(st.smp, rec.data(), rec.size() * sizeof(uint4), hipMemcpyHostToDevice));
+  }
   c->smp_temp.assign(S, 0.f);
   c->n_sampling = 0;
   if ((r = c->dalloc(&st.slots, S)) || (r = c->dalloc(&st.pos, S)) || (r = c->dalloc(&st.prev, S)) ||
@@ -765,6 +774,10 @@ int lvx_finalize(lvx_ctx* c) {
     c->str_pct.assign(S, 0);
     c->str_par.assign(S, 0);
   }
+  // ---- the slots' token history (S * P * 2 bytes; allocated last: every other buffer stays where it was) ----
+  if ((r = c->dalloc(&st.hist, (size_t)S * P)) || (r = c->dalloc(&st.hist_from, S))) return r;
+  HIP_TRY(hipMemset(st.hist, 0, (size_t)S * P * 2));
+  HIP_TRY(hipMemset(st.hist_from, 0, (size_t)S * 4));
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
   c->finalized = true;
@@ -799,7 +812,8 @@ int lvx_stream_reset(lvx_ctx* c, int slot, void* stream) {
   NEED_FINAL(c);
   if (slot < 0 || slot >= c->cfg.max_streams) return fail(LVX_E_ARG, "slot out of range");
   HIP_TRY(hipSetDevice(c->cfg.device));
-  HIP_TRY(hipMemsetAsync(c->st.pos + slot, 0, 4, (hipStream_t)stream));
+  launch_reset_slot(c->st, slot, (hipStream_t)stream);  // position 0, the history known from 0
+  HIP_TRY(hipGetLastError());
   return LVX_OK;
 }
 
@@ -809,24 +823,64 @@ int lvx_stream_set(lvx_ctx* c, int slot, int pos, int prev_token, void* stream) 
   if (pos < 0 || pos > c->cfg.max_positions) return fail(LVX_E_CAPACITY, "position out of range");
   if (prev_token < 0 || prev_token >= VOCAB) return fail(LVX_E_ARG, "prev_token out of range");
   HIP_TRY(hipSetDevice(c->cfg.device));
-  launch_set_slot(c->st.pos, c->st.prev, slot, pos, prev_token, (hipStream_t)stream);
+  launch_set_slot(c->st, slot, pos, prev_token, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+int lvx_stream_sampling_ex(lvx_ctx* c, int slot, const lvx_sampling* p, void* stream) {
+  NEED_FINAL(c);
+  if (slot < 0 || slot >= c->cfg.max_streams) return fail(LVX_E_ARG, "slot out of range");
+  if (!p) return fail(LVX_E_ARG, "null sampling parameters");
+  if (!std::isfinite(p->temperature) || p->temperature < 0.f) return fail(LVX_E_ARG, "temperature must be finite and >= 0");
+  if (p->top_k < 0) return fail(LVX_E_ARG, "top_k must be >= 0");
+  if (!(p->top_p > 0.f && p->top_p <= 1.f)) return fail(LVX_E_ARG, "top_p must be in (0, 1]");
+  if (!(p->min_p >= 0.f && p->min_p < 1.f)) return fail(LVX_E_ARG, "min_p must be in [0, 1)");
+  if (!std::isfinite(p->repetition_penalty) || !(p->repetition_penalty > 0.f))
+    return fail(LVX_E_ARG, "repetition_penalty must be finite and > 0");
+  if (p->repetition_window < 1 || p->repetition_window > 256) return fail(LVX_E_ARG, "repetition_window must be in [1, 256]");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const long long P = std::min(std::max(std::llround((double)p->top_p * 16777216.0), 1LL), 1LL << 24);
+  const float lnminp = (float)std::log((double)p->min_p);  // min_p 0: -inf, no crop
+  uint4 ex;
+  ex.x = (uint32_t)P;
+  std::memcpy(&ex.y, &lnminp, 4);
+  std::memcpy(&ex.z, &p->repetition_penalty, 4);
+  ex.w = (uint32_t)p->repetition_window;
+  bool fresh;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    fresh = p->temperature > 0.f && !(c->smp_temp[slot] > 0.f);
+    c->n_sampling += (p->temperature > 0.f) - (c->smp_temp[slot] > 0.f);
+    c->smp_temp[slot] = p->temperature;
+  }
+  launch_set_sampling(c->st, slot, p->temperature, p->top_k, p->seed, ex, fresh, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return LVX_OK;
 }
 
 int lvx_stream_sampling(lvx_ctx* c, int slot, float temperature, int top_k, uint64_t seed, void* stream) {
+  const lvx_sampling p{temperature, top_k, 1.f, 0.f, 1.f, 64, seed};
+  return lvx_stream_sampling_ex(c, slot, &p, stream);
+}
+
+int lvx_stream_history(lvx_ctx* c, int slot, int pos0, int n, int32_t* tokens, int write, void* stream) {
   NEED_FINAL(c);
   if (slot < 0 || slot >= c->cfg.max_streams) return fail(LVX_E_ARG, "slot out of range");
-  if (!std::isfinite(temperature) || temperature < 0.f) return fail(LVX_E_ARG, "temperature must be finite and >= 0");
-  if (top_k < 0) return fail(LVX_E_ARG, "top_k must be >= 0");
+  if (!tokens) return fail(LVX_E_ARG, "null tokens");
+  if (pos0 < 0 || n < 1 || (long long)pos0 + n > (long long)c->cfg.max_positions)
+    return fail(LVX_E_CAPACITY, "entries outside the slot's history");
   HIP_TRY(hipSetDevice(c->cfg.device));
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->n_sampling += (temperature > 0.f) - (c->smp_temp[slot] > 0.f);
-    c->smp_temp[slot] = temperature;
-  }
-  launch_set_sampling(c->st, slot, temperature, top_k, seed, (hipStream_t)stream);
+  launch_history(c->st, slot, pos0, n, tokens, write != 0, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+int lvx_sample_kept(lvx_ctx* c, int B, int32_t* dst, void* stream) {
+  NEED_FINAL(c);
+  if (B < 1 || B > c->cfg.max_streams || !dst) return fail(LVX_E_ARG, "bad B/dst");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  HIP_TRY(hipMemcpyAsync(dst, c->st.smp_kept(), (size_t)B * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return LVX_OK;
 }
 

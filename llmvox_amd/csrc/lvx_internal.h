@@ -110,10 +110,23 @@ struct ArState {
   uint32_t* selrow = nullptr;    // [B] batched deferred select: row b's logits not yet committed
   int32_t* pos = nullptr;       // [max_streams] per-slot next position
   int32_t* prev = nullptr;      // [max_streams] per-slot previous token
-  // per-slot sampling parameters (lvx_stream_sampling; read by ar_sample_kernel, so graphs replay unchanged)
-  float* smp_temp = nullptr;    // [max_streams] temperature; 0: the slot decodes greedily
-  int32_t* smp_topk = nullptr;  // [max_streams] top-k crop; 0 or >= VOCAB: none
-  uint2* smp_seed = nullptr;    // [max_streams] Philox key (seed low word, high word)
+  // Per-slot sampling state in the 24 bytes the three parameter pointers of the first sampler took: ArState
+  // travels by value in every kernel's arguments (inside GemvArgs too), and moving its other members or the
+  // members behind it costs the whole step (32 bytes more: +0.8 us per step at B = 1 and 8; 8 bytes fewer:
+  // +2.0 us at B = 1). Size and offsets of everything else are those of before.
+  //   smp[2 s], smp[2 s + 1]  the slot's parameters, read by ar_sample_kernel with two adjacent 16-byte loads, so
+  //                           graphs replay unchanged: {temperature bits (0: the slot decodes greedily), top-k (0
+  //                           or >= VOCAB: none), Philox key low word, high word}, {P = round(top_p 2^24) (2^24:
+  //                           no nucleus crop), bits of lnminp = (float)log(min_p) (-inf: no min-p crop), bits of
+  //                           repetition_penalty (1.0f: none), repetition_window}
+  //   smp_kept()[b]           per batch row of the last sampled select: {kept, bits of the lowest kept z, distinct
+  //                           penalised tokens, 0} (lvx_sample_kept)
+  uint4* smp = nullptr;         // [max_streams][2] + [max_streams]
+  __host__ __device__ uint4* smp_kept() const { return smp + 2 * (size_t)max_streams; }
+  static size_t smp_bytes(int streams) { return (size_t)streams * 3 * sizeof(uint4); }
+  // token history of the sampling plans (ar_sample_kernel's commit; the repetition penalty's window)
+  uint16_t* hist = nullptr;     // [max_streams][max_pos] token decided by the step at position p
+  int32_t* hist_from = nullptr; // [max_streams] first position whose entry is known
   int32_t* err = nullptr;       // [4] error words: [0] AR (1 KV capacity, 2 plan overrun, 4 text id / code out
                                 // of range in the drop-in gathers, 32 fused-MLP fixed-point range); [1] codec
                                 // (4 code out of range, 8 ISTFT envelope); [2] / [3] take slots of
@@ -162,8 +175,12 @@ int ar_attn_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype
                   int info[4], hipStream_t s);
 // ArWeights::q0_text / q0_code / q0_pos from the bf16 c_attn weight of layer 0 (lvx_finalize)
 void ar_launch_q0_tables(const ArWeights& w, int max_pos, float* text, float* code, float* pos, hipStream_t s);
-void launch_set_slot(int32_t* pos, int32_t* prev, int slot, int p, int tok, hipStream_t s);
-void launch_set_sampling(const ArState& st, int slot, float temperature, int top_k, uint64_t seed, hipStream_t s);
+void launch_set_slot(const ArState& st, int slot, int p, int tok, hipStream_t s);
+void launch_reset_slot(const ArState& st, int slot, hipStream_t s);
+// ex: the second record of ArState::smp; fresh: the slot starts sampling (its history begins at its current position)
+void launch_set_sampling(const ArState& st, int slot, float temperature, int top_k, uint64_t seed, uint4 ex, bool fresh,
+                         hipStream_t s);
+void launch_history(const ArState& st, int slot, int pos0, int n, int32_t* tokens, bool write, hipStream_t s);
 void launch_err_take(int32_t* words, int mask_ar, int mask_codec, int32_t* out, hipStream_t s);
 void launch_text_embed(const float* table, const int64_t* ids, int n, float* out, int32_t* err, hipStream_t s);
 void launch_codes_to_features(const float* codebook, const int64_t* codes, int B, int L, float* feats,

@@ -93,11 +93,34 @@ class Engine:
     def set_slot(self, slot: int, pos: int, prev_token: int = 0):
         _lib.check(self.lib.lvx_stream_set(self.h, slot, pos, prev_token, self.stream_handle()))
 
-    def set_sampling(self, slot: int, temperature: float = 0.0, top_k: int = 0, seed: int = 0):
-        """Seeded temperature / top-k sampling of the slot's decode steps (lvx_stream_sampling; temperature 0:
-        greedy). Stream-ordered on the current stream, like ``set_slot``."""
-        _lib.check(self.lib.lvx_stream_sampling(self.h, slot, float(temperature), int(top_k),
-                                                int(seed) & 0xFFFFFFFFFFFFFFFF, self.stream_handle()))
+    def set_sampling(self, slot: int, temperature: float = 0.0, top_k: int = 0, seed: int = 0, top_p: float = 1.0,
+                     min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64):
+        """Seeded sampling of the slot's decode steps (lvx_stream_sampling_ex; temperature 0: greedy): top-k,
+        nucleus and min-p crops and a repetition penalty over the slot's last ``repetition_window`` tokens.
+        Stream-ordered on the current stream, like ``set_slot``."""
+        p = _lib.LvxSampling(float(temperature), int(top_k), float(top_p), float(min_p), float(repetition_penalty),
+                             int(repetition_window), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        _lib.check(self.lib.lvx_stream_sampling_ex(self.h, slot, ctypes.byref(p), self.stream_handle()))
+
+    def stream_history(self, slot: int, pos0: int, n: int) -> torch.Tensor:
+        """Test hook: entries ``pos0 .. pos0 + n - 1`` of the slot's token history, a device int32 tensor [n]
+        (lvx_stream_history)."""
+        out = torch.empty(max(int(n), 0), device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.lvx_stream_history(self.h, int(slot), int(pos0), int(n), _ptr(out), 0, self.stream_handle()))
+        return out
+
+    def write_history(self, slot: int, pos0: int, tokens):
+        """Test hook: store ``tokens`` as the slot's history entries from ``pos0`` on (hist_from drops to pos0)."""
+        t = torch.as_tensor(tokens, dtype=torch.int32).to(self.device).contiguous()
+        _lib.check(self.lib.lvx_stream_history(self.h, int(slot), int(pos0), int(t.numel()), _ptr(t), 1,
+                                               self.stream_handle()))
+
+    def sample_kept(self, B: int) -> torch.Tensor:
+        """Test hook: per batch row of the last sampled select, int32 [B, 4] = (kept tokens, fp32 bits of the
+        lowest kept z, distinct penalised tokens, 0) (lvx_sample_kept)."""
+        out = torch.empty(int(B), 4, device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.lvx_sample_kept(self.h, int(B), _ptr(out), self.stream_handle()))
+        return out
 
     def slot_position(self, slot: int) -> int:
         v = ctypes.c_int()

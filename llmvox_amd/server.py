@@ -365,13 +365,18 @@ def speed_pct_of(speed) -> int:
 
 
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
-               encoding: str = "f32le", container: str = "raw", speed: float = 1.0):
+               encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
+               min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
     (>= 0, finite; 0: greedy), ``top_k`` (>= 0; 0: no crop) and ``seed`` (int >= 0; absent with a
     temperature > 0: drawn from os.urandom), the reference's GPT.generate controls; ``temperature`` /
-    ``top_k`` here are the defaults of requests that name none of the three. Invalid values: 422. A request
+    ``top_k`` here are the defaults of requests that name none of the three. Invalid values: 422. A sampled
+    request may further name ``top_p`` (in (0, 1]; 1: no nucleus crop), ``min_p`` (in [0, 1); 0: none),
+    ``repetition_penalty`` (> 0; 1: none) and ``repetition_window`` (1 .. 256 recent tokens of the sentence), the
+    controls of ``sampling.Sampling`` (include/llmvox.h, lvx_stream_sampling_ex); a field it leaves out takes the
+    default given here; out of range: 422. A request
     may also name its audio format: ``sample_rate`` (24000, 16000, 8000, 48000), ``encoding`` ("f32le",
     "s16le") and ``container`` ("raw", "wav": a 44-byte header of a stream of unknown length first); a
     field it leaves out takes the default given here; invalid values: 422. The response says what it
@@ -387,7 +392,9 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
 
     from .audio import AudioFormat
     from .sampling import Sampling
-    Sampling(temperature, top_k)  # (the defaults are validated at start-up)
+    Sampling(temperature, top_k, 0, top_p, min_p, repetition_penalty, repetition_window)  # (validated at start-up)
+    extra_defaults = {"top_p": top_p, "min_p": min_p, "repetition_penalty": repetition_penalty,
+                      "repetition_window": repetition_window}
     default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed))
 
     class TTSRequest(BaseModel):
@@ -395,6 +402,10 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         temperature: Optional[float] = None
         top_k: Optional[int] = None
         seed: Optional[int] = None
+        top_p: Optional[float] = None
+        min_p: Optional[float] = None
+        repetition_penalty: Optional[float] = None
+        repetition_window: Optional[int] = None
         sample_rate: Optional[int] = None
         encoding: Optional[str] = None
         container: Optional[str] = None
@@ -415,14 +426,16 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         named = not (request.temperature is None and request.top_k is None and request.seed is None)
         t = request.temperature if named and request.temperature is not None else temperature
         k = request.top_k if named and request.top_k is not None else top_k
+        extra = {name: default if getattr(request, name) is None else getattr(request, name)
+                 for name, default in extra_defaults.items()}
         try:
-            sp = Sampling(t, k, request.seed if request.seed is not None else 0)
+            sp = Sampling(t, k, request.seed if request.seed is not None else 0, **extra)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
         if not sp.temperature > 0:
             return None
         if request.seed is None:
-            sp = Sampling(sp.temperature, sp.top_k, int.from_bytes(os.urandom(8), "little"))
+            sp = Sampling(sp.temperature, sp.top_k, int.from_bytes(os.urandom(8), "little"), **extra)
         return sp
 
     app = FastAPI(title="llmvox_amd streaming TTS")
@@ -458,8 +471,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     return app
 
 
-def main(argv=None):
-    """python -m llmvox_amd.server [--port 8000] [--dtype bf16] [--ckpt ... --wavtokenizer ...]"""
+def arg_parser():
+    """The command line of ``main``."""
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--host", default="127.0.0.1")
@@ -482,13 +495,30 @@ def main(argv=None):
     ap.add_argument("--temperature", type=float, default=0.0,
                     help="sampling temperature of requests that name no sampling field (0: greedy)")
     ap.add_argument("--top-k", type=int, default=0, help="their top-k crop (0: none)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="their nucleus mass, in (0, 1] (1: no crop)")
+    ap.add_argument("--min-p", type=float, default=0.0, help="their min-p crop, in [0, 1) (0: none)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0,
+                    help="their penalty on the recent tokens of the sentence, > 0 (1: none)")
+    ap.add_argument("--repetition-window", type=int, default=64, help="how many recent tokens it covers (1 .. 256)")
     ap.add_argument("--sample-rate", type=int, default=24000, choices=[24000, 16000, 8000, 48000],
                     help="output sample rate of requests that name none")
     ap.add_argument("--encoding", default="f32le", choices=["f32le", "s16le"], help="their sample encoding")
     ap.add_argument("--container", default="raw", choices=["raw", "wav"], help="their container (wav: a header first)")
     ap.add_argument("--speed", type=float, default=1.0,
                     help="speaking rate of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def app_options(a) -> dict:
+    """``create_app``'s keywords from the parsed command line: the defaults of the requests' optional fields."""
+    return dict(temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate, encoding=a.encoding,
+                container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
+                repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window)
+
+
+def main(argv=None):
+    """python -m llmvox_amd.server [--port 8000] [--dtype bf16] [--ckpt ... --wavtokenizer ...]"""
+    a = arg_parser().parse_args(argv)
     from .engine import build_engine
     from . import weights as W
     gw, cw, tt = W.synthetic_all(a.seed)
@@ -512,8 +542,7 @@ def main(argv=None):
                           "llm_max_tokens": a.llm_max_tokens}).load()
     svc = TTSService(engines, stream_model=sm)
     import uvicorn
-    uvicorn.run(create_app(svc, temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate,
-                           encoding=a.encoding, container=a.container, speed=a.speed), host=a.host, port=a.port)
+    uvicorn.run(create_app(svc, **app_options(a)), host=a.host, port=a.port)
 
 
 if __name__ == "__main__":

@@ -686,7 +686,8 @@ class FusedScheduler:
         if st.sampling is not None:
             from .sampling import segment_seed
             sp = st.sampling
-            self.engine.set_sampling(st.slot, sp.temperature, sp.top_k, segment_seed(sp.seed, st.index, st.segment))
+            self.engine.set_sampling(st.slot, sp.temperature, sp.top_k, segment_seed(sp.seed, st.index, st.segment),
+                                     **sp.extra())
 
     def close_stream(self, st: FusedStream):
         self.streams.remove(st)

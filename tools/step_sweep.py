@@ -6,7 +6,9 @@ default (null) stream it launches every kernel). LVX_SWEEP_KV=fp8: fp8 KV cache 
 LVX_SWEEP_W=fp32: the fp32 parity mode (fp32 weights and KV).
 LVX_SWEEP_SAMPLE=T,k: every option set is measured twice in the same process, greedy as given and
 then with seeded sampling (temperature T, top-k k) enabled on all B slots (the step then runs the
-defer_select 0 plan with ar_sample_kernel after lm_head: compare with the set 'defer_select=0')."""
+defer_select 0 plan with ar_sample_kernel after lm_head: compare with the set 'defer_select=0').
+T,k,top_p[,R[,W]] adds a nucleus and a repetition penalty R over the last W tokens (1 and 64 when left
+out); several sets separated by ';' are measured one after the other."""
 import os, statistics, sys, time
 import torch
 from llmvox_amd.engine import build_engine
@@ -22,15 +24,20 @@ side = torch.cuda.Stream(device=dev) if os.environ.get("LVX_SWEEP_STREAM") == "1
 if side is not None:
     torch.cuda.set_stream(side)
 SAMPLE = os.environ.get("LVX_SWEEP_SAMPLE")
-runs = [(spec, smp) for spec in (sys.argv[3:] or [""]) for smp in ([None, SAMPLE] if SAMPLE else [None])]
+runs = [(spec, smp) for spec in (sys.argv[3:] or [""]) for smp in ([None] + SAMPLE.split(";") if SAMPLE else [None])]
 for spec, smp in runs:
     opts = [kv.split("=") for kv in spec.split(",") if kv]
     for k, v in opts:
         e.set_option(k, int(v))
     if smp:
-        T, topk = smp.split(",")
+        f = smp.split(",")
+        T, topk = f[0], f[1]
+        extra = {}
+        if len(f) > 2:  # only then does the call name the extended parameters
+            extra = {"top_p": float(f[2]), "repetition_penalty": float(f[3]) if len(f) > 3 else 1.0,
+                     "repetition_window": int(f[4]) if len(f) > 4 else 64}
         for s in range(B):
-            e.set_sampling(s, float(T), int(topk), 1000 + s)
+            e.set_sampling(s, float(T), int(topk), 1000 + s, **extra)
     ts = []
     for rep in range(3):
         for s in range(B):
