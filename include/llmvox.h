@@ -466,6 +466,71 @@ int lvx_pcm_stretch(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const i
                     const uint8_t* final_host, int speed_pct, float* out_dev, long long out_stride_bytes,
                     int32_t* n_out_host, int32_t* d_out_dev, int d_stride, void* stream);
 
+/* ---- PCM pitch shift ----------------------------------------------------------
+ * The pitch control. LLMVoX has one voice and no conditioning input, so pitch, like speed, is made on the
+ * PCM: a pitch shift is a time stretch by one factor followed by a resampling by the inverse factor. The
+ * stretch is lvx_pcm_stretch above, unchanged; what this section adds is the resampler for an arbitrary
+ * ratio, lvx_pcm_ratio, and the integer plan that ties the two to a stream's speed and pitch. A stream
+ * that names no pitch (or 100) never comes here. The order of the stages is stretch, ratio, then
+ * lvx_pcm_convert for the rate and the encoding; each keeps its own bit-exact rule.
+ *
+ * Plan (lvx_pcm_pitch_plan; all integers). speed_pct and pitch_pct each in [50, 200], 100 neutral.
+ *   stretch_pct = (200 speed_pct + pitch_pct) div (2 pitch_pct)     (speed 100 / pitch, rounded half up)
+ * The combination is valid iff 50 <= stretch_pct <= 200 (else LVX_E_ARG).
+ *   g = gcd(stretch_pct, speed_pct),  L = stretch_pct / g,  M = speed_pct / g.
+ * The stream is stretched at stretch_pct (100: nothing is launched), the stretched signal resampled by
+ * L / M (output count over input count), still nominally at 24 kHz (L == M, which every pitch_pct 100
+ * gives: nothing is launched). The duration is that of speed_pct; the pitch is multiplied by the realised
+ * ratio M / L = speed_pct / stretch_pct, which approximates pitch_pct / 100 to within the rounding of
+ * stretch_pct. A sentence of T samples delivers n1 = ceil(T 100 / stretch_pct), then n2 = ceil(n1 L / M)
+ * samples, then the rate conversion's count of n2.
+ *
+ * Ratio resampler: the rule of the "PCM output stage" with a general (L, M), L and M coprime.
+ *   lo = min(1, L / M);  fc = 0.5 lo 0.85 / L;  N = round(24 L / lo) = 24 max(L, M) <= 4800;
+ *   h[n] = L 2 fc sinc(2 fc n) kaiser(2 N + 1, beta = 9.0)[n + N],  n = -N .. N,
+ * built on the host in double, stored as fp32, by the very function that designs the three fixed rates:
+ * (L, M) = (2, 3), (1, 3), (2, 1) give N = 72, 72, 48 and the taps of 16000 / 8000 / 48000 Hz bit for bit.
+ *   y[m] = sum over the i with |m M - i L| <= N of x[i] h[m M - i L],   m = 0 .. ceil(T L / M) - 1,
+ * in fp32 in the same ONE fixed order: acc = 0, then for i ascending (x[i] = 0 outside [0, T))
+ * acc = fl(acc + fl(x[i] h[m M - i L])), no fused multiply-add. Every output is an independent dot
+ * product: THE CONCATENATED OUTPUTS OF ANY CHUNKING OF A SEGMENT ARE BIT-IDENTICAL TO ITS ONE-SHOT OUTPUT,
+ * and llmvox_amd/audio.py: ratio_ref gives the same bits on the host. An output takes at most
+ * floor(2 N / L) + 1 taps.
+ * Over the 9,155 reduced (L, M) != (1, 1) the plan can produce (float64 response of the fp32 taps): the
+ * passband is within 0.1 dB up to 0.765 lo, the stopband <= -91 dB from lo on (lo in units of the input's
+ * Nyquist frequency), the DC gain of every phase is 1 within 5e-5, and an output reaches back <= 96 inputs.
+ *
+ * Streaming counts: the same formula. After a non-final call that brings the input count to T the emitted
+ * outputs are the m < E(T) = min(floor(((T - 1) L - N) / M) + 1, ceil(T L / M)), 0 if (T - 1) L < N; a
+ * final call emits the rest. lvx_pcm_ratio accepts any coprime 1 <= L, M <= 200 with M <= 4 L and
+ * L <= 4 M (wider than the plan produces; (1, 1) is the identity: N = 0, the tap 1, nothing launched).
+ * With M <= 4 L an output reaches back at most ceil(2 N / L) <= 192 inputs: the library keeps, per KV slot,
+ * the last 256 inputs of the previous call (two buffers per slot) and, on the host, the slot's input count
+ * and ratio. The taps are designed once per (L, M) and cached on the host; on the device every slot has a
+ * table region of its own, written by a stream-ordered copy on the call's stream when the slot's call
+ * finds another ratio in it: a slot's calls are issued in order on one stream, so no launch reads a table
+ * that a later segment overwrites. A segment has one ratio: another before its final call is LVX_E_ARG. */
+/* host only: the plan of a (speed_pct, pitch_pct). LVX_E_ARG: either outside [50, 200], or a combination
+ * whose stretch_pct falls outside [50, 200]. Any of the three outputs may be NULL. */
+int lvx_pcm_pitch_plan(int speed_pct, int pitch_pct, int* stretch_pct, int* L, int* M);
+/* host only: N and the 2 N + 1 fp32 taps h[-N .. N] of a ratio ((1, 1): 0 and the tap 1). taps_host may be
+ * NULL (only N). LVX_E_ARG: L, M not coprime, outside 1 .. 200, M > 4 L or L > 4 M, or cap < 2 N + 1. */
+int lvx_pcm_ratio_filter(int L, int M, int* N, float* taps_host, int cap);
+/* host only: samples a call emits for a slot that has consumed t0 inputs of its segment (negative:
+ * LVX_E_ARG for a bad ratio, t0 < 0 or n_in < 0) */
+int lvx_pcm_ratio_emitted(int L, int M, long long t0, int n_in, int final);
+/* lvx_pcm_stretch's conventions: rows b of pcm_dev [B][n_in] f32 continue the ratio segments of
+ * slots_host[b]; final_host[b] != 0 emits the rest and resets the slot; n_in may be 0 with final (flush
+ * only). out row b (f32) starts at out_dev + b * out_stride_bytes; n_out_host[b] = samples written.
+ * L == M == 1: nothing is launched and nothing written, the rows of pcm_dev are the output (n_out_host[b]
+ * = n_in; out_dev may be NULL). LVX_E_ARG (and no slot's state changed): a bad ratio or another than the
+ * slot's open segment has, B < 1, n_in < 0, a slot out of range or named twice, out_dev or
+ * out_stride_bytes not a multiple of 4, out_stride_bytes smaller than a row's output. lvx_pcm_reset also
+ * forgets a slot's ratio state. */
+int lvx_pcm_ratio(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
+                  const uint8_t* final_host, int L, int M, float* out_dev, long long out_stride_bytes,
+                  int32_t* n_out_host, void* stream);
+
 /* ---- WavTokenizer encoder, a context of its own (its weights are not needed for TTS).
  * Replaces WavTokenizer.encode_infer (WavTokenizer/decoder/pretrained.py:185-190 ->
  * decoder/feature_extractors.py:122-133): SEANet encoder (encoder/modules/seanet.py:94-143) + the

@@ -3,11 +3,14 @@
 fp32 summation order and the s16le quantisation). The device stage is ``Engine.pcm_convert``; everything
 here runs on the host and is what the tests and the documentation compare it with. The speaking-rate
 control ("PCM time stretch" in the same header: WSOLA on the 24 kHz rows, before the resampler) is stated
-here too: ``stretch_ref``."""
+here too: ``stretch_ref``. So is the pitch control ("PCM pitch shift": the integer plan that turns a speed and a
+pitch into a stretch and a resampling ratio L / M, and the resampler of that ratio, between the stretch and the
+rate conversion): ``pitch_plan``, ``ratio_ref``."""
 from __future__ import annotations
 
 import struct
 from dataclasses import dataclass
+from math import gcd
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -22,6 +25,26 @@ STRETCH_H = 240         # output hop of the time stretch (10 ms)
 STRETCH_D = 240         # its search radius
 STRETCH_C = 480         # its correlation length
 STRETCH_HISTORY = 1280  # inputs of history a slot keeps between stretch calls
+PITCH_MIN, PITCH_MAX = 50, 200  # pitch_pct of a stream (100: no shift)
+RATIO_MAX = 200         # L and M of a ratio the resampler takes: 1 .. 200, coprime, M <= 4 L and L <= 4 M
+RATIO_HISTORY = 256     # inputs of history a slot keeps between ratio calls
+
+
+def pitch_plan(speed_pct: int, pitch_pct: int) -> Tuple[int, int, int]:
+    """(stretch_pct, L, M) of a stream's speed and pitch, all integers (``lvx_pcm_pitch_plan``): the PCM is
+    time-stretched at stretch_pct = speed 100 / pitch rounded half up, then resampled by L / M =
+    stretch_pct / speed_pct in lowest terms (output count over input count). The duration is that of speed_pct,
+    the pitch is multiplied by M / L. ValueError: either outside [50, 200], or a stretch_pct outside."""
+    for name, v in (("speed_pct", speed_pct), ("pitch_pct", pitch_pct)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 50 <= v <= 200:
+            raise ValueError(f"{name} must be an integer in [50, 200], got {v!r}")
+    speed_pct, pitch_pct = int(speed_pct), int(pitch_pct)
+    stretch = (200 * speed_pct + pitch_pct) // (2 * pitch_pct)
+    if not SPEED_MIN <= stretch <= SPEED_MAX:
+        raise ValueError(f"speed_pct {speed_pct} with pitch_pct {pitch_pct} needs a time stretch of {stretch} percent, "
+                         f"outside [{SPEED_MIN}, {SPEED_MAX}]")
+    g = gcd(stretch, speed_pct)
+    return stretch, stretch // g, speed_pct // g
 
 
 @dataclass(frozen=True)
@@ -31,6 +54,7 @@ class AudioFormat:
     encoding: str = "f32le"
     container: str = "raw"
     speed_pct: int = 100  # speaking rate in percent (pitch-preserving time stretch of the PCM; 100: none)
+    pitch_pct: int = 100  # pitch in percent (a stretch and a resampling of the PCM, ``pitch_plan``; 100: none)
 
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
@@ -42,17 +66,32 @@ class AudioFormat:
         if isinstance(self.speed_pct, bool) or not isinstance(self.speed_pct, int) \
                 or not SPEED_MIN <= self.speed_pct <= SPEED_MAX:
             raise ValueError(f"speed_pct must be an integer in [{SPEED_MIN}, {SPEED_MAX}], got {self.speed_pct!r}")
+        if isinstance(self.pitch_pct, bool) or not isinstance(self.pitch_pct, int) \
+                or not PITCH_MIN <= self.pitch_pct <= PITCH_MAX:
+            raise ValueError(f"pitch_pct must be an integer in [{PITCH_MIN}, {PITCH_MAX}], got {self.pitch_pct!r}")
+        pitch_plan(self.speed_pct, self.pitch_pct)  # (the two together: the stretch they need must exist)
 
     @property
     def is_default(self) -> bool:
         return (self.sample_rate == BASE_RATE and self.encoding == "f32le" and self.container == "raw"
-                and self.speed_pct == 100)
+                and self.speed_pct == 100 and self.pitch_pct == 100)
 
     @property
     def converts(self) -> bool:
-        """The samples differ from the codec's (another rate, encoding or speed): the stream needs the device
-        stage."""
-        return self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
+        """The samples differ from the codec's (another rate, encoding, speed or pitch): the stream needs the
+        device stage."""
+        return (self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
+                or self.pitch_pct != 100)
+
+    @property
+    def stretch_pct(self) -> int:
+        """What the time stretch runs at (``pitch_plan``): speed_pct itself without a pitch."""
+        return pitch_plan(self.speed_pct, self.pitch_pct)[0]
+
+    @property
+    def ratio(self) -> Tuple[int, int]:
+        """(L, M) of the resampling behind the stretch (``pitch_plan``): (1, 1) without a pitch."""
+        return pitch_plan(self.speed_pct, self.pitch_pct)[1:]
 
     @property
     def sample_bytes(self) -> int:
@@ -84,23 +123,54 @@ def design(sample_rate: int) -> Tuple[int, int, int, np.ndarray]:
     if sample_rate not in RATES:
         raise ValueError(f"unsupported sample rate {sample_rate}")
     L, M, _ = RATES[sample_rate]
-    if sample_rate == BASE_RATE:
-        return 1, 1, 0, np.ones(1)
+    N, h = ratio_design(L, M)
+    return L, M, N, h
+
+
+def _check_ratio(L: int, M: int):
+    if not (1 <= L <= RATIO_MAX and 1 <= M <= RATIO_MAX and M <= 4 * L and L <= 4 * M and gcd(L, M) == 1):
+        raise ValueError(f"L / M must be coprime, each in 1 .. {RATIO_MAX}, with M <= 4 L and L <= 4 M, got {L} / {M}")
+
+
+def ratio_design(L: int, M: int) -> Tuple[int, np.ndarray]:
+    """(N, taps float64 [2 N + 1]) of the ratio L / M, the one design of the fixed rates and of the pitch
+    control's ratios (the library stores it as fp32: ``lvx_pcm_ratio_filter``). 1 / 1 is the identity: N = 0
+    and the tap 1."""
+    _check_ratio(L, M)
+    if L == M:
+        return 0, np.ones(1)
     lo = min(1.0, L / M)
     fc = 0.5 * lo * 0.85 / L
-    N = int(round(24 * L / lo))
+    N = int(round(24 * L / lo))  # 24 max(L, M)
     n = np.arange(-N, N + 1)
-    return L, M, N, L * 2 * fc * np.sinc(2 * fc * n) * np.kaiser(2 * N + 1, 9.0)
+    return N, L * 2 * fc * np.sinc(2 * fc * n) * np.kaiser(2 * N + 1, 9.0)
 
 
-def emitted_upto(sample_rate: int, T: int, final: bool) -> int:
-    """Outputs of a segment emitted once T inputs are consumed (after a non-final / a final call)."""
-    L, M, N = RATES[sample_rate]
+def _ratio_N(L: int, M: int) -> int:
+    return 0 if L == M else 24 * max(L, M)
+
+
+def ratio_emitted_upto(L: int, M: int, T: int, final: bool) -> int:
+    """Outputs of a segment resampled by L / M emitted once T inputs are consumed (after a non-final / a
+    final call)."""
+    N = _ratio_N(L, M)
     full = -((-T * L) // M)
     if final or N == 0:
         return full
     a = (T - 1) * L - N
     return 0 if a < 0 else min(a // M + 1, full)
+
+
+def ratio_emitted(L: int, M: int, t0: int, n_in: int, final: bool) -> int:
+    """Samples a ratio call emits for a slot that has consumed t0 inputs of its segment
+    (``lvx_pcm_ratio_emitted``)."""
+    return ratio_emitted_upto(L, M, t0 + n_in, final) - ratio_emitted_upto(L, M, t0, False)
+
+
+def emitted_upto(sample_rate: int, T: int, final: bool) -> int:
+    """Outputs of a segment emitted once T inputs are consumed (after a non-final / a final call)."""
+    L, M, _ = RATES[sample_rate]
+    return ratio_emitted_upto(L, M, T, final)
 
 
 def emitted(sample_rate: int, t0: int, n_in: int, final: bool) -> int:
@@ -113,11 +183,20 @@ def resample_ref(x, sample_rate: int, taps=None, m0: int = 0, m1: Optional[int] 
     dtype float32: the rule's fixed order (inputs ascending, a rounded product and a rounded sum per tap, no
     fused multiply-add), bit for bit what the device computes with the same fp32 taps. dtype float64: the
     same sums in double (with the fp32 taps' values): the yardstick of the device's accumulation error."""
-    L, M, N = RATES[sample_rate]
+    L, M, _ = RATES[sample_rate]
+    return ratio_ref(x, L, M, taps, m0, m1, dtype)
+
+
+def ratio_ref(x, L: int, M: int, taps=None, m0: int = 0, m1: Optional[int] = None, dtype=np.float32) -> np.ndarray:
+    """``resample_ref`` for any ratio L / M the resampler takes (output count over input count): outputs
+    m0 .. m1 - 1 (default: all ceil(T L / M)) of the segment x[0 .. T), in the rule's fixed fp32 order (the
+    device's bits, ``lvx_pcm_ratio``, with the same fp32 taps) or, dtype float64, the same sums in double."""
+    _check_ratio(L, M)
+    N = _ratio_N(L, M)
     x = np.asarray(x, dtype=np.float32)
     T = x.shape[-1]
     if taps is None:
-        taps = design(sample_rate)[3].astype(np.float32)
+        taps = ratio_design(L, M)[1].astype(np.float32)
     h = np.asarray(taps, dtype=np.float32).astype(dtype)
     if m1 is None:
         m1 = -((-T * L) // M)
@@ -260,23 +339,28 @@ def stretch_ref(x, speed_pct: int, windows=None, force_d0: bool = False) -> Tupl
     return y[:total], ds
 
 
-def convert_ref(x, fmt: AudioFormat, taps=None, windows=None) -> np.ndarray:
-    """A whole segment x (float32 at 24 kHz) at the format's speed, rate and encoding (int16 or float32
-    array): stretched, then resampled, then encoded."""
-    if fmt.speed_pct != 100:
-        x = stretch_ref(x, fmt.speed_pct, windows)[0]
+def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None) -> np.ndarray:
+    """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, rate and encoding (int16 or
+    float32 array): stretched at the plan's stretch_pct, resampled by its L / M, then resampled to the rate and
+    encoded. ``ratio_taps``: the fp32 table of the format's ratio (default: designed here)."""
+    stretch, (L, M) = fmt.stretch_pct, fmt.ratio
+    if stretch != 100:
+        x = stretch_ref(x, stretch, windows)[0]
+    if L != M:
+        x = ratio_ref(x, L, M, ratio_taps)
     return encode_ref(resample_ref(x, fmt.sample_rate, taps), fmt)
 
 
 class StreamRef:
     """The streaming form of the rule for one slot, on the host: ``push(x, final)`` returns the samples the
-    call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_stretch`` when the format has a speed, then
-    ``lvx_pcm_convert``). Keeps the whole segment; for tests and stand-in engines. ``last_d``: the d_j of the
-    hops the last push emitted."""
+    call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_stretch`` when the plan has a stretch, then
+    ``lvx_pcm_ratio`` when it has a ratio, then ``lvx_pcm_convert``). Keeps the whole segment; for tests and
+    stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
 
-    def __init__(self, fmt: AudioFormat, taps=None, windows=None):
-        self.fmt, self.taps = fmt, taps
-        if fmt.speed_pct != 100:
+    def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None):
+        self.fmt, self.taps, self.ratio_taps = fmt, taps, ratio_taps
+        self.stretch_pct, (self.L, self.M) = fmt.stretch_pct, fmt.ratio
+        if self.stretch_pct != 100:
             wr, wf = windows if windows is not None else stretch_window()
             self.windows = (np.asarray(wr, dtype=np.float32), np.asarray(wf, dtype=np.float32))
         self.last_d = np.zeros(0, dtype=np.int32)
@@ -287,9 +371,18 @@ class StreamRef:
         self.t0 = 0
         self.raw: List[np.ndarray] = []  # the stretch's view: the segment's input, its count, hops and p_{j-1}
         self.raw_t0, self.hops, self.p_prev = 0, 0, -STRETCH_H
+        self.mid: List[np.ndarray] = []  # the ratio resampler's view: the stretched segment and its count
+        self.mid_t0 = 0
+
+    def _ratio(self, x, final: bool) -> np.ndarray:
+        m0 = ratio_emitted_upto(self.L, self.M, self.mid_t0, False)
+        m1 = ratio_emitted_upto(self.L, self.M, self.mid_t0 + x.size, final)
+        self.mid.append(x)
+        self.mid_t0 += x.size
+        return ratio_ref(np.concatenate(self.mid), self.L, self.M, self.ratio_taps, m0, m1)
 
     def _stretch(self, x, final: bool) -> np.ndarray:
-        pct = self.fmt.speed_pct
+        pct = self.stretch_pct
         self.raw.append(x)
         self.raw_t0 += x.size
         m0 = self.hops * STRETCH_H
@@ -303,8 +396,10 @@ class StreamRef:
 
     def push(self, x, final: bool) -> np.ndarray:
         x = np.asarray(x, dtype=np.float32).reshape(-1)
-        if self.fmt.speed_pct != 100:
+        if self.stretch_pct != 100:
             x = self._stretch(x, final)
+        if self.L != self.M:
+            x = self._ratio(x, final)
         rate = self.fmt.sample_rate
         m0 = emitted_upto(rate, self.t0, False)
         m1 = emitted_upto(rate, self.t0 + x.size, final)
@@ -320,4 +415,5 @@ class StreamRef:
 __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "resample_ref", "quantize_s16",
            "convert_ref", "StreamRef", "RATES", "ENCODINGS", "CONTAINERS", "BASE_RATE", "HISTORY",
            "stretch_window", "stretch_ref", "stretch_emitted", "stretch_emitted_upto", "SPEED_MIN", "SPEED_MAX",
-           "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY"]
+           "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY", "pitch_plan", "ratio_design", "ratio_emitted",
+           "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY"]

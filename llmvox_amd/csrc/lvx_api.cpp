@@ -212,26 +212,49 @@ static double bessel_i0(double x) {  // the power series: sum ((x / 2)^k / k!)^2
   return sum;
 }
 
-// h[n] = L 2 fc sinc(2 fc n) kaiser(2 N + 1, 9.0)[n + N], n = -N .. N, designed in double, stored as fp32
-static std::vector<float> pcm_design(const PcmRate& pr) {
-  if (pr.N == 0) return {1.f};
-  const double lo = std::min(1.0, (double)pr.L / pr.M), fc = 0.5 * lo * 0.85 / pr.L, beta = 9.0, pi = 3.14159265358979323846;
-  std::vector<float> h(2 * pr.N + 1);
-  for (int n = -pr.N; n <= pr.N; ++n) {
+// h[n] = L 2 fc sinc(2 fc n) kaiser(2 N + 1, 9.0)[n + N], n = -N .. N, designed in double, stored as fp32:
+// the three fixed rates and every ratio of the pitch control (llmvox.h, "PCM pitch shift")
+static std::vector<float> pcm_design(int L, int M, int N) {
+  if (N == 0) return {1.f};
+  const double lo = std::min(1.0, (double)L / M), fc = 0.5 * lo * 0.85 / L, beta = 9.0, pi = 3.14159265358979323846;
+  std::vector<float> h(2 * N + 1);
+  for (int n = -N; n <= N; ++n) {
     const double a = 2.0 * fc * n, sinc = n == 0 ? 1.0 : std::sin(pi * a) / (pi * a);
-    const double u = (double)n / pr.N;
+    const double u = (double)n / N;
     const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / bessel_i0(beta);
-    h[n + pr.N] = (float)(pr.L * 2.0 * fc * sinc * w);
+    h[n + N] = (float)(L * 2.0 * fc * sinc * w);
   }
   return h;
 }
+static std::vector<float> pcm_design(const PcmRate& pr) { return pcm_design(pr.L, pr.M, pr.N); }
 
 // outputs of a segment emitted once T inputs are consumed
+static long long pcm_emitted_upto(int L, int M, int N, long long T, bool final) {
+  const long long all = (T * L + M - 1) / M;  // ceil(T L / M)
+  if (final || N == 0) return all;
+  const long long a = (T - 1) * L - N;
+  return a < 0 ? 0 : std::min(a / M + 1, all);
+}
 static long long pcm_emitted_upto(const PcmRate& pr, long long T, bool final) {
-  const long long all = (T * pr.L + pr.M - 1) / pr.M;  // ceil(T L / M)
-  if (final || pr.N == 0) return all;
-  const long long a = (T - 1) * pr.L - pr.N;
-  return a < 0 ? 0 : std::min(a / pr.M + 1, all);
+  return pcm_emitted_upto(pr.L, pr.M, pr.N, T, final);
+}
+
+// ---- PCM pitch shift: the plan and the ratios the resampler takes (llmvox.h) ----
+static int gcd_of(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+// coprime 1 <= L, M <= 200 with M <= 4 L and L <= 4 M
+static bool ratio_ok(int L, int M) {
+  return L >= 1 && M >= 1 && L <= RAT_MAX && M <= RAT_MAX && M <= 4 * L && L <= 4 * M && gcd_of(L, M) == 1;
+}
+static int ratio_N(int L, int M) { return L == M ? 0 : 24 * std::max(L, M); }  // (coprime: L == M is 1 / 1, the identity)
+static std::string ratio_msg(int L, int M) {
+  return "L / M must be coprime, each in 1 .. 200, with M <= 4 L and L <= 4 M, got " + std::to_string(L) + " / " + std::to_string(M);
 }
 
 // ---- PCM time stretch: the window tables and the streaming counts (llmvox.h) ----
@@ -309,6 +332,17 @@ struct lvx_ctx {
   std::vector<long long> str_hops;  // hops of it emitted so far
   std::vector<int> str_pct;       // speed of the slot's open segment, 0: none open
   std::vector<uint8_t> str_par;   // which of the slot's two history buffers is current
+  // PCM pitch shift: every slot's device table region [max_streams][RAT_TAPS_STRIDE] and the ratio it holds,
+  // the slots' history pool [2][max_streams][RAT_HIST], the host cache of the designed tables (never
+  // evicted: a stream-ordered copy may still read an entry) and the host mirror of every slot's segment
+  // (lvx_pcm_ratio, under mu)
+  float* rat_taps = nullptr;
+  float* rat_hist = nullptr;
+  std::map<std::pair<int, int>, std::vector<float>> rat_cache;
+  std::vector<std::pair<int, int>> rat_tab;  // (L, M) of the table in the slot's region, (0, 0): none
+  std::vector<long long> rat_t0;  // inputs of the slot's segment consumed so far
+  std::vector<std::pair<int, int>> rat_lm;  // ratio of the slot's open segment, (0, 0): none open
+  std::vector<uint8_t> rat_par;   // which of the slot's two history buffers is current
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -778,6 +812,15 @@ int lvx_finalize(lvx_ctx* c) {
   if ((r = c->dalloc(&st.hist, (size_t)S * P)) || (r = c->dalloc(&st.hist_from, S))) return r;
   HIP_TRY(hipMemset(st.hist, 0, (size_t)S * P * 2));
   HIP_TRY(hipMemset(st.hist_from, 0, (size_t)S * 4));
+  // ---- PCM pitch shift (allocated last: every other buffer stays where it was) ----
+  if ((r = c->dalloc(&c->rat_taps, (size_t)S * RAT_TAPS_STRIDE)) || (r = c->dalloc(&c->rat_hist, (size_t)2 * S * RAT_HIST)))
+    return r;
+  HIP_TRY(hipMemset(c->rat_taps, 0, (size_t)S * RAT_TAPS_STRIDE * 4));
+  HIP_TRY(hipMemset(c->rat_hist, 0, (size_t)2 * S * RAT_HIST * 4));
+  c->rat_tab.assign(S, {0, 0});
+  c->rat_t0.assign(S, 0);
+  c->rat_lm.assign(S, {0, 0});
+  c->rat_par.assign(S, 0);
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
   c->finalized = true;
@@ -1285,6 +1328,8 @@ int lvx_pcm_reset(lvx_ctx* c, int slot, void* stream) {
   c->str_t0[slot] = 0;
   c->str_hops[slot] = 0;
   c->str_pct[slot] = 0;
+  c->rat_t0[slot] = 0;
+  c->rat_lm[slot] = {0, 0};
   return LVX_OK;
 }
 
@@ -1440,6 +1485,127 @@ int lvx_pcm_stretch(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t
     if (!any) continue;  // (a flush with nothing left)
     pcm_launch_stretch(pk, nr, speed_pct, pcm, n_in, c->str_win, c->str_hist, c->str_d, out, out_stride, d_out, d_stride,
                        (hipStream_t)stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+// ---- PCM pitch shift ----
+int lvx_pcm_pitch_plan(int speed_pct, int pitch_pct, int* stretch_pct, int* L, int* M) {
+  if (speed_pct < 50 || speed_pct > 200) return fail(LVX_E_ARG, "speed_pct must be in [50, 200], got " + std::to_string(speed_pct));
+  if (pitch_pct < 50 || pitch_pct > 200) return fail(LVX_E_ARG, "pitch_pct must be in [50, 200], got " + std::to_string(pitch_pct));
+  const int st = (200 * speed_pct + pitch_pct) / (2 * pitch_pct);  // speed 100 / pitch, rounded half up
+  if (st < 50 || st > 200)
+    return fail(LVX_E_ARG, "speed_pct " + std::to_string(speed_pct) + " with pitch_pct " + std::to_string(pitch_pct) +
+                               " needs a time stretch of " + std::to_string(st) + " percent, outside [50, 200]");
+  const int g = gcd_of(st, speed_pct);
+  if (stretch_pct) *stretch_pct = st;
+  if (L) *L = st / g;
+  if (M) *M = speed_pct / g;
+  return LVX_OK;
+}
+
+int lvx_pcm_ratio_filter(int L, int M, int* N, float* taps_host, int cap) {
+  if (!ratio_ok(L, M)) return fail(LVX_E_ARG, ratio_msg(L, M));
+  const int n = ratio_N(L, M);
+  if (N) *N = n;
+  if (taps_host) {
+    if (cap < 2 * n + 1) return fail(LVX_E_ARG, "taps_host holds fewer than 2 N + 1 floats");
+    const std::vector<float> h = pcm_design(L, M, n);
+    std::memcpy(taps_host, h.data(), h.size() * 4);
+  }
+  return LVX_OK;
+}
+
+int lvx_pcm_ratio_emitted(int L, int M, long long t0, int n_in, int final) {
+  if (!ratio_ok(L, M)) return fail(LVX_E_ARG, ratio_msg(L, M));
+  if (t0 < 0 || n_in < 0) return fail(LVX_E_ARG, "t0 and n_in must be >= 0");
+  const int N = ratio_N(L, M);
+  return (int)(pcm_emitted_upto(L, M, N, t0 + n_in, final != 0) - pcm_emitted_upto(L, M, N, t0, false));
+}
+
+int lvx_pcm_ratio(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const uint8_t* final_host,
+                  int L, int M, float* out, long long out_stride, int32_t* n_out_host, void* stream) {
+  NEED_FINAL(c);
+  if (!ratio_ok(L, M)) return fail(LVX_E_ARG, ratio_msg(L, M));
+  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
+  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
+  const int N = ratio_N(L, M);
+  const bool launch = N != 0;  // 1 / 1: the rows of pcm_dev are the output
+  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
+    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  const int S = c->cfg.max_streams;
+  const std::pair<int, int> lm{L, M};
+  std::vector<RatioRow> rows(B);
+  std::vector<int> upload;  // slots whose table region gets this ratio's table
+  const std::vector<float>* table = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror and the host cache: released before the launches)
+    // every row is checked before any slot's state changes
+    std::vector<uint8_t> seen(S, 0);
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
+      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
+      seen[s] = 1;
+      if (c->rat_lm[s].first && c->rat_lm[s] != lm)
+        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at the ratio " +
+                                   std::to_string(c->rat_lm[s].first) + " / " + std::to_string(c->rat_lm[s].second));
+      if (!launch) {
+        rows[b] = RatioRow{0, 0, n_in, 0, -1, b, 0};
+        continue;
+      }
+      const long long t0 = c->rat_t0[s];
+      const long long m0 = pcm_emitted_upto(L, M, N, t0, false), m1 = pcm_emitted_upto(L, M, N, t0 + n_in, final_host[b] != 0);
+      if (m1 - m0 > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
+      if ((m1 - m0) * 4 > out_stride)
+        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
+                                   std::to_string((m1 - m0) * 4) + " bytes)");
+      const int cur = (c->rat_par[s] * S + s) * RAT_HIST, other = ((1 - c->rat_par[s]) * S + s) * RAT_HIST;
+      const bool keep = n_in > 0 && !final_host[b];  // a history for the segment's next call
+      rows[b] = RatioRow{t0, m0, (int)(m1 - m0), cur, keep ? other : -1, b, s * RAT_TAPS_STRIDE};
+    }
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      n_out_host[b] = rows[b].n_out;
+      if (final_host[b]) {
+        c->rat_t0[s] = 0;
+        c->rat_lm[s] = {0, 0};
+      } else if (launch) {
+        c->rat_t0[s] += n_in;
+        c->rat_lm[s] = lm;
+        if (rows[b].hist_out >= 0) c->rat_par[s] ^= 1;
+      }
+      if (launch && rows[b].n_out > 0 && c->rat_tab[s] != lm) {
+        c->rat_tab[s] = lm;
+        upload.push_back(s);
+      }
+    }
+    if (!upload.empty()) {  // designed once per ratio; an entry stays (and stays where it is) for the context's life
+      auto it = c->rat_cache.find(lm);
+      if (it == c->rat_cache.end()) it = c->rat_cache.emplace(lm, pcm_design(L, M, N)).first;
+      table = &it->second;
+    }
+  }
+  if (!launch) return LVX_OK;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  // stream-ordered: behind the slot's earlier launches (which read the table of its last segment) and
+  // before this call's
+  for (int s : upload)
+    HIP_TRY(hipMemcpyAsync(c->rat_taps + (size_t)s * RAT_TAPS_STRIDE, table->data(), table->size() * 4, hipMemcpyHostToDevice,
+                           (hipStream_t)stream));
+  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
+    const int nr = std::min(PCM_ROWS, B - b0);
+    RatioRows pk{};
+    int max_out = 0;
+    bool any = false;
+    for (int k = 0; k < nr; ++k) {
+      pk.r[k] = rows[b0 + k];
+      max_out = std::max(max_out, pk.r[k].n_out);
+      any = any || pk.r[k].n_out > 0 || pk.r[k].hist_out >= 0;
+    }
+    if (!any) continue;  // (a flush with nothing left)
+    pcm_launch_ratio(pk, nr, max_out, L, M, N, pcm, n_in, c->rat_taps, c->rat_hist, out, out_stride, (hipStream_t)stream);
   }
   HIP_TRY(hipGetLastError());
   return LVX_OK;

@@ -270,6 +270,27 @@ struct PcmRows {
 void pcm_launch_convert(int sample_rate, int enc, const PcmRows& rows, int n_rows, int max_out, const float* pcm,
                         int n_in, const float* taps, float* hist, void* out, long long out_stride, hipStream_t s);
 
+// ---------------- PCM pitch shift: the ratio resampler (pcm_kernels.hip; llmvox.h "PCM pitch shift") ----------------
+constexpr int RAT_HIST = 256;        // inputs of history a slot keeps between calls (an output reaches back <= 192)
+constexpr int RAT_MAX = 200;         // L and M of a ratio: 1 .. 200
+constexpr int RAT_TAPS = 2 * 24 * RAT_MAX + 1;  // the longest prototype: 2 N + 1 with N = 24 max(L, M)
+constexpr int RAT_TAPS_STRIDE = (RAT_TAPS + 63) / 64 * 64;  // floats of a slot's table region
+struct RatioRow {  // PcmRow and where the slot's table is
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long m0;  // outputs of the segment emitted before this call = index of the call's first output
+  int n_out;     // outputs of this call
+  int hist_in;   // float offset of the slot's history [RAT_HIST] (inputs t0 - 256 .. t0 - 1) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int row;       // row of pcm / out
+  int taps;      // float offset of the slot's table region (h[-N .. N]) in the table pool
+};
+struct RatioRows {
+  RatioRow r[PCM_ROWS];
+};
+// one launch for n_rows <= PCM_ROWS rows; 1 <= L, M <= RAT_MAX, M <= 4 L, N = 24 max(L, M)
+void pcm_launch_ratio(const RatioRows& rows, int n_rows, int max_out, int L, int M, int N, const float* pcm, int n_in,
+                      const float* taps, float* hist, float* out, long long out_stride, hipStream_t s);
+
 // ---------------- PCM time stretch (pcm_kernels.hip; llmvox.h "PCM time stretch") ----------------
 constexpr int STR_H = 240;      // output hop
 constexpr int STR_D = 240;      // search radius

@@ -2,7 +2,8 @@
 // 24 kHz fp32 rows to 16 / 8 / 48 kHz and the s16le quantisation, one kernel family templated on
 // (L, M, N, encoding). Launched only for a stream that asked for another format than f32le at 24 kHz.
 // And the speaking-rate control in front of it ("PCM time stretch"): WSOLA on the 24 kHz rows, one block
-// per row, launched only for a stream that asked for another speed.
+// per row, launched only for a stream that asked for another speed. And the pitch control between the two
+// ("PCM pitch shift"): the same polyphase rule with a run-time L / M, launched only for a pitched stream.
 #include <algorithm>
 
 #include "lvx_internal.h"
@@ -122,6 +123,74 @@ void launch_enc(const PcmRows& rows, int n_rows, int max_out, int enc, const flo
   else
     pcm_convert_kernel<L, M, N, LVX_PCM_F32LE><<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, taps, hist,
                                                                             (unsigned char*)out, out_stride);
+}
+
+// ---- PCM pitch shift (llmvox.h, "PCM pitch shift"): the resampler of a run-time ratio L / M ----
+// pcm_convert_kernel's rule, packet and grid with L, M, N as arguments, f32 in and out. The slot's table
+// h[-N .. N] (its own region of the table pool) and the block's input span go to LDS: a block of PCM_OB
+// outputs touches every phase of the table.
+constexpr int RAT_SPAN = (PCM_OB - 1) * 4 + 2 * 24 * 4 + 3;  // inputs of a block at M = 4 L, the most the entry admits
+
+__global__ __launch_bounds__(PCM_THREADS) void pcm_ratio_kernel(RatioRows rows, int L, int M, int N,
+                                                                const float* __restrict__ pcm, int n_in,
+                                                                const float* __restrict__ taps, float* hist,
+                                                                unsigned char* __restrict__ out, long long out_stride) {
+  const RatioRow r = rows.r[blockIdx.y];
+  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
+  const int tid = threadIdx.x;
+  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
+  // segment input g (t0 - RAT_HIST <= g < t1) from the call's row or the slot's history; zero outside the segment
+  auto input = [&](long long g) -> float {
+    if (g < 0 || g >= t1) return 0.f;
+    if (g >= r.t0) return x[g - r.t0];
+    const long long back = r.t0 - g;
+    return back <= RAT_HIST ? hist[r.hist_in + RAT_HIST - back] : 0.f;
+  };
+  if (blockIdx.x == 0 && r.hist_out >= 0 && tid < RAT_HIST) hist[r.hist_out + tid] = input(t1 - RAT_HIST + tid);
+
+  const int mb = blockIdx.x * PCM_OB;
+  if (mb >= r.n_out) return;
+  const int nb = min(PCM_OB, r.n_out - mb);
+  const int ml = tid * PCM_PER_THREAD;  // the thread's first output within the block
+
+  __shared__ float s_h[RAT_TAPS];
+  __shared__ float s_x[RAT_SPAN];
+  const float* __restrict__ h = taps + r.taps;
+  const int n_taps = min(2 * N + 1, RAT_TAPS);
+  for (int k = tid; k < n_taps; k += PCM_THREADS) s_h[k] = h[k];
+  const long long m_first = r.m0 + mb;
+  const long long i0 = ceil_div(m_first * M - N, L);
+  const int span = (int)(floor_div((m_first + nb - 1) * M + N, L) - i0) + 1;  // <= RAT_SPAN while M <= 4 L
+  for (int k = tid; k < span && k < RAT_SPAN; k += PCM_THREADS) s_x[k] = input(i0 + k);
+  __syncthreads();
+  float v[PCM_PER_THREAD];
+#pragma unroll
+  for (int e = 0; e < PCM_PER_THREAD; ++e) {
+    float acc = 0.f;
+    if (ml + e < nb) {
+      const long long mm = (m_first + ml + e) * M;
+      const long long ilo = ceil_div(mm - N, L);
+      int t = (int)(mm - ilo * L);  // the first tap index: in (N - L, N]
+      int k = (int)(ilo - i0);
+      // inputs in ascending order, each product and each sum rounded to fp32 (no fused multiply-add): the
+      // rule's fixed order, as in pcm_convert_kernel
+      for (; t >= -N; t -= L, ++k) {
+#pragma clang fp contract(off)
+        const float prod = s_x[k] * s_h[t + N];
+        acc = acc + prod;
+      }
+    }
+    v[e] = acc;
+  }
+
+  float* o = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride) + mb + ml;
+  if (ml + PCM_PER_THREAD <= nb && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < PCM_PER_THREAD; ++e)
+      if (ml + e < nb) o[e] = v[e];
+  }
 }
 
 // ---- PCM time stretch (llmvox.h, "PCM time stretch"): WSOLA on the 24 kHz rows ----
@@ -280,6 +349,12 @@ void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, cons
                         int d_stride, hipStream_t s) {
   pcm_stretch_kernel<<<dim3((unsigned)n_rows), STR_THREADS, 0, s>>>(rows, speed_pct, pcm, n_in, win, hist, dstate,
                                                                     (unsigned char*)out, out_stride, d_out, d_stride);
+}
+
+void pcm_launch_ratio(const RatioRows& rows, int n_rows, int max_out, int L, int M, int N, const float* pcm, int n_in,
+                      const float* taps, float* hist, float* out, long long out_stride, hipStream_t s) {
+  const dim3 grid((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
+  pcm_ratio_kernel<<<grid, PCM_THREADS, 0, s>>>(rows, L, M, N, pcm, n_in, taps, hist, (unsigned char*)out, out_stride);
 }
 
 void pcm_launch_convert(int sample_rate, int enc, const PcmRows& rows, int n_rows, int max_out, const float* pcm,

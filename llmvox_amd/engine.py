@@ -319,34 +319,95 @@ class Engine:
                                             width * 4, cnt, _ptr(d), dw, self.stream_handle()))
         return out, list(cnt), d
 
+    def pcm_pitch_plan(self, speed_pct: int, pitch_pct: int):
+        """(stretch_pct, L, M) of a speed and a pitch as the library plans them (lvx_pcm_pitch_plan)."""
+        st, L, M = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _lib.check(self.lib.lvx_pcm_pitch_plan(int(speed_pct), int(pitch_pct), ctypes.byref(st), ctypes.byref(L),
+                                               ctypes.byref(M)))
+        return st.value, L.value, M.value
+
+    def pcm_ratio_filter(self, L: int, M: int):
+        """(N, taps float32 [2 N + 1]) of the ratio L / M, as the library designs them (lvx_pcm_ratio_filter)."""
+        N = ctypes.c_int()
+        _lib.check(self.lib.lvx_pcm_ratio_filter(int(L), int(M), ctypes.byref(N), None, 0))
+        taps = np.zeros(2 * N.value + 1, dtype=np.float32)
+        _lib.check(self.lib.lvx_pcm_ratio_filter(int(L), int(M), None, taps.ctypes.data_as(ctypes.c_void_p), taps.size))
+        return N.value, taps
+
+    def pcm_ratio(self, pcm: Optional[torch.Tensor], slots, finals, L: int, M: int):
+        """The pitch control's resampler alone (lvx_pcm_ratio): rows of ``pcm`` (device float32 [B, n_in]; None or
+        n_in 0: flush only) continue the ratio segments of ``slots`` at L / M (output count over input count); a
+        true ``finals[b]`` emits the rest of row b's segment and ends it. Returns (out, counts): a device
+        float32 tensor [B, width] whose row b holds counts[b] samples. 1 / 1: the rows themselves. Asynchronous
+        on the current stream; a slot's calls must be issued in order on one stream."""
+        slots = [int(s) for s in slots]
+        B = len(slots)
+        pcm, n_in = self._pcm_rows(pcm, B)
+        L, M = int(L), int(M)
+        out, width = None, 0
+        if L == M == 1:
+            out = pcm if pcm is not None else torch.empty(B, 0, device=self.device, dtype=torch.float32)
+        elif 1 <= L <= 200 and 1 <= M <= 200:
+            # a call emits at most (n_in L + L + N) / M + 2 samples, N = 24 max(L, M) (a final call of a segment
+            # whose earlier outputs waited for their right-hand inputs); rows start on 16-byte boundaries
+            width = ((n_in * L + L + 24 * max(L, M)) // M + 3 + 7) // 8 * 8
+            out = torch.empty(B, width, device=self.device, dtype=torch.float32)
+        sl = (ctypes.c_int32 * B)(*slots)
+        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
+        cnt = (ctypes.c_int32 * B)()
+        _lib.check(self.lib.lvx_pcm_ratio(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, L, M, _ptr(out), width * 4,
+                                          cnt, self.stream_handle()))
+        return out, list(cnt)
+
     def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
-        ``audio.AudioFormat`` (its speed, rate and encoding). Returns (out, counts): a device tensor
-        [B, width] of int16 or float32 whose row b holds counts[b] samples. A format with a speed has its rows
-        time-stretched first (lvx_pcm_stretch); the stretched rows, which may hold different counts, then pass
-        the resampling / quantisation grouped by count. Asynchronous on the current stream; a slot's calls
-        must be issued in order on one stream (lvx_pcm_convert)."""
-        if fmt.speed_pct == 100:
-            return self._pcm_resample(pcm, slots, finals, fmt)
+        ``audio.AudioFormat`` (its speed, pitch, rate and encoding). Returns (out, counts): a device tensor
+        [B, width] of int16 or float32 whose row b holds counts[b] samples. Three stages, each only where the
+        format needs it: the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the
+        plan's L / M (lvx_pcm_ratio), the rate and the encoding (lvx_pcm_convert). Rows may leave a stage with
+        different counts: they pass the next one grouped by count. A format without a pitch makes the calls it
+        made before there was one. Asynchronous on the current stream; a slot's calls must be issued in order
+        on one stream."""
+        stretch_pct, (L, M) = fmt.stretch_pct, fmt.ratio
+        plain = fmt.sample_rate == 24000 and fmt.encoding == "f32le"  # the last stage has nothing to do
+        dtype = torch.int16 if fmt.encoding == "s16le" else torch.float32
+
+        def last(sub, sl, fl):
+            return self._pcm_resample(sub, sl, fl, fmt)
+
+        def ratio(sub, sl, fl):
+            if L == M:
+                return last(sub, sl, fl)
+            o, c = self.pcm_ratio(sub, sl, fl, L, M)
+            return (o, c) if plain else self._pcm_grouped(o, c, sl, fl, last, dtype)
+
+        if stretch_pct == 100:
+            return ratio(pcm, slots, finals)
         slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
-        st, cnt, _ = self.pcm_stretch(pcm, slots, finals, fmt.speed_pct)
-        if fmt.sample_rate == 24000 and fmt.encoding == "f32le":
+        st, cnt, _ = self.pcm_stretch(pcm, slots, finals, stretch_pct)
+        if L == M and plain:
             return st, cnt
+        return self._pcm_grouped(st, cnt, slots, finals, ratio, dtype)
+
+    def _pcm_grouped(self, st, cnt, slots, finals, stage, dtype):
+        """The hand-over between two stages: row b of ``st`` holds cnt[b] samples; the rows pass
+        ``stage(rows, slots, finals)`` grouped by count (a row with nothing to hand on and no end is left
+        out). Returns (out, counts) over all rows."""
+        slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
         groups: Dict[int, list] = {}
         for b, n in enumerate(cnt):
-            if n or finals[b]:  # (nothing stretched and no end: nothing to hand on)
+            if n or finals[b]:  # (nothing came out of the stage before and no end: nothing to hand on)
                 groups.setdefault(n, []).append(b)
         parts = []
         for n, rows in groups.items():
             sub = None if n == 0 else st[:, :n] if len(rows) == len(slots) else st[rows, :n]
-            o, c = self._pcm_resample(sub, [slots[b] for b in rows], [finals[b] for b in rows], fmt)
+            o, c = stage(sub, [slots[b] for b in rows], [finals[b] for b in rows])
             parts.append((rows, o, c))
         if len(parts) == 1 and len(parts[0][0]) == len(slots):
             return parts[0][1], parts[0][2]
         width = max([o.shape[1] for _, o, _ in parts], default=0)
-        out = torch.zeros(len(slots), width, device=self.device,
-                          dtype=torch.int16 if fmt.encoding == "s16le" else torch.float32)
+        out = torch.zeros(len(slots), width, device=self.device, dtype=dtype)
         counts = [0] * len(slots)
         for rows, o, c in parts:
             out[rows, :o.shape[1]] = o
@@ -355,7 +416,7 @@ class Engine:
         return out, counts
 
     def _pcm_resample(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
-        """pcm_convert without the speed: the rate and the encoding (lvx_pcm_convert)."""
+        """pcm_convert without the speed and the pitch: the rate and the encoding (lvx_pcm_convert)."""
         slots = [int(s) for s in slots]
         B = len(slots)
         n_in = 0 if pcm is None else int(pcm.shape[1])

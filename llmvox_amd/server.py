@@ -364,9 +364,20 @@ def speed_pct_of(speed) -> int:
     return pct
 
 
+def pitch_pct_of(pitch) -> int:
+    """A pitch factor (a float in 0.5 .. 2.0) as the integer percentage the pitch control takes
+    (``audio.AudioFormat.pitch_pct``); ValueError for anything else."""
+    if isinstance(pitch, bool) or not isinstance(pitch, (int, float)) or not math.isfinite(pitch):
+        raise ValueError(f"pitch must be a number in 0.5 .. 2.0, got {pitch!r}")
+    pct = int(round(pitch * 100))
+    if not 50 <= pct <= 200:
+        raise ValueError(f"pitch must be in 0.5 .. 2.0, got {pitch!r}")
+    return pct
+
+
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
                encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
-               min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64):
+               min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -383,7 +394,11 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     carries in ``X-Audio-Sample-Rate`` / ``X-Audio-Encoding`` and its media type (audio/wav for the wav
     container). ``speed`` (a float in 0.5 .. 2.0; 1.0: as spoken) is the speaking rate: the PCM is
     time-stretched on the device, pitch preserved, to round(speed * 100) percent (``audio.AudioFormat.speed_pct``);
-    out of range: 422; the response carries it in ``X-Audio-Speed``. The reference's /voicechat,
+    out of range: 422; the response carries it in ``X-Audio-Speed``. ``pitch`` (a float in 0.5 .. 2.0; 1.0: as
+    spoken) shifts the pitch at the same duration: the PCM is stretched and resampled on the device as
+    ``audio.pitch_plan`` says for round(pitch * 100) percent; out of range, or a speed / pitch combination whose
+    stretch falls outside 50 .. 200 percent: 422 with the plan's message; the response carries the realised
+    ratio, speed_pct / stretch_pct, in ``X-Audio-Pitch``. The reference's /voicechat,
     /multimodalchat and /vlmschat differ from /tts only in the producer (ASR / multimodal LLM,
     out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
@@ -395,7 +410,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     Sampling(temperature, top_k, 0, top_p, min_p, repetition_penalty, repetition_window)  # (validated at start-up)
     extra_defaults = {"top_p": top_p, "min_p": min_p, "repetition_penalty": repetition_penalty,
                       "repetition_window": repetition_window}
-    default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed))
+    default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch))
 
     class TTSRequest(BaseModel):
         text: str
@@ -410,6 +425,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         encoding: Optional[str] = None
         container: Optional[str] = None
         speed: Optional[float] = None
+        pitch: Optional[float] = None
 
     def audio_of(request):
         """The request's AudioFormat (the defaults for the fields it does not name)."""
@@ -417,7 +433,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
             return AudioFormat(default_audio.sample_rate if request.sample_rate is None else request.sample_rate,
                                default_audio.encoding if request.encoding is None else request.encoding,
                                default_audio.container if request.container is None else request.container,
-                               default_audio.speed_pct if request.speed is None else speed_pct_of(request.speed))
+                               default_audio.speed_pct if request.speed is None else speed_pct_of(request.speed),
+                               default_audio.pitch_pct if request.pitch is None else pitch_pct_of(request.pitch))
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -462,7 +479,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
             raise HTTPException(status_code=503, detail=str(e))
         return StreamingResponse(service.chunks(session), media_type=fmt.media_type,
                                  headers={"X-Audio-Sample-Rate": str(fmt.sample_rate), "X-Audio-Encoding": fmt.encoding,
-                                          "X-Audio-Speed": f"{fmt.speed_pct / 100:.2f}"})
+                                          "X-Audio-Speed": f"{fmt.speed_pct / 100:.2f}",
+                                          "X-Audio-Pitch": f"{fmt.speed_pct / fmt.stretch_pct:.4f}"})
 
     @app.get("/health")
     def health():
@@ -506,6 +524,8 @@ def arg_parser():
     ap.add_argument("--container", default="raw", choices=["raw", "wav"], help="their container (wav: a header first)")
     ap.add_argument("--speed", type=float, default=1.0,
                     help="speaking rate of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
+    ap.add_argument("--pitch", type=float, default=1.0,
+                    help="pitch factor of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
     return ap
 
 
@@ -513,7 +533,7 @@ def app_options(a) -> dict:
     """``create_app``'s keywords from the parsed command line: the defaults of the requests' optional fields."""
     return dict(temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate, encoding=a.encoding,
                 container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
-                repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window)
+                repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch)
 
 
 def main(argv=None):
