@@ -284,6 +284,37 @@ int lvx_kv_read(lvx_ctx* ctx, int slot, int layer, int pos0, int n, float* k_dev
  * written in stream order. */
 int lvx_attn_probe(lvx_ctx* ctx, int B, const int32_t* slots_dev, int layer, const float* q_dev, float* out_dev,
                    float* part_o_dev, float* part_ml_dev, int* form_out, void* stream);
+/* Test hook: stages [first, last] of the codec decode on caller-supplied input, through the decode's own
+ * launch helpers and scratch (so kernel routing, split-K choice and the split-image decisions are exactly
+ * those of lvx_codec_decode_codes at this B, L and these options). Never part of a step or a graph.
+ * Stages, in decode order (LVX_CODEC_STAGES of them):
+ *    0      code gather + embed conv (k7)       in: codes int32 [B][L]      out: x float32 [B*L][768]
+ *    1, 2   pos_net ResnetBlocks 0, 1           x -> x
+ *    3      AttnBlock                           x -> x
+ *    4, 5   pos_net ResnetBlocks 2, 3           x -> x
+ *    6      pos_net GroupNorm + backbone AdaLN  x -> x
+ *    7..18  ConvNeXt blocks 0..11               x -> x
+ *   19      final LayerNorm + head Linear       x -> spec float32 [B*L][1282]
+ *   20      iSTFT frames + overlap-add          spec -> pcm float32 [B][320*L]
+ * in_dev holds the input of stage `first`, out_dev receives the output of stage `last` (device buffers,
+ * copied / written in stream order). routes_out (host, may be null with route_cap 0) receives one record
+ * per GEMM launched in the window, in launch order; *n_routes_out their number (which may exceed
+ * route_cap: only route_cap are written). Arguments are checked as lvx_codec_decode_codes checks them
+ * (LVX_E_CAPACITY, LVX_E_ARG), plus 0 <= first <= last < LVX_CODEC_STAGES. */
+#define LVX_CODEC_STAGES 21
+#define LVX_ROUTE_MFMA64 0   /* gemm_mfma_kernel, 64 x 64 tile: v = {bf16 operands, batch, K % 32 == 0} */
+#define LVX_ROUTE_BF16_128 1 /* gemm_bf16_kernel, 128 x 128 tile: v = {bytes of A, bytes of W (1: fp8), 0} */
+#define LVX_ROUTE_GLDS 2     /* gemm_glds_kernel, 128 x 192 tile: v = {NS stages, SPLIT form, bytes of A} */
+#define LVX_ROUTE_SKINNY 3   /* gemm_skinny_kernel: v = {MI, NJ, NWV} */
+typedef struct lvx_codec_route {
+  int32_t family;   /* LVX_ROUTE_* */
+  int32_t ksplit;   /* K splits of the launch (1: none) */
+  int32_t inlaunch; /* 1: the split-K partials are combined inside the GEMM launch, 0: by a reduce kernel */
+  int32_t v[3];     /* per family, above */
+  int32_t N, K;     /* the GEMM's N and K */
+} lvx_codec_route;
+int lvx_codec_stages(lvx_ctx* ctx, int first, int last, const void* in_dev, int B, int L, int bandwidth_id,
+                     float* out_dev, lvx_codec_route* routes_out, int route_cap, int* n_routes_out, void* stream);
 /* Host-side view of a slot's position (synchronises the stream). */
 int lvx_stream_position(lvx_ctx* ctx, int slot, int* pos_out, void* stream);
 /* Cross-check switches between two correct implementations of the same step, per context (round 4:

@@ -110,6 +110,7 @@ _SIGS = {
     "lvx_set_option": (_I, [_P, ctypes.c_char_p, _I]),
     "lvx_codec_decode_features": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "lvx_codec_decode_codes": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "lvx_codec_stages": (_I, [_P, _I, _I, _P, _I, _I, _I, _P, _P, _I, ctypes.POINTER(_I), _P]),
     "lvx_pcm_filter": (_I, [_I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _P, _I]),
     "lvx_pcm_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
     "lvx_pcm_reset": (_I, [_P, _I, _P]),
@@ -155,6 +156,9 @@ def load():
 ERRW_AR = 1     # LVX_ERRW_AR: the decode / drop-in gather error word
 ERRW_CODEC = 2  # LVX_ERRW_CODEC: the codec's error word
 BIT_NUMERIC = 32  # AR word: the fused MLP's fixed-point range check
+# LVX_ROUTE_*: the GEMM family of a route record of lvx_codec_stages
+ROUTE_MFMA64, ROUTE_BF16_128, ROUTE_GLDS, ROUTE_SKINNY = 0, 1, 2, 3
+CODEC_STAGES = 21  # LVX_CODEC_STAGES
 
 
 def error_for(code: int, bits: int = 0):

@@ -380,6 +380,15 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(GemmArgs g, int batch)
 // devices) never see each other's workspace or tickets
 static thread_local size_t g_ws_floats = 0;
 static thread_local uint32_t* g_tick = nullptr;
+// route records of the GEMMs a stage window launches (test hook lvx_codec_stages; null in production
+// decodes): one CodecRoute per weight / activation GEMM, in launch order, written by the launch helpers
+static thread_local CodecRoute* g_route = nullptr;
+static thread_local int g_route_cap = 0, g_route_n = 0;
+static inline void route_note(int family, const GemmArgs& g, int ksplit, int inlaunch, int v0, int v1, int v2) {
+  if (!g_route) return;
+  if (g_route_n < g_route_cap) g_route[g_route_n] = CodecRoute{family, ksplit, inlaunch, v0, v1, v2, g.N, g.K};
+  ++g_route_n;
+}
 
 template <bool BF, typename TA, typename TB, int AMODE, int EPI, typename TC>
 static void gemm_launch(GemmArgs g, int batch, hipStream_t s) {
@@ -398,6 +407,7 @@ static void gemm_launch(GemmArgs g, int batch, hipStream_t s) {
   g.ksplit = ks;
   g.tick = (inl && ks > 1) ? g_tick : nullptr;
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, batch * ks);
+  route_note(LVX_ROUTE_MFMA64, g, ks, g.tick != nullptr, BF, batch, g.K % BK == 0);
   if (g.K % BK == 0) hipLaunchKernelGGL((gemm_mfma_kernel<BF, TA, TB, AMODE, EPI, TC, true>), grid, dim3(256), 0, s, g);
   else hipLaunchKernelGGL((gemm_mfma_kernel<BF, TA, TB, AMODE, EPI, TC, false>), grid, dim3(256), 0, s, g);
   if (ks > 1 && !g.tick) {
@@ -672,6 +682,7 @@ static void gemm2_launch(GemmArgs g, hipStream_t s) {
   g.ksplit = ks;
   g.xcd_remap = 1;
   dim3 grid((g.N + G2_BN - 1) / G2_BN, (g.M + 127) / 128, ks);
+  route_note(LVX_ROUTE_BF16_128, g, ks, 0, (int)sizeof(TA), (int)sizeof(TB), 0);
   hipLaunchKernelGGL((gemm_bf16_kernel<TA, TB, AMODE, EPI, TC, 128>), grid, dim3(256), 0, s, g);
   if (ks > 1) {
     const int blocks = (int)std::min<size_t>(((size_t)g.M * g.N + 255) / 256, 2048);
@@ -1054,6 +1065,7 @@ static void g3_launch(GemmArgs g, hipStream_t s) {
   // tiles) 40.4 vs 47 us; 16 x 256 frames (N = 2,304: 384 tiles) 1.57 vs 1.70 ms per decode
   // (round 5: one block per CU at any tile count, leaving 40 KB of LDS to the decode kernels beside the
   // codec, measured the same: configs[2] 235.0 / 235.5 / 235.7k vs 235.1 / 234.4 / 235.2k tok/s)
+  route_note(LVX_ROUTE_GLDS, g, 1, 0, grid.x * grid.y > 256 ? 2 : 3, SPLIT, (int)sizeof(TA));
   if (grid.x * grid.y > 256) hipLaunchKernelGGL((gemm_glds_kernel<AMODE, EPI, TC, 2, TA, SPLIT>), grid, dim3(512), 0, s, g);
   else hipLaunchKernelGGL((gemm_glds_kernel<AMODE, EPI, TC, 3, TA, SPLIT>), grid, dim3(512), 0, s, g);
 }
@@ -1171,6 +1183,7 @@ static bool skinny_go(const GemmArgs& g, hipStream_t s) {
   const dim3 grid((g.N + 16 * NJ - 1) / (16 * NJ), (g.M + 16 * MI - 1) / (16 * MI));
   const int S = g.K / (32 * NWV);
   if (g.K % (32 * NWV)) return false;
+  if (S == 3 || S == 6 || S == 9 || S == 14 || S == 18 || S == 28) route_note(LVX_ROUTE_SKINNY, g, 1, 0, MI, NJ, NWV);
   switch (S) {  // the codec's K: 768 (1x1 convs, head), 2,304 (pwconv2, k3 convs), 3,584 (embed k7)
     case 3: hipLaunchKernelGGL((gemm_skinny_kernel<AMODE, EPI, TC, MI, NJ, 3, NWV>), grid, dim3(NWV * 64), 0, s, g); return true;
     case 6: hipLaunchKernelGGL((gemm_skinny_kernel<AMODE, EPI, TC, MI, NJ, 6, NWV>), grid, dim3(NWV * 64), 0, s, g); return true;
@@ -1862,7 +1875,11 @@ __global__ void istft_ola_kernel(const float* __restrict__ frames, const float* 
 // ---------------------------------------------------------------------------------
 template <typename TW>
 static void decode_impl(const CodecWeights& w, const CodecScratch& sc, const float* feats_in, const int32_t* codes,
-                        int B, int L, int bw, float* pcm, hipStream_t s) {
+                        int B, int L, int bw, float* pcm, hipStream_t s, int first = 0, int last = CODEC_STAGES - 1) {
+  // stages in decode order (the table at lvx_codec_stages in llmvox.h); sc.x is the only state that crosses a stage
+  // boundary (sc.spec between 19 and 20). The production entry points run the full window; the test hook
+  // lvx_codec_stages a part of it, through the same launches.
+  auto on = [&](int st) { return st >= first && st <= last; };
   const int M = B * L;
   float* x = sc.x;
   float* t1 = sc.t1;
@@ -1883,24 +1900,26 @@ static void decode_impl(const CodecWeights& w, const CodecScratch& sc, const flo
     if constexpr (sizeof(TW) == 4) c.asplit = g3_split_in(c);
     return c.asplit != 0;
   };
-  GemmArgs g{};
-  g.ws = sc.ws;
-  g.L = L;
-  g.M = M;
-  // embed Conv1d(512->768, k7, pad 3)
-  g.A = feats; g.lda = CIN; g.cin = CIN; g.taps = 7;
-  g.W = w.embed_w; g.wscale = w.embed_s; g.ldw = 7 * CIN; g.K = 7 * CIN; g.N = CD;
-  g.C = x; g.ldc = CD; g.bias = w.embed_b;
-  spl(g);
-  if (codes) {
-    if constexpr (sizeof(TAct) == 2) hipLaunchKernelGGL(codes_gather_bf16_kernel, dim3(M), dim3(CIN / 4), 0, s, w.codebook, codes, feats, sc.err);
-    else if (g.asplit) hipLaunchKernelGGL(codes_gather_kernel<true>, dim3(M), dim3(CIN / 4), 0, s, w.codebook, codes, feats, sc.err);
-    else hipLaunchKernelGGL(codes_gather_kernel<>, dim3(M), dim3(CIN / 4), 0, s, w.codebook, codes, feats, sc.err);
-  } else {
-    g.asplit = 0;  // features handed in: transposed as plain rows
-    hipLaunchKernelGGL(feats_transpose_kernel<TAct>, dim3((L + 31) / 32, CIN / 32, B), dim3(256), 0, s, feats_in, L, feats);
+  if (on(0)) {
+    GemmArgs g{};
+    g.ws = sc.ws;
+    g.L = L;
+    g.M = M;
+    // embed Conv1d(512->768, k7, pad 3)
+    g.A = feats; g.lda = CIN; g.cin = CIN; g.taps = 7;
+    g.W = w.embed_w; g.wscale = w.embed_s; g.ldw = 7 * CIN; g.K = 7 * CIN; g.N = CD;
+    g.C = x; g.ldc = CD; g.bias = w.embed_b;
+    spl(g);
+    if (codes) {
+      if constexpr (sizeof(TAct) == 2) hipLaunchKernelGGL(codes_gather_bf16_kernel, dim3(M), dim3(CIN / 4), 0, s, w.codebook, codes, feats, sc.err);
+      else if (g.asplit) hipLaunchKernelGGL(codes_gather_kernel<true>, dim3(M), dim3(CIN / 4), 0, s, w.codebook, codes, feats, sc.err);
+      else hipLaunchKernelGGL(codes_gather_kernel<>, dim3(M), dim3(CIN / 4), 0, s, w.codebook, codes, feats, sc.err);
+    } else {
+      g.asplit = 0;  // features handed in: transposed as plain rows
+      hipLaunchKernelGGL(feats_transpose_kernel<TAct>, dim3((L + 31) / 32, CIN / 32, B), dim3(256), 0, s, feats_in, L, feats);
+    }
+    gemm_w<TW, TAct, A_CONV, E_BIAS>(g, s);
   }
-  gemm_w<TW, TAct, A_CONV, E_BIAS>(g, s);
 
   auto resnet = [&](int i) {  // models.py:58-78
     GemmArgs c{};
@@ -1914,9 +1933,9 @@ static void decode_impl(const CodecWeights& w, const CodecScratch& sc, const flo
     c.W = w.rn_c2w[i]; c.wscale = w.rn_c2s[i]; c.bias = w.rn_c2b[i]; c.C = x; c.res = x; c.ldr = CD;
     gemm_w<TW, TAct, A_CONV, E_BIAS_RES>(c, s);
   };
-  resnet(0);
-  resnet(1);
-  {  // AttnBlock (models.py:107-127)
+  if (on(1)) resnet(0);
+  if (on(2)) resnet(1);
+  if (on(3)) {  // AttnBlock (models.py:107-127)
     GemmArgs c{};
     c.ws = sc.ws;
     c.L = L; c.M = M; c.K = CD; c.N = 3 * CD; c.ldw = CD;
@@ -1958,13 +1977,15 @@ static void decode_impl(const CodecWeights& w, const CodecScratch& sc, const flo
     o.C = x; o.ldc = CD; o.res = x; o.ldr = CD;
     gemm_w<TW, TAct, A_PLAIN, E_BIAS_RES>(o, s);
   }
-  resnet(2);
-  resnet(3);
-  // pos_net[5] GroupNorm + backbone AdaLN
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(GN_G, B), dim3(256), 0, s, x, L, sc.stats);
-  hipLaunchKernelGGL(gn_adaln_kernel, dim3(M), dim3(256), 0, s, x, L, sc.stats, w.pn_w, w.pn_b,
-                     w.ada_scale + (size_t)bw * CD, w.ada_shift + (size_t)bw * CD, x);
+  if (on(4)) resnet(2);
+  if (on(5)) resnet(3);
+  if (on(6)) {  // pos_net[5] GroupNorm + backbone AdaLN
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(GN_G, B), dim3(256), 0, s, x, L, sc.stats);
+    hipLaunchKernelGGL(gn_adaln_kernel, dim3(M), dim3(256), 0, s, x, L, sc.stats, w.pn_w, w.pn_b,
+                       w.ada_scale + (size_t)bw * CD, w.ada_shift + (size_t)bw * CD, x);
+  }
   for (int i = 0; i < 12; ++i) {  // ConvNeXt blocks (modules.py:43-60)
+    if (!on(7 + i)) continue;
     const int dwft = (opts().codec_exp >> 1) & 3;
     GemmArgs c{};
     c.ws = sc.ws;
@@ -2012,7 +2033,7 @@ static void decode_impl(const CodecWeights& w, const CodecScratch& sc, const flo
     gemm_w<TW, TAct, A_PLAIN, E_BIAS_GELU, TAct>(c, s);
     gemm_w<TW, TAct, A_PLAIN, E_BIAS_GAMMA_RES>(d, s);
   }
-  {  // final LayerNorm, ISTFTHead.out Linear(768 -> 1282)
+  if (on(19)) {  // final LayerNorm, ISTFTHead.out Linear(768 -> 1282)
     GemmArgs h{};
     h.ws = sc.ws;
     h.M = M; h.L = L; h.N = 2 * NB; h.K = CD; h.ldw = CD;
@@ -2021,6 +2042,7 @@ static void decode_impl(const CodecWeights& w, const CodecScratch& sc, const flo
     else hipLaunchKernelGGL(ln_affine_kernel<TAct>, dim3(M), dim3(256), 0, s, x, w.fln_w, w.fln_b, t2a);
     gemm_w<TW, TAct, A_PLAIN, E_BIAS>(h, s);
   }
+  if (!on(20)) return;
   if (sizeof(TAct) == 2 && !(opts().codec_exp & 8))
     hipLaunchKernelGGL(istft_frames_kernel<true>, dim3(M), dim3(256), 0, s, sc.spec,
                        reinterpret_cast<const float2*>(w.twiddle), w.window, sc.frames);
@@ -2034,6 +2056,25 @@ void codec_launch_decode(const CodecWeights& w, const CodecScratch& sc, int wdty
                          const int32_t* codes, int B, int L, int bw, float* pcm, hipStream_t s) {
   if (wdtype == LVX_DTYPE_BF16) decode_impl<bf16_t>(w, sc, feats_in, codes, B, L, bw, pcm, s);
   else decode_impl<float>(w, sc, feats_in, codes, B, L, bw, pcm, s);
+}
+
+int codec_launch_stages(const CodecWeights& w, const CodecScratch& sc, int wdtype, int first, int last, const void* in,
+                        int B, int L, int bw, float* out, CodecRoute* routes, int cap, hipStream_t s) {
+  const size_t M = (size_t)B * L;
+  const int32_t* codes = nullptr;
+  if (first == 0) codes = static_cast<const int32_t*>(in);
+  else if (first == CODEC_STAGES - 1) (void)hipMemcpyAsync(sc.spec, in, M * 2 * NB * 4, hipMemcpyDeviceToDevice, s);
+  else (void)hipMemcpyAsync(sc.x, in, M * CD * 4, hipMemcpyDeviceToDevice, s);
+  g_route = routes;
+  g_route_cap = cap;
+  g_route_n = 0;
+  float* pcm = last == CODEC_STAGES - 1 ? out : nullptr;
+  if (wdtype == LVX_DTYPE_BF16) decode_impl<bf16_t>(w, sc, nullptr, codes, B, L, bw, pcm, s, first, last);
+  else decode_impl<float>(w, sc, nullptr, codes, B, L, bw, pcm, s, first, last);
+  g_route = nullptr;
+  if (last == CODEC_STAGES - 2) (void)hipMemcpyAsync(out, sc.spec, M * 2 * NB * 4, hipMemcpyDeviceToDevice, s);
+  else if (last < CODEC_STAGES - 2) (void)hipMemcpyAsync(out, sc.x, M * CD * 4, hipMemcpyDeviceToDevice, s);
+  return g_route_n;
 }
 
 }  // namespace lvx

@@ -1294,6 +1294,25 @@ int lvx_codec_decode_codes(lvx_ctx* c, const int32_t* codes, int B, int L, int b
   return LVX_OK;
 }
 
+int lvx_codec_stages(lvx_ctx* c, int first, int last, const void* in, int B, int L, int bw, float* out,
+                     lvx_codec_route* routes, int route_cap, int* n_routes, void* stream) {
+  NEED_FINAL(c);
+  if (int r = codec_check(c, B, L, bw)) return r;
+  if (first < 0 || last >= LVX_CODEC_STAGES || first > last)
+    return fail(LVX_E_ARG, "stage window must satisfy 0 <= first <= last < " + std::to_string(LVX_CODEC_STAGES));
+  if (!in || !out) return fail(LVX_E_ARG, "null in/out");
+  if (route_cap < 0 || (route_cap > 0 && !routes)) return fail(LVX_E_ARG, "route_cap without routes_out");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const Opts o = c->opts_snapshot();
+  OptScope os(&o);
+  // launched kernel by kernel, never captured into a graph
+  const int n = codec_launch_stages(c->cw, c->cs, c->cfg.weight_dtype, first, last, in, B, L, bw, out, routes,
+                                    route_cap, (hipStream_t)stream);
+  if (n_routes) *n_routes = n;
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
 // ---- PCM output stage ----
 int lvx_pcm_filter(int sample_rate, int* L, int* M, int* N, float* taps_host, int cap) {
   const PcmRate* pr = pcm_rate_of(sample_rate);

@@ -243,6 +243,13 @@ struct CodecScratch {
 // feats_in: [B][512][L] (reference layout) when codes == nullptr; else codes [B][L]
 void codec_launch_decode(const CodecWeights& w, const CodecScratch& sc, int wdtype, const float* feats_in,
                          const int32_t* codes, int B, int L, int bw, float* pcm, hipStream_t s);
+// test hook (lvx_codec_stages): stages [first, last] of the decode on `in` (codes for stage 0, x for 1..19,
+// the spectrum for 20), the state after `last` copied to `out`; one route record per GEMM launched, at
+// most `cap` of them written to `routes` (host). Returns the number of GEMMs launched.
+constexpr int CODEC_STAGES = LVX_CODEC_STAGES;
+typedef lvx_codec_route CodecRoute;
+int codec_launch_stages(const CodecWeights& w, const CodecScratch& sc, int wdtype, int first, int last, const void* in,
+                        int B, int L, int bw, float* out, CodecRoute* routes, int cap, hipStream_t s);
 
 // ---------------- encoder (encode_infer) ----------------
 void enc_launch_conv(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int L, int T,

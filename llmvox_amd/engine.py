@@ -259,6 +259,28 @@ class Engine:
                                                    self.stream_handle()))
         return pcm
 
+    def codec_stages(self, first: int, last: int, inp: torch.Tensor, B: int, L: int, bandwidth_id: int = 0):
+        """Test hook: stages ``first .. last`` of the codec decode (the table at lvx_codec_stages in llmvox.h)
+        on ``inp``: int32 codes [B, L] for stage 0, the float32 residual stream [B * L, 768] for 1 .. 19, the
+        spectrum [B * L, 1282] for 20. Returns (out, routes): the state after ``last`` (x, the spectrum after
+        19, PCM [B, 320 L] after 20) and one tuple (family, ksplit, inlaunch, v0, v1, v2, N, K) per GEMM the
+        window launched, in launch order (family: _lib.ROUTE_*)."""
+        B, L, M = int(B), int(L), int(B) * int(L)
+        want = (B, L) if first == 0 else (M, 1282) if first == 20 else (M, 768)
+        inp = inp.to(self.device, torch.int32 if first == 0 else torch.float32).contiguous()
+        if tuple(inp.shape) != want:
+            raise ValueError(f"stage {first} takes an input of shape {want}, got {tuple(inp.shape)}")
+        shape = (B, 320 * L) if last == 20 else (M, 1282) if last == 19 else (M, 768)
+        out = torch.empty(*shape, device=self.device, dtype=torch.float32)
+        cap = 64
+        rec = (ctypes.c_int32 * (8 * cap))()
+        n = ctypes.c_int()
+        _lib.check(self.lib.lvx_codec_stages(self.h, int(first), int(last), _ptr(inp), B, L, int(bandwidth_id),
+                                             _ptr(out), rec, cap, ctypes.byref(n), self.stream_handle()))
+        if n.value > cap:
+            raise RuntimeError(f"{n.value} GEMMs in the window, more than the {cap} route records asked for")
+        return out, [tuple(rec[8 * i:8 * i + 8]) for i in range(n.value)]
+
     # ---- PCM output stage ------------------------------------------------------------
     def pcm_filter(self, sample_rate: int):
         """(L, M, N, taps float32 [2 N + 1]) of an output rate, as the library designs them (lvx_pcm_filter)."""
