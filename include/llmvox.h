@@ -427,7 +427,7 @@ int lvx_pcm_filter(int sample_rate, int* L, int* M, int* N, float* taps_host, in
 /* host only: samples a call emits for a slot that has consumed t0 inputs of its segment
  * (negative: LVX_E_ARG for an unsupported rate, t0 < 0 or n_in < 0) */
 int lvx_pcm_emitted(int sample_rate, long long t0, int n_in, int final);
-/* forget a slot's history and position (a new segment); stream-ordered */
+/* forget a slot's history and position (a new segment) in every PCM stage below; stream-ordered */
 int lvx_pcm_reset(lvx_ctx* ctx, int slot, void* stream);
 /* rows b of pcm_dev [B][n_in] f32 continue the segments of slots_host[b]; final_host[b] != 0 flushes and
  * resets the slot. n_in may be 0 with final (flush only). out row b starts at out_dev + b * out_stride_bytes
@@ -561,6 +561,63 @@ int lvx_pcm_ratio_emitted(int L, int M, long long t0, int n_in, int final);
 int lvx_pcm_ratio(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
                   const uint8_t* final_host, int L, int M, float* out_dev, long long out_stride_bytes,
                   int32_t* n_out_host, void* stream);
+
+/* ---- PCM dump join ------------------------------------------------------------
+ * The click-free join of a sentence's dumps. A sentence reaches the listener as a series of dumps, each
+ * decoded by the codec on its own; the codec is not causal (k7 depthwise and k3 convolutions, attention
+ * over the call), so the last frames of a dump are rendered against zero padding and the first frames of
+ * the next one without left context: plain concatenation has a seam at every dump boundary. A stream that
+ * asks for the join has every dump after a sentence's first decoded with up to LVX_JOIN_CONTEXT frames of
+ * context in front (the tokens dumped just before it), and this stage, IN FRONT of the stretch, the ratio
+ * and the rate conversion, holds back the last frame of every non-final rendering and crossfades it with
+ * the next call's rendering of the same frame. A stream that does not ask never comes here.
+ *
+ * UNLIKE THE OTHER THREE STAGES THE RESULT DEPENDS ON WHERE THE DUMPS WERE CUT: that is its nature (the
+ * renderings it joins differ with the cuts). Given the cuts and the context counts, the device output is
+ * bit-identical to a host evaluation of the same order (llmvox_amd/audio.py: join_ref).
+ *
+ * Constants: LVX_JOIN_HOLD = 320 samples, one codec frame: the hold-back and the crossfade length.
+ * LVX_JOIN_CONTEXT = 16 frames: the most context a call may carry.
+ * Windows, built on the host in double, each rounded once to fp32 (lvx_pcm_join_window):
+ *   wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / 320), n = 0 .. 319;  wf[n] = 1 - wr[n] (subtracted in double).
+ *
+ * One segment is one sentence of one stream. A slot's segment is OPEN after a non-final call and closed
+ * after a final call or lvx_pcm_reset. An open slot holds tail[0 .. 320): the last 320 samples of its
+ * previous call's rendering, which were not emitted.
+ *
+ * A call's row is r[0 .. n_in), n_in = 320 (c + Lb): c = ctx_frames in [0, 16] frames that re-render what
+ * the segment has already delivered, then Lb >= 1 new frames; s = 320 c. In this order:
+ *   1. Head. Open slot, c >= 1: emit x[n] = fl(fl(tail[n] wf[n]) + fl(r[s - 320 + n] wr[n])), n = 0 .. 319
+ *      (two rounded products and a rounded sum, no fused multiply-add). Open slot, c = 0: emit tail
+ *      unchanged (plain concatenation at this seam). Closed slot: emit nothing, and c must be 0.
+ *   2. Body. Not final: emit r[s .. n_in - 320). Final: emit r[s .. n_in).
+ *   3. State. Not final: tail = r[n_in - 320 .. n_in), the slot is open. Final: the slot is closed.
+ *   4. Flush (n_in = 0, final, c = 0): an open slot emits tail, a closed one nothing.
+ * Samples emitted: closed, non-final 320 Lb - 320 (0 for a one-frame dump); open, non-final 320 Lb; open,
+ * final 320 Lb + 320; closed, final 320 Lb. A SENTENCE OF T FRAMES DELIVERS EXACTLY 320 T SAMPLES, as
+ * without the join, and a sentence that is one dump delivers the codec's row bit for bit.
+ *
+ * The library keeps, per KV slot, the tail in two device buffers (a launch reads one and writes the other)
+ * and, on the host, a mirror of "open" and of which buffer is current: a slot's calls are issued in order
+ * on one stream. The window table is uploaded once. */
+#define LVX_JOIN_HOLD 320
+#define LVX_JOIN_CONTEXT 16
+/* host only: the fp32 window tables wr[0 .. 320) and wf[0 .. 320). LVX_E_ARG: a null table, cap < 320. */
+int lvx_pcm_join_window(float* wr_host, float* wf_host, int cap);
+/* host only: samples a join call emits for a slot whose segment is open (open != 0) or closed (negative:
+ * LVX_E_ARG for n_in negative or no multiple of 320, ctx_frames outside [0, 16], n_in > 0 with
+ * 320 ctx_frames >= n_in, ctx_frames > 0 on a closed slot, n_in = 0 without final or with ctx_frames != 0) */
+int lvx_pcm_join_emitted(int open, int ctx_frames, int n_in, int final);
+/* lvx_pcm_stretch's conventions: rows b of pcm_dev [B][n_in] f32 (n_in common to the call) continue the
+ * join segments of slots_host[b] with ctx_frames_host[b] frames of context in front; final_host[b] != 0
+ * emits the row to its end and closes the slot; n_in may be 0 with final (flush only). out row b (f32)
+ * starts at out_dev + b * out_stride_bytes; n_out_host[b] = samples written. LVX_E_ARG (and no slot's state
+ * changed): the cases of lvx_pcm_join_emitted for any row, B < 1, a slot out of range or named twice,
+ * out_dev null or out_dev / out_stride_bytes not a multiple of 4, out_stride_bytes smaller than a row's
+ * output. lvx_pcm_reset also closes a slot's join segment. */
+int lvx_pcm_join(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
+                 const int32_t* ctx_frames_host, const uint8_t* final_host, float* out_dev,
+                 long long out_stride_bytes, int32_t* n_out_host, void* stream);
 
 /* ---- WavTokenizer encoder, a context of its own (its weights are not needed for TTS).
  * Replaces WavTokenizer.encode_infer (WavTokenizer/decoder/pretrained.py:185-190 ->

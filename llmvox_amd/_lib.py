@@ -122,6 +122,9 @@ _SIGS = {
     "lvx_pcm_ratio_filter": (_I, [_I, _I, ctypes.POINTER(_I), _P, _I]),
     "lvx_pcm_ratio_emitted": (_I, [_I, _I, ctypes.c_longlong, _I, _I]),
     "lvx_pcm_ratio": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, ctypes.c_longlong, _P, _P]),
+    "lvx_pcm_join_window": (_I, [_P, _P, _I]),
+    "lvx_pcm_join_emitted": (_I, [_I, _I, _I, _I]),
+    "lvx_pcm_join": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, ctypes.c_longlong, _P, _P]),
     "lvx_enc_create": (_I, [_I, ctypes.c_longlong, ctypes.POINTER(_P)]),
     "lvx_enc_set_weight": (_I, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
     "lvx_enc_finalize": (_I, [_P]),

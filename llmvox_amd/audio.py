@@ -5,7 +5,8 @@ here runs on the host and is what the tests and the documentation compare it wit
 control ("PCM time stretch" in the same header: WSOLA on the 24 kHz rows, before the resampler) is stated
 here too: ``stretch_ref``. So is the pitch control ("PCM pitch shift": the integer plan that turns a speed and a
 pitch into a stretch and a resampling ratio L / M, and the resampler of that ratio, between the stretch and the
-rate conversion): ``pitch_plan``, ``ratio_ref``."""
+rate conversion): ``pitch_plan``, ``ratio_ref``. And the join of a sentence's dumps ("PCM dump join": a held-back
+frame crossfaded with the next dump's rendering of it, in front of the other three): ``join_ref``."""
 from __future__ import annotations
 
 import struct
@@ -28,6 +29,8 @@ STRETCH_HISTORY = 1280  # inputs of history a slot keeps between stretch calls
 PITCH_MIN, PITCH_MAX = 50, 200  # pitch_pct of a stream (100: no shift)
 RATIO_MAX = 200         # L and M of a ratio the resampler takes: 1 .. 200, coprime, M <= 4 L and L <= 4 M
 RATIO_HISTORY = 256     # inputs of history a slot keeps between ratio calls
+JOIN_HOLD = 320         # samples the dump join holds back and crossfades (LVX_JOIN_HOLD): one codec frame
+JOIN_CONTEXT = 16       # the most context frames a joined dump is decoded with (LVX_JOIN_CONTEXT)
 
 
 def pitch_plan(speed_pct: int, pitch_pct: int) -> Tuple[int, int, int]:
@@ -55,6 +58,7 @@ class AudioFormat:
     container: str = "raw"
     speed_pct: int = 100  # speaking rate in percent (pitch-preserving time stretch of the PCM; 100: none)
     pitch_pct: int = 100  # pitch in percent (a stretch and a resampling of the PCM, ``pitch_plan``; 100: none)
+    join: bool = False    # click-free dump joins: context frames and a crossfade at every dump boundary (``join_ref``)
 
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
@@ -70,18 +74,20 @@ class AudioFormat:
                 or not PITCH_MIN <= self.pitch_pct <= PITCH_MAX:
             raise ValueError(f"pitch_pct must be an integer in [{PITCH_MIN}, {PITCH_MAX}], got {self.pitch_pct!r}")
         pitch_plan(self.speed_pct, self.pitch_pct)  # (the two together: the stretch they need must exist)
+        if not isinstance(self.join, bool):
+            raise ValueError(f"join must be true or false, got {self.join!r}")
 
     @property
     def is_default(self) -> bool:
         return (self.sample_rate == BASE_RATE and self.encoding == "f32le" and self.container == "raw"
-                and self.speed_pct == 100 and self.pitch_pct == 100)
+                and self.speed_pct == 100 and self.pitch_pct == 100 and not self.join)
 
     @property
     def converts(self) -> bool:
-        """The samples differ from the codec's (another rate, encoding, speed or pitch): the stream needs the
-        device stage."""
+        """The samples differ from the codec's (another rate, encoding, speed or pitch, or joined dumps): the
+        stream needs the device stage."""
         return (self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
-                or self.pitch_pct != 100)
+                or self.pitch_pct != 100 or self.join)
 
     @property
     def stretch_pct(self) -> int:
@@ -339,6 +345,70 @@ def stretch_ref(x, speed_pct: int, windows=None, force_d0: bool = False) -> Tupl
     return y[:total], ds
 
 
+# ---- the dump join's rule (include/llmvox.h, "PCM dump join"), in numpy --------------------------------
+
+def join_window() -> Tuple[np.ndarray, np.ndarray]:
+    """(wr, wf) float32 [320]: the crossfade's rising half-Hann window and its complement, built in double,
+    each rounded once (the library's own: ``lvx_pcm_join_window``)."""
+    n = np.arange(JOIN_HOLD, dtype=np.float64)
+    wr = 0.5 - 0.5 * np.cos(np.pi * (n + 0.5) / JOIN_HOLD)
+    return wr.astype(np.float32), (1.0 - wr).astype(np.float32)
+
+
+def join_emitted(open: bool, ctx_frames: int, n_in: int, final: bool) -> int:
+    """Samples a join call of n_in samples, the first 320 ctx_frames of them context, emits for a slot whose
+    segment is open or closed (``lvx_pcm_join_emitted``). ValueError for a call the rule does not admit."""
+    c = ctx_frames
+    bad = n_in < 0 or n_in % JOIN_HOLD or not 0 <= c <= JOIN_CONTEXT
+    if not bad and n_in == 0:
+        bad = not final or c != 0
+    elif not bad:
+        bad = JOIN_HOLD * c >= n_in or (c > 0 and not open)
+    if bad:
+        raise ValueError(f"not a join call: n_in {n_in}, ctx_frames {c}, final {bool(final)}, "
+                         f"{'open' if open else 'closed'} segment")
+    if n_in == 0:
+        return JOIN_HOLD if open else 0
+    return (JOIN_HOLD if open else 0) + n_in - JOIN_HOLD * c - (0 if final else JOIN_HOLD)
+
+
+def _join_step(tail: Optional[np.ndarray], r: np.ndarray, c: int, final: bool, wr, wf):
+    """One call of the rule for a slot whose tail is ``tail`` (None: closed): (samples emitted float32, the
+    slot's next tail or None). Head, body, state, in the header's order; every product and the sum of the
+    crossfade an fp32 operation."""
+    n_out = join_emitted(tail is not None, c, r.size, final)
+    s = JOIN_HOLD * c
+    parts = []
+    if tail is not None:
+        if c >= 1:
+            with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+                parts.append(tail * wf + r[s - JOIN_HOLD:s] * wr)
+        else:
+            parts.append(tail)
+    if r.size:
+        parts.append(r[s:] if final else r[s:r.size - JOIN_HOLD])
+    out = np.concatenate(parts).astype(np.float32) if parts else np.zeros(0, dtype=np.float32)
+    assert out.size == n_out
+    return out, (None if final else r[r.size - JOIN_HOLD:].copy())
+
+
+def join_ref(rows, ctx_frames, windows=None) -> List[np.ndarray]:
+    """The rule over the calls of one sentence: ``rows[k]`` (float32, 320 (c_k + Lb_k) samples) is the codec's
+    rendering of call k's ``ctx_frames[k]`` context frames followed by its new frames; the last call is the
+    final one (an empty last row: a flush). Returns what each call emits; concatenated, 320 samples per frame
+    of the sentence. ``windows``: (wr, wf) fp32 tables (default: built here; the device tests pass the
+    library's). The bits the device computes (``lvx_pcm_join``)."""
+    wr, wf = windows if windows is not None else join_window()
+    wr, wf = np.asarray(wr, dtype=np.float32), np.asarray(wf, dtype=np.float32)
+    if len(rows) != len(ctx_frames):
+        raise ValueError("one ctx_frames per row")
+    out, tail = [], None
+    for k, (r, c) in enumerate(zip(rows, ctx_frames)):
+        y, tail = _join_step(tail, np.asarray(r, dtype=np.float32).reshape(-1), int(c), k == len(rows) - 1, wr, wf)
+        out.append(y)
+    return out
+
+
 def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None) -> np.ndarray:
     """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, rate and encoding (int16 or
     float32 array): stretched at the plan's stretch_pct, resampled by its L / M, then resampled to the rate and
@@ -353,12 +423,16 @@ def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None) -
 
 class StreamRef:
     """The streaming form of the rule for one slot, on the host: ``push(x, final)`` returns the samples the
-    call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_stretch`` when the plan has a stretch, then
-    ``lvx_pcm_ratio`` when it has a ratio, then ``lvx_pcm_convert``). Keeps the whole segment; for tests and
-    stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
+    call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_join`` when the format joins its dumps, then
+    ``lvx_pcm_stretch`` when the plan has a stretch, then ``lvx_pcm_ratio`` when it has a ratio, then
+    ``lvx_pcm_convert``). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the
+    whole segment; for tests and stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
 
-    def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None):
+    def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, join_windows=None):
         self.fmt, self.taps, self.ratio_taps = fmt, taps, ratio_taps
+        if fmt.join:
+            wr, wf = join_windows if join_windows is not None else join_window()
+            self.join_windows = (np.asarray(wr, dtype=np.float32), np.asarray(wf, dtype=np.float32))
         self.stretch_pct, (self.L, self.M) = fmt.stretch_pct, fmt.ratio
         if self.stretch_pct != 100:
             wr, wf = windows if windows is not None else stretch_window()
@@ -373,6 +447,7 @@ class StreamRef:
         self.raw_t0, self.hops, self.p_prev = 0, 0, -STRETCH_H
         self.mid: List[np.ndarray] = []  # the ratio resampler's view: the stretched segment and its count
         self.mid_t0 = 0
+        self.join_tail: Optional[np.ndarray] = None  # the join's view: the held-back frame (None: closed)
 
     def _ratio(self, x, final: bool) -> np.ndarray:
         m0 = ratio_emitted_upto(self.L, self.M, self.mid_t0, False)
@@ -394,8 +469,12 @@ class StreamRef:
         self.hops = j1
         return y[:max(0, m1 - m0)]
 
-    def push(self, x, final: bool) -> np.ndarray:
+    def push(self, x, final: bool, ctx_frames: int = 0) -> np.ndarray:
         x = np.asarray(x, dtype=np.float32).reshape(-1)
+        if self.fmt.join:
+            x, self.join_tail = _join_step(self.join_tail, x, int(ctx_frames), bool(final), *self.join_windows)
+        elif ctx_frames:
+            raise ValueError("ctx_frames without a joined format")
         if self.stretch_pct != 100:
             x = self._stretch(x, final)
         if self.L != self.M:
@@ -416,4 +495,5 @@ __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "re
            "convert_ref", "StreamRef", "RATES", "ENCODINGS", "CONTAINERS", "BASE_RATE", "HISTORY",
            "stretch_window", "stretch_ref", "stretch_emitted", "stretch_emitted_upto", "SPEED_MIN", "SPEED_MAX",
            "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY", "pitch_plan", "ratio_design", "ratio_emitted",
-           "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY"]
+           "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY",
+           "join_window", "join_emitted", "join_ref", "JOIN_HOLD", "JOIN_CONTEXT"]

@@ -186,6 +186,25 @@ static uint8_t f32_to_e4m3_host(float x) {
   return sign | (uint8_t)code;
 }
 
+// ---- PCM dump join: the window tables and the counts (llmvox.h) ----
+// wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / 320), wf = 1 - wr in double; each table rounded once
+static void join_design(float* wr, float* wf) {
+  const double pi = 3.14159265358979323846;
+  for (int n = 0; n < JOIN_HOLD; ++n) {
+    const double r = 0.5 - 0.5 * std::cos(pi * (n + 0.5) / JOIN_HOLD);
+    wr[n] = (float)r;
+    wf[n] = (float)(1.0 - r);
+  }
+}
+
+// samples a join call emits, -1 where the call is not one the rule admits (llmvox.h: the LVX_E_ARG cases)
+static int join_emitted(bool open, int c, int n_in, bool final) {
+  if (n_in < 0 || n_in % JOIN_HOLD || c < 0 || c > JOIN_CTX) return -1;
+  if (n_in == 0) return (final && c == 0) ? (open ? JOIN_HOLD : 0) : -1;
+  if ((long long)JOIN_HOLD * c >= n_in || (c > 0 && !open)) return -1;
+  return (open ? JOIN_HOLD : 0) + n_in - JOIN_HOLD * c - (final ? 0 : JOIN_HOLD);
+}
+
 // ---- PCM output stage: the rates, their prototype filters and the streaming counts (llmvox.h) ----
 struct PcmRate {
   int rate, L, M, N;
@@ -343,6 +362,12 @@ struct lvx_ctx {
   std::vector<long long> rat_t0;  // inputs of the slot's segment consumed so far
   std::vector<std::pair<int, int>> rat_lm;  // ratio of the slot's open segment, (0, 0): none open
   std::vector<uint8_t> rat_par;   // which of the slot's two history buffers is current
+  // PCM dump join: the device window tables (wr then wf), the slots' tail pool [2][max_streams][JOIN_HOLD]
+  // and the host mirror of every slot's segment (lvx_pcm_join, under mu)
+  float* join_win = nullptr;
+  float* join_tail = nullptr;
+  std::vector<uint8_t> join_open;  // the slot's segment is open: its current tail buffer holds 320 samples not emitted
+  std::vector<uint8_t> join_par;   // which of the slot's two tail buffers is current
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -821,6 +846,16 @@ int lvx_finalize(lvx_ctx* c) {
   c->rat_t0.assign(S, 0);
   c->rat_lm.assign(S, {0, 0});
   c->rat_par.assign(S, 0);
+  // ---- PCM dump join (allocated last: every other buffer stays where it was) ----
+  {
+    float win[2 * JOIN_HOLD];
+    join_design(win, win + JOIN_HOLD);
+    if ((r = c->dalloc(&c->join_win, 2 * JOIN_HOLD)) || (r = c->dalloc(&c->join_tail, (size_t)2 * S * JOIN_HOLD))) return r;
+    HIP_TRY(hipMemcpy(c->join_win, win, sizeof(win), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->join_tail, 0, (size_t)2 * S * JOIN_HOLD * 4));
+    c->join_open.assign(S, 0);
+    c->join_par.assign(S, 0);
+  }
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
   c->finalized = true;
@@ -1349,6 +1384,7 @@ int lvx_pcm_reset(lvx_ctx* c, int slot, void* stream) {
   c->str_pct[slot] = 0;
   c->rat_t0[slot] = 0;
   c->rat_lm[slot] = {0, 0};
+  c->join_open[slot] = 0;
   return LVX_OK;
 }
 
@@ -1625,6 +1661,85 @@ int lvx_pcm_ratio(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* 
     }
     if (!any) continue;  // (a flush with nothing left)
     pcm_launch_ratio(pk, nr, max_out, L, M, N, pcm, n_in, c->rat_taps, c->rat_hist, out, out_stride, (hipStream_t)stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+// ---- PCM dump join ----
+int lvx_pcm_join_window(float* wr_host, float* wf_host, int cap) {
+  if (!wr_host || !wf_host) return fail(LVX_E_ARG, "null wr_host / wf_host");
+  if (cap < JOIN_HOLD) return fail(LVX_E_ARG, "wr_host / wf_host hold fewer than 320 floats");
+  join_design(wr_host, wf_host);
+  return LVX_OK;
+}
+
+static std::string join_msg(bool open, int c, int n_in, bool final) {
+  return "not a join call: n_in " + std::to_string(n_in) + ", ctx_frames " + std::to_string(c) + (final ? ", final" : ", not final") +
+         (open ? ", open segment" : ", closed segment") +
+         " (n_in a multiple of 320; ctx_frames in [0, 16], 320 ctx_frames < n_in, 0 on a closed segment; n_in 0 only as a final "
+         "flush without context)";
+}
+
+int lvx_pcm_join_emitted(int open, int ctx_frames, int n_in, int final) {
+  const int n = join_emitted(open != 0, ctx_frames, n_in, final != 0);
+  if (n < 0) return fail(LVX_E_ARG, join_msg(open != 0, ctx_frames, n_in, final != 0));
+  return n;
+}
+
+int lvx_pcm_join(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const int32_t* ctx_frames,
+                 const uint8_t* final_host, float* out, long long out_stride, int32_t* n_out_host, void* stream) {
+  NEED_FINAL(c);
+  if (B < 1 || n_in < 0 || !slots || !ctx_frames || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
+  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
+  if (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3))
+    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  const int S = c->cfg.max_streams;
+  std::vector<JoinRow> rows(B);
+  {
+    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
+    // every row is checked before any slot's state changes
+    std::vector<uint8_t> seen(S, 0);
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
+      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
+      seen[s] = 1;
+      const bool open = c->join_open[s] != 0, final = final_host[b] != 0;
+      const int cf = ctx_frames[b];
+      const int n_out = join_emitted(open, cf, n_in, final);
+      if (n_out < 0) return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": " + join_msg(open, cf, n_in, final));
+      if ((long long)n_out * 4 > out_stride)
+        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
+                                   std::to_string((long long)n_out * 4) + " bytes)");
+      const int cur = (c->join_par[s] * S + s) * JOIN_HOLD, other = ((1 - c->join_par[s]) * S + s) * JOIN_HOLD;
+      rows[b] = JoinRow{JOIN_HOLD * cf, !open ? JOIN_HEAD_NONE : cf > 0 ? JOIN_HEAD_FADE : JOIN_HEAD_TAIL, n_out, cur,
+                        final ? -1 : other, b};
+    }
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      n_out_host[b] = rows[b].n_out;
+      if (final_host[b]) {
+        c->join_open[s] = 0;
+      } else {
+        c->join_open[s] = 1;
+        c->join_par[s] ^= 1;
+      }
+    }
+  }
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
+    const int nr = std::min(PCM_ROWS, B - b0);
+    JoinRows pk{};
+    int max_out = 0;
+    bool any = false;
+    for (int k = 0; k < nr; ++k) {
+      pk.r[k] = rows[b0 + k];
+      max_out = std::max(max_out, pk.r[k].n_out);
+      any = any || pk.r[k].n_out > 0 || pk.r[k].tail_out >= 0;
+    }
+    if (!any) continue;  // (a flush of closed slots)
+    pcm_launch_join(pk, nr, max_out, pcm, n_in, c->join_win, c->join_tail, out, out_stride, (hipStream_t)stream);
   }
   HIP_TRY(hipGetLastError());
   return LVX_OK;

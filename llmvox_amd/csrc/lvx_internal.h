@@ -322,4 +322,23 @@ void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, cons
                         const float* win, float* hist, int* dstate, float* out, long long out_stride, int* d_out,
                         int d_stride, hipStream_t s);
 
+// ---------------- PCM dump join (pcm_kernels.hip; llmvox.h "PCM dump join") ----------------
+constexpr int JOIN_HOLD = 320;  // samples held back and crossfaded: one codec frame
+constexpr int JOIN_CTX = 16;    // the most context frames of a call
+enum { JOIN_HEAD_NONE = 0, JOIN_HEAD_TAIL = 1, JOIN_HEAD_FADE = 2 };
+struct JoinRow {
+  int s;         // samples of context in front of the row: 320 c
+  int head;      // JOIN_HEAD_*: nothing, the slot's tail as it is, the tail crossfaded with r[s - 320 .. s)
+  int n_out;     // samples of this call: the head's 320 (if any), then r[s .. s + n_out - head's)
+  int tail_in;   // float offset of the slot's current tail [JOIN_HOLD] in the pool
+  int tail_out;  // where r[n_in - 320 .. n_in) goes (the slot's other buffer); -1: none kept
+  int row;       // row of pcm / out
+};
+struct JoinRows {
+  JoinRow r[PCM_ROWS];
+};
+// one launch for n_rows <= PCM_ROWS rows; win: wr [JOIN_HOLD] then wf [JOIN_HOLD]
+void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float* pcm, int n_in, const float* win,
+                     float* tails, float* out, long long out_stride, hipStream_t s);
+
 }  // namespace lvx

@@ -4,6 +4,8 @@
 // And the speaking-rate control in front of it ("PCM time stretch"): WSOLA on the 24 kHz rows, one block
 // per row, launched only for a stream that asked for another speed. And the pitch control between the two
 // ("PCM pitch shift"): the same polyphase rule with a run-time L / M, launched only for a pitched stream.
+// And, in front of all three, the join of a sentence's dumps ("PCM dump join"): a copy that holds back one
+// frame and crossfades it with the next dump's rendering of it, launched only for a stream that asked.
 #include <algorithm>
 
 #include "lvx_internal.h"
@@ -342,7 +344,90 @@ __global__ __launch_bounds__(STR_THREADS) void pcm_stretch_kernel(StretchRows ro
   if (tid == 0) dstate[r.slot] = d;
 }
 
+// ---- PCM dump join (llmvox.h, "PCM dump join"): the crossfaded concatenation of a sentence's dumps ----
+// pcm_convert_kernel's row packet and grid. Output m of row y's call is the head's sample m (the slot's
+// tail, as it is or crossfaded with the row's rendering of the same frame) while m < the head's 320, then
+// r[s + m - head's]: a streaming copy. The head's length, s and n_out are multiples of 4 samples, so a
+// thread's PCM_PER_THREAD outputs lie wholly in the head or wholly in the body and move as one 16-byte
+// load and store where the row's and the output's addresses allow (the tail pool and the window table are
+// 16-byte aligned by construction). Block (0, y) also writes the slot's next tail.
+__device__ __forceinline__ float4 join_fade(float4 t, float4 wf, float4 x, float4 wr) {
+#pragma clang fp contract(off)
+  float4 o;
+  {
+    const float a = t.x * wf.x, b = x.x * wr.x;
+    o.x = a + b;
+  }
+  {
+    const float a = t.y * wf.y, b = x.y * wr.y;
+    o.y = a + b;
+  }
+  {
+    const float a = t.z * wf.z, b = x.z * wr.z;
+    o.z = a + b;
+  }
+  {
+    const float a = t.w * wf.w, b = x.w * wr.w;
+    o.w = a + b;
+  }
+  return o;
+}
+
+__global__ __launch_bounds__(PCM_THREADS) void pcm_join_kernel(JoinRows rows, const float* __restrict__ pcm, int n_in,
+                                                               const float* __restrict__ win, float* tails,
+                                                               unsigned char* __restrict__ out, long long out_stride) {
+  const JoinRow r = rows.r[blockIdx.y];
+  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;  // (never read when n_in == 0: no body, no fade)
+  const int tid = threadIdx.x;
+  const bool xvec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  if (blockIdx.x == 0 && r.tail_out >= 0) {  // the next tail r[n_in - 320 .. n_in), into the buffer no block reads
+    const float* __restrict__ src = x + (n_in - JOIN_HOLD);
+    float* dst = tails + r.tail_out;
+    if (xvec) {
+      if (tid < JOIN_HOLD / 4) reinterpret_cast<float4*>(dst)[tid] = reinterpret_cast<const float4*>(src)[tid];
+    } else {
+      for (int i = tid; i < JOIN_HOLD; i += PCM_THREADS) dst[i] = src[i];
+    }
+  }
+
+  const int mb = blockIdx.x * PCM_OB;
+  if (mb >= r.n_out) return;
+  const int m = mb + tid * PCM_PER_THREAD;  // the thread's first output
+  if (m >= r.n_out) return;                 // (n_out is a multiple of PCM_PER_THREAD: a thread has all or none)
+  const int hl = r.head != JOIN_HEAD_NONE ? JOIN_HOLD : 0;
+  float* o = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride) + m;
+  const bool ovec = (reinterpret_cast<uintptr_t>(o) & 15) == 0;
+  float4 v;
+  if (m < hl) {
+    const float* __restrict__ t = tails + r.tail_in + m;
+    v = *reinterpret_cast<const float4*>(t);
+    if (r.head == JOIN_HEAD_FADE) {
+      const float* __restrict__ xs = x + (r.s - JOIN_HOLD + m);
+      const float4 xv = xvec ? *reinterpret_cast<const float4*>(xs) : make_float4(xs[0], xs[1], xs[2], xs[3]);
+      v = join_fade(v, *reinterpret_cast<const float4*>(win + JOIN_HOLD + m), xv,
+                    *reinterpret_cast<const float4*>(win + m));
+    }
+  } else {
+    const float* __restrict__ xs = x + (r.s + m - hl);
+    v = xvec ? *reinterpret_cast<const float4*>(xs) : make_float4(xs[0], xs[1], xs[2], xs[3]);
+  }
+  if (ovec) {
+    *reinterpret_cast<float4*>(o) = v;
+  } else {
+    o[0] = v.x;
+    o[1] = v.y;
+    o[2] = v.z;
+    o[3] = v.w;
+  }
+}
+
 }  // namespace
+
+void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float* pcm, int n_in, const float* win,
+                     float* tails, float* out, long long out_stride, hipStream_t s) {
+  const dim3 grid((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
+  pcm_join_kernel<<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, win, tails, (unsigned char*)out, out_stride);
+}
 
 void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, const float* pcm, int n_in,
                         const float* win, float* hist, int* dstate, float* out, long long out_stride, int* d_out,

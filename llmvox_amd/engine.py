@@ -6,6 +6,7 @@ returns torch device tensors (torch is only the allocator and the stream provide
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from typing import Dict, Optional
 
 import numpy as np
@@ -381,7 +382,35 @@ class Engine:
                                           cnt, self.stream_handle()))
         return out, list(cnt)
 
-    def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
+    def pcm_join_window(self):
+        """(wr, wf) float32 [320]: the dump join's crossfade tables as the library builds them
+        (lvx_pcm_join_window)."""
+        wr, wf = np.zeros(320, dtype=np.float32), np.zeros(320, dtype=np.float32)
+        _lib.check(self.lib.lvx_pcm_join_window(wr.ctypes.data_as(ctypes.c_void_p),
+                                                wf.ctypes.data_as(ctypes.c_void_p), 320))
+        return wr, wf
+
+    def pcm_join(self, pcm: Optional[torch.Tensor], slots, ctx_frames, finals):
+        """The dump join alone (lvx_pcm_join): rows of ``pcm`` (device float32 [B, n_in] at 24 kHz, n_in a
+        multiple of 320; None or n_in 0: flush only) continue the join segments of ``slots``; the first
+        ``ctx_frames[b]`` frames of row b re-render what its segment has already delivered; a true
+        ``finals[b]`` emits the row to its end and closes the segment. Returns (out, counts): a device float32
+        tensor [B, width] whose row b holds counts[b] samples. Asynchronous on the current stream; a slot's
+        calls must be issued in order on one stream."""
+        slots = [int(s) for s in slots]
+        B = len(slots)
+        pcm, n_in = self._pcm_rows(pcm, B)
+        width = n_in + 320  # (the most a call emits: its row and the held-back frame; rows on 16-byte boundaries)
+        out = torch.empty(B, width, device=self.device, dtype=torch.float32)
+        sl = (ctypes.c_int32 * B)(*slots)
+        cf = (ctypes.c_int32 * B)(*[int(c) for c in ctx_frames])
+        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
+        cnt = (ctypes.c_int32 * B)()
+        _lib.check(self.lib.lvx_pcm_join(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, cf, fl, _ptr(out), width * 4,
+                                         cnt, self.stream_handle()))
+        return out, list(cnt)
+
+    def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt, ctx_frames=None):
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
         ``audio.AudioFormat`` (its speed, pitch, rate and encoding). Returns (out, counts): a device tensor
@@ -389,11 +418,22 @@ class Engine:
         format needs it: the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the
         plan's L / M (lvx_pcm_ratio), the rate and the encoding (lvx_pcm_convert). Rows may leave a stage with
         different counts: they pass the next one grouped by count. A format without a pitch makes the calls it
-        made before there was one. Asynchronous on the current stream; a slot's calls must be issued in order
-        on one stream."""
+        made before there was one. A format with ``join`` passes the dump join first (lvx_pcm_join), row b with
+        ``ctx_frames[b]`` frames of context in front (None: none anywhere); one without makes exactly the calls
+        it made before there was a join. Asynchronous on the current stream; a slot's calls must be issued in
+        order on one stream."""
         stretch_pct, (L, M) = fmt.stretch_pct, fmt.ratio
         plain = fmt.sample_rate == 24000 and fmt.encoding == "f32le"  # the last stage has nothing to do
         dtype = torch.int16 if fmt.encoding == "s16le" else torch.float32
+        if fmt.join:
+            slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
+            jo, cnt = self.pcm_join(pcm, slots, ctx_frames if ctx_frames is not None else [0] * len(slots), finals)
+            rest = dataclasses.replace(fmt, join=False)
+            if stretch_pct == 100 and L == M and plain:
+                return jo, cnt
+            return self._pcm_grouped(jo, cnt, slots, finals, lambda sub, sl, fl: self.pcm_convert(sub, sl, fl, rest), dtype)
+        if ctx_frames is not None and any(ctx_frames):
+            raise ValueError("ctx_frames without a joined format")
 
         def last(sub, sl, fl):
             return self._pcm_resample(sub, sl, fl, fmt)

@@ -377,7 +377,8 @@ def pitch_pct_of(pitch) -> int:
 
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
                encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
-               min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0):
+               min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0,
+               join: bool = False):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -398,19 +399,23 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     spoken) shifts the pitch at the same duration: the PCM is stretched and resampled on the device as
     ``audio.pitch_plan`` says for round(pitch * 100) percent; out of range, or a speed / pitch combination whose
     stretch falls outside 50 .. 200 percent: 422 with the plan's message; the response carries the realised
-    ratio, speed_pct / stretch_pct, in ``X-Audio-Pitch``. The reference's /voicechat,
+    ratio, speed_pct / stretch_pct, in ``X-Audio-Pitch``. ``join`` (true or false; anything else: 422) asks for
+    click-free dump joins: every dump of a sentence after its first is decoded with context frames in front and
+    crossfaded with the one before it on the device (``audio.join_ref``); the sample counts, and so the WAV
+    header, are those of a request without it; the response says which in ``X-Audio-Join`` (0 or 1). The
+    reference's /voicechat,
     /multimodalchat and /vlmschat differ from /tts only in the producer (ASR / multimodal LLM,
     out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import StreamingResponse
-    from pydantic import BaseModel
+    from pydantic import BaseModel, StrictBool
 
     from .audio import AudioFormat
     from .sampling import Sampling
     Sampling(temperature, top_k, 0, top_p, min_p, repetition_penalty, repetition_window)  # (validated at start-up)
     extra_defaults = {"top_p": top_p, "min_p": min_p, "repetition_penalty": repetition_penalty,
                       "repetition_window": repetition_window}
-    default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch))
+    default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join)
 
     class TTSRequest(BaseModel):
         text: str
@@ -426,6 +431,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         container: Optional[str] = None
         speed: Optional[float] = None
         pitch: Optional[float] = None
+        join: Optional[StrictBool] = None
 
     def audio_of(request):
         """The request's AudioFormat (the defaults for the fields it does not name)."""
@@ -434,7 +440,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                default_audio.encoding if request.encoding is None else request.encoding,
                                default_audio.container if request.container is None else request.container,
                                default_audio.speed_pct if request.speed is None else speed_pct_of(request.speed),
-                               default_audio.pitch_pct if request.pitch is None else pitch_pct_of(request.pitch))
+                               default_audio.pitch_pct if request.pitch is None else pitch_pct_of(request.pitch),
+                               default_audio.join if request.join is None else request.join)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -480,7 +487,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         return StreamingResponse(service.chunks(session), media_type=fmt.media_type,
                                  headers={"X-Audio-Sample-Rate": str(fmt.sample_rate), "X-Audio-Encoding": fmt.encoding,
                                           "X-Audio-Speed": f"{fmt.speed_pct / 100:.2f}",
-                                          "X-Audio-Pitch": f"{fmt.speed_pct / fmt.stretch_pct:.4f}"})
+                                          "X-Audio-Pitch": f"{fmt.speed_pct / fmt.stretch_pct:.4f}",
+                                          "X-Audio-Join": "1" if fmt.join else "0"})
 
     @app.get("/health")
     def health():
@@ -526,6 +534,8 @@ def arg_parser():
                     help="speaking rate of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
     ap.add_argument("--pitch", type=float, default=1.0,
                     help="pitch factor of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
+    ap.add_argument("--join", action="store_true",
+                    help="click-free dump joins for requests that do not name `join` (context frames and a crossfade)")
     return ap
 
 
@@ -533,7 +543,8 @@ def app_options(a) -> dict:
     """``create_app``'s keywords from the parsed command line: the defaults of the requests' optional fields."""
     return dict(temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate, encoding=a.encoding,
                 container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
-                repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch)
+                repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch,
+                join=a.join)
 
 
 def main(argv=None):

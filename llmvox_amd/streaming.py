@@ -30,6 +30,7 @@ from typing import Callable, Deque, Dict, List, Optional
 import numpy as np
 
 from . import config as C
+from .audio import JOIN_CONTEXT
 from .streams import side_stream
 
 
@@ -414,6 +415,7 @@ class FusedStream:
         self.segment = 0                 # sentences ended so far: each one draws from a seed of its own
         self.audio = None                # an audio.AudioFormat that converts: the dumps pass the PCM output stage
         self.pcm_open = False            # the sentence has dumps behind it that its filter has not been flushed after
+        self.joined: List[int] = []      # a joined stream: the last tokens of its sentence dumped so far (<= 16)
 
     def feed(self, word):
         self.fed = True
@@ -422,6 +424,16 @@ class FusedStream:
     def _out(self, item):
         self.events.append(item)
         self.sink.put(item)
+
+
+class _JoinedRow(list):
+    """The codec row of a joined stream's dump: ``ctx`` context tokens (the last ones its sentence dumped
+    before), then the dump's own."""
+    ctx = 0
+
+
+def _dump_ctx(toks) -> int:
+    return getattr(toks, "ctx", 0)
 
 
 def _copy_machine(m: SegmentMachine) -> SegmentMachine:
@@ -515,8 +527,8 @@ class _PcmPass:
     """The PCM output-stage calls of one chunk's dumps (streams opened with ``audio``). A slot's calls
     must reach the engine in dump order, whatever order the codec groups are decoded in, and no call may
     name a slot twice: ``run()`` converts, in rounds, every dump that is the next one of its stream and
-    whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch), and leaves the
-    others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
+    whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch, join), and
+    leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
 
     def __init__(self, sched, dumps, finals):
         self.sched, self.dumps, self.finals = sched, dumps, finals
@@ -549,7 +561,7 @@ class _PcmPass:
                     eng.pcm_reset(st.slot)
                     continue
                 buckets.setdefault((id(self.where[i][0]), st.audio.sample_rate, st.audio.encoding,
-                                    st.audio.speed_pct, st.audio.pitch_pct), []).append(i)
+                                    st.audio.speed_pct, st.audio.pitch_pct, st.audio.join), []).append(i)
             if not buckets:
                 return calls
             for idx in buckets.values():
@@ -561,8 +573,10 @@ class _PcmPass:
                     pcm = out[rows[0]:rows[0] + len(rows)]
                 else:
                     pcm = out[rows]
+                audio = self.dumps[idx[0]][0].audio
+                kw = {"ctx_frames": [_dump_ctx(self.dumps[i][1]) for i in idx]} if audio.join else {}
                 o, counts = eng.pcm_convert(pcm, [self.dumps[i][0].slot for i in idx],
-                                            [i in self.finals for i in idx], self.dumps[idx[0]][0].audio)
+                                            [i in self.finals for i in idx], audio, **kw)
                 calls.append((idx, o, counts))
 
 
@@ -659,7 +673,9 @@ class FusedScheduler:
         the stream is converted on the device (``Engine.pcm_convert``), behind its codec call on the same
         stream, each sentence as a signal of its own, and the stream's items are those samples (int16 /
         float32 arrays with ``to_bytes=False``). None (or 24 kHz f32le): today's items, and the engine's
-        ``pcm_*`` are never called."""
+        ``pcm_*`` are never called. A format with ``join``: every dump of a sentence after its first is decoded
+        with context in front, the last min(16, frames of the sentence dumped so far, max_codec_frames - the
+        dump's length) tokens dumped before it (``_join_row``), and the output stage crossfades the seam."""
         if sampling is not None and not sampling.temperature > 0:
             sampling = None
         if sampling is not None and not hasattr(self.engine, "set_sampling"):
@@ -707,6 +723,18 @@ class FusedScheduler:
 
     def _on_ar(self):
         return self.torch.cuda.stream(self.ar_stream) if self.ar_stream is not None else contextlib.nullcontext()
+
+    def _join_row(self, st: FusedStream, tokens: List[int]):
+        """The codec row of a dump of committed tokens: for a joined stream its context tokens in front (none
+        where the engine has no room for them: that seam is then a plain one), and the record of the
+        sentence's dumped tokens moved on; any other stream: the tokens themselves."""
+        if st is None or st.audio is None or not st.audio.join or not tokens:
+            return tokens
+        c = max(0, min(JOIN_CONTEXT, len(st.joined), self.engine.max_codec_frames - len(tokens)))
+        row = _JoinedRow(st.joined[len(st.joined) - c:] + list(tokens))
+        row.ctx = c
+        st.joined = (st.joined + list(tokens))[-JOIN_CONTEXT:]
+        return row
 
     def _steps_to_dump(self, m: SegmentMachine):
         return max(1, m.dump_size - len(m.speech_outputs))
@@ -877,10 +905,11 @@ class FusedScheduler:
             reset = False
             for e in evs:
                 if e.kind == "audio":
-                    dumps.append((st, e.tokens))
+                    dumps.append((st, self._join_row(st, e.tokens)))
                     order[st].append(("audio", len(dumps) - 1))
                 else:
                     order[st].append(("signal", e.signal))
+                    st.joined = []  # (the sentence ends: an end of audio or the max_audio_length reset)
                     reset = True
             if reset:
                 # run-ahead past end-of-audio: drop the rest, restart the slot at position 0
@@ -951,7 +980,8 @@ class FusedScheduler:
         return se
 
     def _groups(self, dumps):
-        """Dump indices batched by length (one codec call per group, within max_codec_frames)."""
+        """Dump indices batched by decoded length, a joined dump's context included (one codec call per group,
+        within max_codec_frames)."""
         by_len: Dict[int, List[int]] = {}
         for i, (_, toks) in enumerate(dumps):
             if toks:  # (no tokens: a flush of the PCM output stage, _mark_finals)
@@ -1054,6 +1084,8 @@ class FusedScheduler:
             if not tokens and not st.pcm_open:
                 return
             st.pcm_open = False
+            dumps[0] = (st, self._join_row(st, tokens))  # (a joined stream: the tail gets its context too)
+            st.joined = []
             if self.deliverer is None:
                 with (self.torch.cuda.stream(self.codec_stream) if self.codec_stream is not None
                       else contextlib.nullcontext()):
