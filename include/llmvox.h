@@ -619,6 +619,67 @@ int lvx_pcm_join(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int3
                  const int32_t* ctx_frames_host, const uint8_t* final_host, float* out_dev,
                  long long out_stride_bytes, int32_t* n_out_host, void* stream);
 
+/* ---- PCM level ----------------------------------------------------------------
+ * The volume control: a gain followed by a peak limiter, because louder speech clips. It runs AFTER the join,
+ * the stretch and the ratio resampler and BEFORE lvx_pcm_convert (rate and encoding), always at the nominal
+ * 24 kHz, so its constants are fixed sample counts. A stream at volume_pct 100 never comes here.
+ *
+ * The limiter has no recursion (no attack / release state carried from sample to sample): every output is a
+ * fixed function of a bounded window of inputs, a sliding minimum (exact in any evaluation order) and ONE
+ * fixed-order fp32 sum. So the device output is bit-identical to a host evaluation of the same order
+ * (llmvox_amd/audio.py: level_ref) and INDEPENDENT OF CHUNKING, like the resamplers and the stretch.
+ *
+ * Constants: A = LVX_LEVEL_A = 120 samples (5 ms), the attack half-window; R = LVX_LEVEL_R = 1200 samples
+ * (50 ms), the hold; c = LVX_LEVEL_CEIL = the fp32 value 0.8912509f (-1 dBFS), the ceiling, which is fixed.
+ * volume_pct is an integer in [0, 400], 100 neutral; G = (float)((double)volume_pct / 100.0), once, on the host.
+ * Window, built on the host in double, each tap rounded once to fp32 (lvx_pcm_level_window):
+ *   w[k] = (0.5 + 0.5 cos(pi k / (A + 1))) / (A + 1),  k = -A .. A  (241 taps; their sum is 1).
+ *
+ * One segment is one sentence of one stream: x[0 .. T), x = 0 outside. All arithmetic is fp32; every product,
+ * sum and quotient is rounded, no fused multiply-add, IEEE division.
+ *   1. v[i] = fl(G x[i]).
+ *   2. r[i] = fl(c / |v[i]|) if |v[i]| > c, else 1. (A NaN compares false: r = 1 and the NaN passes through;
+ *      an infinity gives r = 0.)
+ *   3. m[i] = min of r[k] over k in [i - R, i + A]: exact, however it is evaluated.
+ *   4. d[i] = fl(1 - m[i]);  S[n]: acc = 0, then for k = -A .. A ascending acc = fl(acc + fl(d[n + k] w[k]));
+ *      s[n] = fl(1 - S[n]).
+ *   5. g[n] = max(0, min(s[n], r[n])). (Every m[n + k] with |k| <= A covers n, because R >= A, so s is at most
+ *      r[n] up to rounding; the clamp makes that exact.)
+ *   6. y[n] = fl(v[n] g[n]),  n = 0 .. T - 1: one output per input.
+ * Ceiling: |y[n]| <= c (1 + 2^-22) for finite input. Transparency: if no |v| exceeds c in
+ * [n - 2 A - R, n + 2 A], every d of the sum is exactly 0, so g[n] = 1 exactly and y[n] = v[n] bit for bit.
+ * Dependence: output n depends on x[n - 2 A - R .. n + 2 A] only. THE CONCATENATED OUTPUTS OF ANY CHUNKING OF A
+ * SEGMENT ARE BIT-IDENTICAL TO ITS ONE-SHOT OUTPUT, and bit-identical to audio.level_ref.
+ * The rate conversion that follows can overshoot the ceiling slightly; the s16le quantiser still clamps.
+ *
+ * Streaming. After a non-final call that brings the consumed input to T the emitted outputs are the
+ * n < max(0, T - 2 A); a final call emits up to T: a stream holds back 240 samples (10 ms) until its
+ * sentence's final call. The first output of a call reaches back 3 A + R = 1560 inputs before the call's first
+ * input, so the library keeps, per KV slot, the last 1600 raw inputs x of the previous call (two buffers per
+ * slot: a launch reads one and writes the other) and, on the host, a mirror of the slot's consumed count and
+ * volume_pct: a slot's calls are issued in order on one stream. A segment has one volume: another before its
+ * final call is LVX_E_ARG. */
+#define LVX_LEVEL_A 120
+#define LVX_LEVEL_R 1200
+#define LVX_LEVEL_CEIL 0.8912509f
+/* host only: the 241 fp32 taps w[-120 .. 120]. LVX_E_ARG: a null table, cap < 241. */
+int lvx_pcm_level_window(float* w_host, int cap);
+/* host only: samples a level call emits for a slot that has consumed t0 inputs of its segment (volume_pct
+ * 100: n_in; negative: LVX_E_ARG for volume_pct outside [0, 400], t0 < 0 or n_in < 0) */
+int lvx_pcm_level_emitted(int volume_pct, long long t0, int n_in, int final);
+/* lvx_pcm_ratio's conventions: rows b of pcm_dev [B][n_in] f32 continue the level segments of slots_host[b];
+ * final_host[b] != 0 emits the rest and resets the slot; n_in may be 0 with final (flush only). out row b (f32)
+ * starts at out_dev + b * out_stride_bytes; n_out_host[b] = samples written. g_out_dev (optional test hook, may
+ * be NULL): row b's g[n] of the samples this call emits, f32 at g_out_dev + b * g_stride_bytes. volume_pct 100:
+ * nothing is launched and nothing written, the rows of pcm_dev are the output (n_out_host[b] = n_in; out_dev
+ * may be NULL). LVX_E_ARG (and no slot's state changed): volume_pct outside [0, 400] or another than the slot's
+ * open segment has, B < 1, n_in < 0, a slot out of range or named twice, out_dev / out_stride_bytes (and
+ * g_out_dev / g_stride_bytes when given) not a multiple of 4 or a stride smaller than a row's output.
+ * lvx_pcm_reset also forgets a slot's level state. */
+int lvx_pcm_level(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
+                  const uint8_t* final_host, int volume_pct, float* out_dev, long long out_stride_bytes,
+                  int32_t* n_out_host, float* g_out_dev, long long g_stride_bytes, void* stream);
+
 /* ---- WavTokenizer encoder, a context of its own (its weights are not needed for TTS).
  * Replaces WavTokenizer.encode_infer (WavTokenizer/decoder/pretrained.py:185-190 ->
  * decoder/feature_extractors.py:122-133): SEANet encoder (encoder/modules/seanet.py:94-143) + the

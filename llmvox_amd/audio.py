@@ -6,7 +6,9 @@ control ("PCM time stretch" in the same header: WSOLA on the 24 kHz rows, before
 here too: ``stretch_ref``. So is the pitch control ("PCM pitch shift": the integer plan that turns a speed and a
 pitch into a stretch and a resampling ratio L / M, and the resampler of that ratio, between the stretch and the
 rate conversion): ``pitch_plan``, ``ratio_ref``. And the join of a sentence's dumps ("PCM dump join": a held-back
-frame crossfaded with the next dump's rendering of it, in front of the other three): ``join_ref``."""
+frame crossfaded with the next dump's rendering of it, in front of the other three): ``join_ref``. And the volume
+control ("PCM level": a gain and a feed-forward peak limiter, between the ratio and the rate conversion):
+``level_ref``."""
 from __future__ import annotations
 
 import struct
@@ -31,6 +33,11 @@ RATIO_MAX = 200         # L and M of a ratio the resampler takes: 1 .. 200, copr
 RATIO_HISTORY = 256     # inputs of history a slot keeps between ratio calls
 JOIN_HOLD = 320         # samples the dump join holds back and crossfades (LVX_JOIN_HOLD): one codec frame
 JOIN_CONTEXT = 16       # the most context frames a joined dump is decoded with (LVX_JOIN_CONTEXT)
+VOLUME_MIN, VOLUME_MAX = 0, 400  # volume_pct of a stream (100: no level stage)
+LEVEL_A = 120           # the limiter's attack half-window in samples (LVX_LEVEL_A): 5 ms
+LEVEL_R = 1200          # its hold (LVX_LEVEL_R): 50 ms
+LEVEL_CEIL = np.float32(0.8912509)  # its ceiling c (LVX_LEVEL_CEIL): -1 dBFS
+LEVEL_HISTORY = 1600    # inputs of history a slot keeps between level calls
 
 
 def pitch_plan(speed_pct: int, pitch_pct: int) -> Tuple[int, int, int]:
@@ -59,6 +66,7 @@ class AudioFormat:
     speed_pct: int = 100  # speaking rate in percent (pitch-preserving time stretch of the PCM; 100: none)
     pitch_pct: int = 100  # pitch in percent (a stretch and a resampling of the PCM, ``pitch_plan``; 100: none)
     join: bool = False    # click-free dump joins: context frames and a crossfade at every dump boundary (``join_ref``)
+    volume_pct: int = 100  # volume in percent (a gain and a peak limiter on the PCM, ``level_ref``; 100: none)
 
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
@@ -76,18 +84,21 @@ class AudioFormat:
         pitch_plan(self.speed_pct, self.pitch_pct)  # (the two together: the stretch they need must exist)
         if not isinstance(self.join, bool):
             raise ValueError(f"join must be true or false, got {self.join!r}")
+        if isinstance(self.volume_pct, bool) or not isinstance(self.volume_pct, int) \
+                or not VOLUME_MIN <= self.volume_pct <= VOLUME_MAX:
+            raise ValueError(f"volume_pct must be an integer in [{VOLUME_MIN}, {VOLUME_MAX}], got {self.volume_pct!r}")
 
     @property
     def is_default(self) -> bool:
         return (self.sample_rate == BASE_RATE and self.encoding == "f32le" and self.container == "raw"
-                and self.speed_pct == 100 and self.pitch_pct == 100 and not self.join)
+                and self.speed_pct == 100 and self.pitch_pct == 100 and not self.join and self.volume_pct == 100)
 
     @property
     def converts(self) -> bool:
-        """The samples differ from the codec's (another rate, encoding, speed or pitch, or joined dumps): the
-        stream needs the device stage."""
+        """The samples differ from the codec's (another rate, encoding, speed, pitch or volume, or joined dumps):
+        the stream needs the device stage."""
         return (self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
-                or self.pitch_pct != 100 or self.join)
+                or self.pitch_pct != 100 or self.join or self.volume_pct != 100)
 
     @property
     def stretch_pct(self) -> int:
@@ -409,15 +420,95 @@ def join_ref(rows, ctx_frames, windows=None) -> List[np.ndarray]:
     return out
 
 
-def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None) -> np.ndarray:
-    """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, rate and encoding (int16 or
-    float32 array): stretched at the plan's stretch_pct, resampled by its L / M, then resampled to the rate and
-    encoded. ``ratio_taps``: the fp32 table of the format's ratio (default: designed here)."""
+# ---- the volume control's rule (include/llmvox.h, "PCM level"), in numpy --------------------------------
+
+def _check_volume(volume_pct) -> int:
+    if isinstance(volume_pct, bool) or not isinstance(volume_pct, (int, np.integer)) \
+            or not VOLUME_MIN <= volume_pct <= VOLUME_MAX:
+        raise ValueError(f"volume_pct must be an integer in [{VOLUME_MIN}, {VOLUME_MAX}], got {volume_pct!r}")
+    return int(volume_pct)
+
+
+def level_window() -> np.ndarray:
+    """w float32 [2 A + 1]: the limiter's smoothing window w[k] = (0.5 + 0.5 cos(pi k / (A + 1))) / (A + 1),
+    k = -A .. A, built in double, each tap rounded once (the library's own: ``lvx_pcm_level_window``)."""
+    k = np.arange(-LEVEL_A, LEVEL_A + 1, dtype=np.float64)
+    return ((0.5 + 0.5 * np.cos(np.pi * k / (LEVEL_A + 1))) / (LEVEL_A + 1)).astype(np.float32)
+
+
+def level_emitted_upto(volume_pct: int, T: int, final: bool) -> int:
+    """Samples of a segment the level stage has emitted once T inputs are consumed (after a non-final / a
+    final call): the last 2 A wait for their right-hand inputs. volume_pct 100 is no stage: T."""
+    if volume_pct == 100 or final:
+        return T
+    return max(0, T - 2 * LEVEL_A)
+
+
+def level_emitted(volume_pct: int, t0: int, n_in: int, final: bool) -> int:
+    """Samples a level call emits for a slot that has consumed t0 inputs of its segment
+    (``lvx_pcm_level_emitted``)."""
+    _check_volume(volume_pct)
+    if t0 < 0 or n_in < 0:
+        raise ValueError("t0 and n_in must be >= 0")
+    return level_emitted_upto(volume_pct, t0 + n_in, final) - level_emitted_upto(volume_pct, t0, False)
+
+
+def level_ref(x, volume_pct: int, window=None, n0: int = 0, n1: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """Outputs n0 .. n1 - 1 (default: all T) of the segment x[0 .. T) (float32 at 24 kHz, zero outside) at
+    ``volume_pct``: (samples float32, the gains g[n] float32). The gain G = volume_pct / 100, then the
+    feed-forward limiter, every product, quotient and sum an fp32 operation in the rule's order (the 241-term
+    sum k ascending, no fused multiply-add): the bits the device computes (``lvx_pcm_level``) with the same
+    fp32 window. ``window``: the fp32 table (default: built here; the device tests pass the library's).
+    volume_pct 100 is evaluated like any other (the service never sends such a stream here)."""
+    pct = _check_volume(volume_pct)
+    A, R, c = LEVEL_A, LEVEL_R, LEVEL_CEIL
+    x = np.asarray(x, dtype=np.float32)
+    T = x.shape[-1]
+    if n1 is None:
+        n1 = T
+    n = max(0, n1 - n0)
+    w = level_window() if window is None else np.asarray(window, dtype=np.float32)
+    if w.shape != (2 * A + 1,):
+        raise ValueError(f"the window has {2 * A + 1} taps")
+    lead = x.shape[:-1]
+    if n == 0:
+        return np.zeros(lead + (0,), dtype=np.float32), np.zeros(lead + (0,), dtype=np.float32)
+    lo, hi = n0 - 2 * A - R, n1 + 2 * A  # r over [n0 - A - R, hi) is what the outputs read; the rest is slack
+    xs = np.zeros(lead + (hi - lo,), dtype=np.float32)
+    a, b = max(lo, 0), min(hi, T)
+    if b > a:
+        xs[..., a - lo:b - lo] = x[..., a:b]
+    G = np.float32(pct / 100.0)
+    one = np.float32(1.0)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
+        v = G * xs
+        av = np.abs(v)
+        r = np.where(av > c, c / np.where(av > c, av, one), one).astype(np.float32)
+        # m[i] = min r[i - R .. i + A] for i in [n0 - A, n1 + A): the window that starts at r's index i - R - lo
+        m = np.lib.stride_tricks.sliding_window_view(r[..., A:], R + A + 1, axis=-1).min(axis=-1)
+        d = one - m  # [n + 2 A]: d[j] is the segment's d[n0 - A + j]
+        acc = np.zeros(lead + (n,), dtype=np.float32)
+        for k in range(2 * A + 1):  # k ascending: acc = fl(acc + fl(d[n + k] w[k]))
+            acc = acc + d[..., k:k + n] * w[k]
+        s = one - acc
+        rn = r[..., 2 * A + R:2 * A + R + n]
+        g = np.maximum(np.float32(0.0), np.minimum(s, rn)).astype(np.float32)
+        y = (v[..., 2 * A + R:2 * A + R + n] * g).astype(np.float32)
+    return y, g
+
+
+def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, level_win=None) -> np.ndarray:
+    """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, volume, rate and encoding (int16 or
+    float32 array): stretched at the plan's stretch_pct, resampled by its L / M, levelled at its volume_pct, then
+    resampled to the rate and encoded. ``ratio_taps``: the fp32 table of the format's ratio (default: designed
+    here); ``level_win``: the level stage's fp32 window (default: built here)."""
     stretch, (L, M) = fmt.stretch_pct, fmt.ratio
     if stretch != 100:
         x = stretch_ref(x, stretch, windows)[0]
     if L != M:
         x = ratio_ref(x, L, M, ratio_taps)
+    if fmt.volume_pct != 100:
+        x = level_ref(x, fmt.volume_pct, level_win)[0]
     return encode_ref(resample_ref(x, fmt.sample_rate, taps), fmt)
 
 
@@ -425,11 +516,13 @@ class StreamRef:
     """The streaming form of the rule for one slot, on the host: ``push(x, final)`` returns the samples the
     call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_join`` when the format joins its dumps, then
     ``lvx_pcm_stretch`` when the plan has a stretch, then ``lvx_pcm_ratio`` when it has a ratio, then
-    ``lvx_pcm_convert``). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the
+    ``lvx_pcm_level`` when it has a volume, then ``lvx_pcm_convert``). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the
     whole segment; for tests and stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
 
-    def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, join_windows=None):
+    def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, join_windows=None, level_win=None):
         self.fmt, self.taps, self.ratio_taps = fmt, taps, ratio_taps
+        if fmt.volume_pct != 100:
+            self.level_win = level_window() if level_win is None else np.asarray(level_win, dtype=np.float32)
         if fmt.join:
             wr, wf = join_windows if join_windows is not None else join_window()
             self.join_windows = (np.asarray(wr, dtype=np.float32), np.asarray(wf, dtype=np.float32))
@@ -448,6 +541,8 @@ class StreamRef:
         self.mid: List[np.ndarray] = []  # the ratio resampler's view: the stretched segment and its count
         self.mid_t0 = 0
         self.join_tail: Optional[np.ndarray] = None  # the join's view: the held-back frame (None: closed)
+        self.lvl: List[np.ndarray] = []  # the level stage's view: the resampled segment and its count
+        self.lvl_t0 = 0
 
     def _ratio(self, x, final: bool) -> np.ndarray:
         m0 = ratio_emitted_upto(self.L, self.M, self.mid_t0, False)
@@ -455,6 +550,14 @@ class StreamRef:
         self.mid.append(x)
         self.mid_t0 += x.size
         return ratio_ref(np.concatenate(self.mid), self.L, self.M, self.ratio_taps, m0, m1)
+
+    def _level(self, x, final: bool) -> np.ndarray:
+        pct = self.fmt.volume_pct
+        n0 = level_emitted_upto(pct, self.lvl_t0, False)
+        n1 = level_emitted_upto(pct, self.lvl_t0 + x.size, final)
+        self.lvl.append(x)
+        self.lvl_t0 += x.size
+        return level_ref(np.concatenate(self.lvl), pct, self.level_win, n0, n1)[0]
 
     def _stretch(self, x, final: bool) -> np.ndarray:
         pct = self.stretch_pct
@@ -479,6 +582,8 @@ class StreamRef:
             x = self._stretch(x, final)
         if self.L != self.M:
             x = self._ratio(x, final)
+        if self.fmt.volume_pct != 100:
+            x = self._level(x, final)
         rate = self.fmt.sample_rate
         m0 = emitted_upto(rate, self.t0, False)
         m1 = emitted_upto(rate, self.t0 + x.size, final)
@@ -496,4 +601,6 @@ __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "re
            "stretch_window", "stretch_ref", "stretch_emitted", "stretch_emitted_upto", "SPEED_MIN", "SPEED_MAX",
            "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY", "pitch_plan", "ratio_design", "ratio_emitted",
            "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY",
-           "join_window", "join_emitted", "join_ref", "JOIN_HOLD", "JOIN_CONTEXT"]
+           "join_window", "join_emitted", "join_ref", "JOIN_HOLD", "JOIN_CONTEXT",
+           "level_window", "level_emitted", "level_emitted_upto", "level_ref", "VOLUME_MIN", "VOLUME_MAX",
+           "LEVEL_A", "LEVEL_R", "LEVEL_CEIL", "LEVEL_HISTORY"]

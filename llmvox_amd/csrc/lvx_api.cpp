@@ -310,6 +310,19 @@ static long long stretch_emitted_upto(int pct, long long T, bool final) {
   return STR_H * stretch_hops(pct, T);
 }
 
+// ---- PCM level: the window table and the streaming counts (llmvox.h) ----
+// w[k] = (0.5 + 0.5 cos(pi k / (A + 1))) / (A + 1), k = -A .. A, in double, each tap rounded to fp32 once
+static void level_design(float* w) {
+  const double pi = 3.14159265358979323846;
+  for (int k = -LVL_A; k <= LVL_A; ++k) w[k + LVL_A] = (float)((0.5 + 0.5 * std::cos(pi * k / (LVL_A + 1))) / (LVL_A + 1));
+}
+
+// samples of a segment emitted once T inputs are consumed: the last 2 A wait for their right-hand inputs
+static long long level_emitted_upto(int pct, long long T, bool final) {
+  if (pct == 100 || final) return T;
+  return std::max(0ll, T - 2 * LVL_A);
+}
+
 // the second record of ArState::smp for a slot that asks for none of the extended controls: top_p 1, min_p 0 (lnminp -inf),
 // repetition_penalty 1.0f, repetition_window 64
 static const uint4 kSamplingNeutral{1u << 24, 0xff800000u, 0x3f800000u, 64u};
@@ -368,6 +381,13 @@ struct lvx_ctx {
   float* join_tail = nullptr;
   std::vector<uint8_t> join_open;  // the slot's segment is open: its current tail buffer holds 320 samples not emitted
   std::vector<uint8_t> join_par;   // which of the slot's two tail buffers is current
+  // PCM level: the device window table w[-A .. A], the slots' pool of raw-input histories
+  // [2][max_streams][LVL_HIST] and the host mirror of every slot's segment (lvx_pcm_level, under mu)
+  float* lvl_win = nullptr;
+  float* lvl_hist = nullptr;
+  std::vector<long long> lvl_t0;  // inputs of the slot's segment consumed so far
+  std::vector<int> lvl_pct;       // volume of the slot's open segment, -1: none open (0 is a volume)
+  std::vector<uint8_t> lvl_par;   // which of the slot's two history buffers is current
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -855,6 +875,17 @@ int lvx_finalize(lvx_ctx* c) {
     HIP_TRY(hipMemset(c->join_tail, 0, (size_t)2 * S * JOIN_HOLD * 4));
     c->join_open.assign(S, 0);
     c->join_par.assign(S, 0);
+  }
+  // ---- PCM level (allocated last: every other buffer stays where it was) ----
+  {
+    float win[LVL_TAPS];
+    level_design(win);
+    if ((r = c->dalloc(&c->lvl_win, LVL_TAPS)) || (r = c->dalloc(&c->lvl_hist, (size_t)2 * S * LVL_HIST))) return r;
+    HIP_TRY(hipMemcpy(c->lvl_win, win, sizeof(win), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->lvl_hist, 0, (size_t)2 * S * LVL_HIST * 4));
+    c->lvl_t0.assign(S, 0);
+    c->lvl_pct.assign(S, -1);
+    c->lvl_par.assign(S, 0);
   }
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
@@ -1385,6 +1416,8 @@ int lvx_pcm_reset(lvx_ctx* c, int slot, void* stream) {
   c->rat_t0[slot] = 0;
   c->rat_lm[slot] = {0, 0};
   c->join_open[slot] = 0;
+  c->lvl_t0[slot] = 0;
+  c->lvl_pct[slot] = -1;
   return LVX_OK;
 }
 
@@ -1740,6 +1773,97 @@ int lvx_pcm_join(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* s
     }
     if (!any) continue;  // (a flush of closed slots)
     pcm_launch_join(pk, nr, max_out, pcm, n_in, c->join_win, c->join_tail, out, out_stride, (hipStream_t)stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+// ---- PCM level ----
+int lvx_pcm_level_window(float* w_host, int cap) {
+  if (!w_host) return fail(LVX_E_ARG, "null w_host");
+  if (cap < LVL_TAPS) return fail(LVX_E_ARG, "w_host holds fewer than 241 floats");
+  level_design(w_host);
+  return LVX_OK;
+}
+
+int lvx_pcm_level_emitted(int volume_pct, long long t0, int n_in, int final) {
+  if (volume_pct < 0 || volume_pct > 400) return fail(LVX_E_ARG, "volume_pct must be in [0, 400]");
+  if (t0 < 0 || n_in < 0) return fail(LVX_E_ARG, "t0 and n_in must be >= 0");
+  return (int)(level_emitted_upto(volume_pct, t0 + n_in, final != 0) - level_emitted_upto(volume_pct, t0, false));
+}
+
+int lvx_pcm_level(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const uint8_t* final_host,
+                  int volume_pct, float* out, long long out_stride, int32_t* n_out_host, float* g_out, long long g_stride,
+                  void* stream) {
+  NEED_FINAL(c);
+  if (volume_pct < 0 || volume_pct > 400) return fail(LVX_E_ARG, "volume_pct must be in [0, 400], got " + std::to_string(volume_pct));
+  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
+  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
+  const bool launch = volume_pct != 100;  // 100: the rows of pcm_dev are the output
+  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
+    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  if (launch && g_out && ((reinterpret_cast<uintptr_t>(g_out) & 3) || g_stride < 0 || (g_stride & 3)))
+    return fail(LVX_E_ARG, "g_out_dev and g_stride_bytes must be multiples of 4");
+  const int S = c->cfg.max_streams;
+  std::vector<PcmRow> rows(B);
+  {
+    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
+    // every row is checked before any slot's state changes
+    std::vector<uint8_t> seen(S, 0);
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
+      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
+      seen[s] = 1;
+      if (c->lvl_pct[s] >= 0 && c->lvl_pct[s] != volume_pct)
+        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at volume_pct " + std::to_string(c->lvl_pct[s]));
+      if (!launch) {
+        rows[b] = PcmRow{0, 0, n_in, 0, -1, b};
+        continue;
+      }
+      const long long t0 = c->lvl_t0[s];
+      const long long m0 = level_emitted_upto(volume_pct, t0, false);
+      const long long m1 = level_emitted_upto(volume_pct, t0 + n_in, final_host[b] != 0);
+      if (m1 - m0 > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
+      if ((m1 - m0) * 4 > out_stride)
+        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
+                                   std::to_string((m1 - m0) * 4) + " bytes)");
+      if (g_out && (m1 - m0) * 4 > g_stride)
+        return fail(LVX_E_ARG, "g_stride_bytes " + std::to_string(g_stride) + " is smaller than a row's output (" +
+                                   std::to_string((m1 - m0) * 4) + " bytes)");
+      const int cur = (c->lvl_par[s] * S + s) * LVL_HIST, other = ((1 - c->lvl_par[s]) * S + s) * LVL_HIST;
+      const bool keep = n_in > 0 && !final_host[b];  // a history for the segment's next call
+      rows[b] = PcmRow{t0, m0, (int)(m1 - m0), cur, keep ? other : -1, b};
+    }
+    for (int b = 0; b < B; ++b) {
+      const int s = slots[b];
+      n_out_host[b] = rows[b].n_out;
+      if (final_host[b]) {
+        c->lvl_t0[s] = 0;
+        c->lvl_pct[s] = -1;
+      } else if (launch) {
+        c->lvl_t0[s] += n_in;
+        c->lvl_pct[s] = volume_pct;
+        if (rows[b].hist_out >= 0) c->lvl_par[s] ^= 1;
+      }
+    }
+  }
+  if (!launch) return LVX_OK;
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  const float gain = (float)((double)volume_pct / 100.0);
+  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
+    const int nr = std::min(PCM_ROWS, B - b0);
+    PcmRows pk{};
+    int max_out = 0;
+    bool any = false;
+    for (int k = 0; k < nr; ++k) {
+      pk.r[k] = rows[b0 + k];
+      max_out = std::max(max_out, pk.r[k].n_out);
+      any = any || pk.r[k].n_out > 0 || pk.r[k].hist_out >= 0;
+    }
+    if (!any) continue;  // (a flush with nothing left)
+    pcm_launch_level(pk, nr, max_out, gain, pcm, n_in, c->lvl_win, c->lvl_hist, out, out_stride, g_out, g_stride,
+                     (hipStream_t)stream);
   }
   HIP_TRY(hipGetLastError());
   return LVX_OK;

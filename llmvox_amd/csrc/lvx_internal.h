@@ -341,4 +341,17 @@ struct JoinRows {
 void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float* pcm, int n_in, const float* win,
                      float* tails, float* out, long long out_stride, hipStream_t s);
 
+// ---------------- PCM level (pcm_kernels.hip; llmvox.h "PCM level") ----------------
+constexpr int LVL_A = LVX_LEVEL_A;   // attack half-window
+constexpr int LVL_R = LVX_LEVEL_R;   // hold
+constexpr int LVL_TAPS = 2 * LVL_A + 1;
+constexpr int LVL_HIST = 1600;       // raw inputs of history a slot keeps between calls (an output reaches back <= 3 A + R = 1560)
+// The rows travel as PcmRows: t0 the inputs consumed before the call, m0 the outputs emitted before it (the index
+// of the call's first output: max(0, t0 - 2 A)), hist_in / hist_out float offsets of [LVL_HIST] buffers.
+// one launch for n_rows <= PCM_ROWS rows; gain: G; win: w[-A .. A]; g_out (optional): row b's g[n] at
+// g_out + b * g_stride bytes
+void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, const float* pcm, int n_in,
+                      const float* win, float* hist, float* out, long long out_stride, float* g_out, long long g_stride,
+                      hipStream_t s);
+
 }  // namespace lvx

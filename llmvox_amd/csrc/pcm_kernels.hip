@@ -6,6 +6,9 @@
 // ("PCM pitch shift"): the same polyphase rule with a run-time L / M, launched only for a pitched stream.
 // And, in front of all three, the join of a sentence's dumps ("PCM dump join"): a copy that holds back one
 // frame and crossfades it with the next dump's rendering of it, launched only for a stream that asked.
+// And the volume control between the pitch control and the rate conversion ("PCM level"): a gain and a
+// feed-forward peak limiter (a sliding minimum and one fixed-order sum), launched only for a stream at
+// another volume than 100.
 #include <algorithm>
 
 #include "lvx_internal.h"
@@ -421,7 +424,145 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_join_kernel(JoinRows rows, co
   }
 }
 
+// ---- PCM level (llmvox.h, "PCM level"): a gain and a feed-forward peak limiter ----
+// pcm_convert_kernel's row packet and grid. A block of PCM_OB outputs n0 .. n0 + PCM_OB - 1 stages
+// r[n0 - A - R .. n0 + PCM_OB + 2 A) into LDS (LVL_SPAN values, from the slot's history of raw inputs and the
+// call's row, zeros outside the segment), forms the LVL_D sliding minima m[n0 - A .. n0 + PCM_OB + A) of window
+// R + A + 1 by doubling (min over 2 k from two minima over k, ten passes between two LDS buffers, then two
+// overlapping windows of 1024: a minimum is exact in any order) and keeps d = 1 - m. Each thread then runs the
+// 241-term sum for its four consecutive outputs: d comes as aligned 16-byte LDS reads that slide through
+// registers (a thread's four-float stride would make every 4-byte read a 4-way bank conflict), the window
+// word is a broadcast.
+constexpr int LVL_SPAN = PCM_OB + 3 * LVL_A + LVL_R;  // 2584
+constexpr int LVL_D = PCM_OB + 2 * LVL_A;             // 1264
+constexpr int LVL_WIN = LVL_R + LVL_A + 1;            // 1321: inputs of one sliding minimum
+constexpr int LVL_POW = 1024;                         // the largest power of two <= LVL_WIN
+static_assert(LVL_POW <= LVL_WIN && 2 * LVL_POW >= LVL_WIN, "two windows of LVL_POW cover the sliding minimum's");
+static_assert(LVL_D + LVL_WIN - 1 == LVL_SPAN, "the last minimum ends at the span's last value");
+static_assert(LVL_A % PCM_PER_THREAD == 0 && LVL_D == PCM_PER_THREAD * (PCM_THREADS + 2 * LVL_A / PCM_PER_THREAD),
+              "a thread's last 16-byte read of d ends at the array's end");
+static_assert(3 * LVL_A + LVL_R <= LVL_HIST, "the history covers what a call's first output reaches back");
+
+__device__ __forceinline__ float level_r(float v) {
+  const float a = fabsf(v);
+  return a > LVX_LEVEL_CEIL ? __fdiv_rn(LVX_LEVEL_CEIL, a) : 1.f;  // (a NaN compares false: 1)
+}
+
+__global__ __launch_bounds__(PCM_THREADS) void pcm_level_kernel(PcmRows rows, float gain, const float* __restrict__ pcm,
+                                                                int n_in, const float* __restrict__ win, float* hist,
+                                                                unsigned char* __restrict__ out, long long out_stride,
+                                                                unsigned char* __restrict__ g_out, long long g_stride) {
+  const PcmRow r = rows.r[blockIdx.y];
+  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
+  const int tid = threadIdx.x;
+  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
+  // segment input g (t0 - LVL_HIST <= g < t1) from the call's row or the slot's history; zero outside the segment
+  auto input = [&](long long g) -> float {
+    if (g < 0 || g >= t1) return 0.f;
+    if (g >= r.t0) return x[g - r.t0];
+    const long long back = r.t0 - g;
+    return back <= LVL_HIST ? hist[r.hist_in + LVL_HIST - back] : 0.f;
+  };
+  if (blockIdx.x == 0 && r.hist_out >= 0)
+    for (int i = tid; i < LVL_HIST; i += PCM_THREADS) hist[r.hist_out + i] = input(t1 - LVL_HIST + i);
+
+  const int mb = blockIdx.x * PCM_OB;
+  if (mb >= r.n_out) return;
+  const int nb = min(PCM_OB, r.n_out - mb);
+  const int ml = tid * PCM_PER_THREAD;  // the thread's first output within the block
+  const long long n_first = r.m0 + mb;  // the block's first output in the segment
+
+  __shared__ __attribute__((aligned(16))) float s_a[LVL_SPAN];
+  __shared__ __attribute__((aligned(16))) float s_b[LVL_SPAN];
+  __shared__ __attribute__((aligned(16))) float s_w[LVL_TAPS + 3];
+  if (tid < LVL_TAPS) s_w[tid] = win[tid];
+  const long long i0 = n_first - LVL_A - LVL_R;  // the segment index of s_a[0]
+  for (int k = tid; k < LVL_SPAN; k += PCM_THREADS) s_a[k] = level_r(__fmul_rn(gain, input(i0 + k)));
+  __syncthreads();
+  // dst[i] = min of src over [i, i + 2 k) from src's minima over [i, i + k), wherever that lies within the span
+  // (the entries past it keep a shorter minimum and are not read below)
+  auto twice = [&](const float* src, float* dst, int k) {
+    for (int i = tid; i < LVL_SPAN; i += PCM_THREADS) {
+      const float a = src[i];
+      dst[i] = i + k < LVL_SPAN ? fminf(a, src[i + k]) : a;
+    }
+    __syncthreads();
+  };
+  for (int k = 1; k < LVL_POW; k <<= 2) {  // ten passes: s_a holds the minima over [i, i + 1024) at the end
+    twice(s_a, s_b, k);
+    twice(s_b, s_a, 2 * k);
+  }
+  // d[j] = 1 - min r over [j, j + LVL_WIN): the segment's d[n_first - A + j], j < LVL_D
+  for (int j = tid; j < LVL_D; j += PCM_THREADS) s_b[j] = __fsub_rn(1.f, fminf(s_a[j], s_a[j + LVL_WIN - LVL_POW]));
+  __syncthreads();
+
+  float acc[PCM_PER_THREAD] = {0.f, 0.f, 0.f, 0.f};
+  {
+    // k ascending, each product and each sum rounded to fp32 (no fused multiply-add): the rule's order
+#pragma clang fp contract(off)
+    const float4* __restrict__ d4 = reinterpret_cast<const float4*>(s_b) + tid;  // d[ml + 4 j ..]
+    float4 cur = d4[0];
+    for (int j = 0; j < 2 * LVL_A / 4; ++j) {
+      const float4 nxt = d4[j + 1];
+      const float q[7] = {cur.x, cur.y, cur.z, cur.w, nxt.x, nxt.y, nxt.z};
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const float w = s_w[4 * j + kk];
+#pragma unroll
+        for (int e = 0; e < PCM_PER_THREAD; ++e) {
+          const float prod = q[kk + e] * w;
+          acc[e] = acc[e] + prod;
+        }
+      }
+      cur = nxt;
+    }
+    const float w = s_w[2 * LVL_A];  // the last tap, k = A
+    const float q[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+    for (int e = 0; e < PCM_PER_THREAD; ++e) {
+      const float prod = q[e] * w;
+      acc[e] = acc[e] + prod;
+    }
+  }
+  float y[PCM_PER_THREAD], gg[PCM_PER_THREAD];
+#pragma unroll
+  for (int e = 0; e < PCM_PER_THREAD; ++e) {
+    const float v = __fmul_rn(gain, ml + e < nb ? input(n_first + ml + e) : 0.f);
+    const float s = __fsub_rn(1.f, acc[e]);
+    gg[e] = fmaxf(0.f, fminf(s, level_r(v)));
+    y[e] = __fmul_rn(v, gg[e]);
+  }
+
+  const bool full = ml + PCM_PER_THREAD <= nb;
+  float* o = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride) + mb + ml;
+  if (full && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+    *reinterpret_cast<float4*>(o) = make_float4(y[0], y[1], y[2], y[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < PCM_PER_THREAD; ++e)
+      if (ml + e < nb) o[e] = y[e];
+  }
+  if (g_out) {
+    float* go = reinterpret_cast<float*>(g_out + (size_t)r.row * (size_t)g_stride) + mb + ml;
+    if (full && (reinterpret_cast<uintptr_t>(go) & 15) == 0) {
+      *reinterpret_cast<float4*>(go) = make_float4(gg[0], gg[1], gg[2], gg[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < PCM_PER_THREAD; ++e)
+        if (ml + e < nb) go[e] = gg[e];
+    }
+  }
+}
+
 }  // namespace
+
+void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, const float* pcm, int n_in,
+                      const float* win, float* hist, float* out, long long out_stride, float* g_out, long long g_stride,
+                      hipStream_t s) {
+  const dim3 grid((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
+  pcm_level_kernel<<<grid, PCM_THREADS, 0, s>>>(rows, gain, pcm, n_in, win, hist, (unsigned char*)out, out_stride,
+                                                (unsigned char*)g_out, g_stride);
+}
 
 void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float* pcm, int n_in, const float* win,
                      float* tails, float* out, long long out_stride, hipStream_t s) {

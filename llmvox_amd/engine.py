@@ -410,26 +410,62 @@ class Engine:
                                          cnt, self.stream_handle()))
         return out, list(cnt)
 
+    def pcm_level_window(self):
+        """w float32 [241]: the level stage's smoothing window as the library builds it (lvx_pcm_level_window)."""
+        w = np.zeros(241, dtype=np.float32)
+        _lib.check(self.lib.lvx_pcm_level_window(w.ctypes.data_as(ctypes.c_void_p), w.size))
+        return w
+
+    def pcm_level(self, pcm: Optional[torch.Tensor], slots, finals, volume_pct: int, want_g: bool = False):
+        """The volume control alone (lvx_pcm_level): rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or
+        n_in 0: flush only) continue the level segments of ``slots`` at ``volume_pct`` (a gain of volume_pct / 100
+        and the peak limiter); a true ``finals[b]`` emits the held-back 240 samples too and ends row b's segment.
+        Returns (out, counts, g): a device float32 tensor [B, width] whose row b holds counts[b] samples, and
+        (``want_g``) a device float32 tensor whose row b holds the limiter's gain of each (else None). volume_pct
+        100: the rows themselves. Asynchronous on the current stream; a slot's calls must be issued in order on
+        one stream."""
+        slots = [int(s) for s in slots]
+        B = len(slots)
+        pcm, n_in = self._pcm_rows(pcm, B)
+        volume_pct = int(volume_pct)
+        out = g = None
+        width = 0
+        if volume_pct == 100:
+            out = pcm if pcm is not None else torch.empty(B, 0, device=self.device, dtype=torch.float32)
+        elif 0 <= volume_pct <= 400:
+            width = (n_in + 240 + 7) // 8 * 8  # (the call's inputs and the held-back 240; rows on 16-byte boundaries)
+            out = torch.empty(B, width, device=self.device, dtype=torch.float32)
+            if want_g:
+                g = torch.zeros(B, width, device=self.device, dtype=torch.float32)
+        sl = (ctypes.c_int32 * B)(*slots)
+        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
+        cnt = (ctypes.c_int32 * B)()
+        _lib.check(self.lib.lvx_pcm_level(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, volume_pct, _ptr(out),
+                                          width * 4, cnt, _ptr(g), width * 4, self.stream_handle()))
+        return out, list(cnt), g
+
     def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt, ctx_frames=None):
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
-        ``audio.AudioFormat`` (its speed, pitch, rate and encoding). Returns (out, counts): a device tensor
-        [B, width] of int16 or float32 whose row b holds counts[b] samples. Three stages, each only where the
+        ``audio.AudioFormat`` (its speed, pitch, volume, rate and encoding). Returns (out, counts): a device tensor
+        [B, width] of int16 or float32 whose row b holds counts[b] samples. Four stages, each only where the
         format needs it: the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the
-        plan's L / M (lvx_pcm_ratio), the rate and the encoding (lvx_pcm_convert). Rows may leave a stage with
+        plan's L / M (lvx_pcm_ratio), the gain and limiter at volume_pct (lvx_pcm_level; a format at 100 makes
+        exactly the calls it made before there was one), the rate and the encoding (lvx_pcm_convert). Rows may leave a stage with
         different counts: they pass the next one grouped by count. A format without a pitch makes the calls it
         made before there was one. A format with ``join`` passes the dump join first (lvx_pcm_join), row b with
         ``ctx_frames[b]`` frames of context in front (None: none anywhere); one without makes exactly the calls
         it made before there was a join. Asynchronous on the current stream; a slot's calls must be issued in
         order on one stream."""
         stretch_pct, (L, M) = fmt.stretch_pct, fmt.ratio
+        vol = fmt.volume_pct
         plain = fmt.sample_rate == 24000 and fmt.encoding == "f32le"  # the last stage has nothing to do
         dtype = torch.int16 if fmt.encoding == "s16le" else torch.float32
         if fmt.join:
             slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
             jo, cnt = self.pcm_join(pcm, slots, ctx_frames if ctx_frames is not None else [0] * len(slots), finals)
             rest = dataclasses.replace(fmt, join=False)
-            if stretch_pct == 100 and L == M and plain:
+            if stretch_pct == 100 and L == M and vol == 100 and plain:
                 return jo, cnt
             return self._pcm_grouped(jo, cnt, slots, finals, lambda sub, sl, fl: self.pcm_convert(sub, sl, fl, rest), dtype)
         if ctx_frames is not None and any(ctx_frames):
@@ -438,17 +474,23 @@ class Engine:
         def last(sub, sl, fl):
             return self._pcm_resample(sub, sl, fl, fmt)
 
+        def level(sub, sl, fl):
+            if vol == 100:
+                return last(sub, sl, fl)
+            o, c, _ = self.pcm_level(sub, sl, fl, vol)
+            return (o, c) if plain else self._pcm_grouped(o, c, sl, fl, last, dtype)
+
         def ratio(sub, sl, fl):
             if L == M:
-                return last(sub, sl, fl)
+                return level(sub, sl, fl)
             o, c = self.pcm_ratio(sub, sl, fl, L, M)
-            return (o, c) if plain else self._pcm_grouped(o, c, sl, fl, last, dtype)
+            return (o, c) if plain and vol == 100 else self._pcm_grouped(o, c, sl, fl, level, dtype)
 
         if stretch_pct == 100:
             return ratio(pcm, slots, finals)
         slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
         st, cnt, _ = self.pcm_stretch(pcm, slots, finals, stretch_pct)
-        if L == M and plain:
+        if L == M and vol == 100 and plain:
             return st, cnt
         return self._pcm_grouped(st, cnt, slots, finals, ratio, dtype)
 

@@ -43,7 +43,7 @@ import math
 import os
 import threading
 from queue import Queue
-from typing import List, Optional
+from typing import List, Optional, Union
 
 from . import config as C
 from .streaming import FusedScheduler, audio_chunks, route_text
@@ -375,10 +375,21 @@ def pitch_pct_of(pitch) -> int:
     return pct
 
 
+def volume_pct_of(volume) -> int:
+    """A volume factor (a float in 0.0 .. 4.0) as the integer percentage the level stage takes
+    (``audio.AudioFormat.volume_pct``); ValueError for anything else."""
+    if isinstance(volume, bool) or not isinstance(volume, (int, float)) or not math.isfinite(volume):
+        raise ValueError(f"volume must be a number in 0.0 .. 4.0, got {volume!r}")
+    pct = int(round(volume * 100))
+    if not 0 <= pct <= 400:
+        raise ValueError(f"volume must be in 0.0 .. 4.0, got {volume!r}")
+    return pct
+
+
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
                encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
                min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0,
-               join: bool = False):
+               join: bool = False, volume: float = 1.0):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -402,20 +413,23 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     ratio, speed_pct / stretch_pct, in ``X-Audio-Pitch``. ``join`` (true or false; anything else: 422) asks for
     click-free dump joins: every dump of a sentence after its first is decoded with context frames in front and
     crossfaded with the one before it on the device (``audio.join_ref``); the sample counts, and so the WAV
-    header, are those of a request without it; the response says which in ``X-Audio-Join`` (0 or 1). The
-    reference's /voicechat,
-    /multimodalchat and /vlmschat differ from /tts only in the producer (ASR / multimodal LLM,
-    out of scope): their speech path is this one."""
+    header, are those of a request without it; the response says which in ``X-Audio-Join`` (0 or 1). ``volume``
+    (a float in 0.0 .. 4.0; 1.0: as spoken; a bool, a non-number, a non-finite or an out-of-range value: 422) is the
+    loudness: the PCM is multiplied by round(volume * 100) percent and peak-limited at -1 dBFS on the device
+    (``audio.level_ref``), which holds back 10 ms of every sentence until its end; the response carries it in
+    ``X-Audio-Volume``. The reference's /voicechat, /multimodalchat and /vlmschat differ from /tts only in the
+    producer (ASR / multimodal LLM, out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import StreamingResponse
-    from pydantic import BaseModel, StrictBool
+    from pydantic import BaseModel, StrictBool, StrictFloat, StrictInt
 
     from .audio import AudioFormat
     from .sampling import Sampling
     Sampling(temperature, top_k, 0, top_p, min_p, repetition_penalty, repetition_window)  # (validated at start-up)
     extra_defaults = {"top_p": top_p, "min_p": min_p, "repetition_penalty": repetition_penalty,
                       "repetition_window": repetition_window}
-    default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join)
+    default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join,
+                                volume_pct_of(volume))
 
     class TTSRequest(BaseModel):
         text: str
@@ -432,6 +446,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         speed: Optional[float] = None
         pitch: Optional[float] = None
         join: Optional[StrictBool] = None
+        volume: Optional[Union[StrictInt, StrictFloat]] = None  # (strict: true / false are not numbers here)
 
     def audio_of(request):
         """The request's AudioFormat (the defaults for the fields it does not name)."""
@@ -441,7 +456,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                default_audio.container if request.container is None else request.container,
                                default_audio.speed_pct if request.speed is None else speed_pct_of(request.speed),
                                default_audio.pitch_pct if request.pitch is None else pitch_pct_of(request.pitch),
-                               default_audio.join if request.join is None else request.join)
+                               default_audio.join if request.join is None else request.join,
+                               default_audio.volume_pct if request.volume is None else volume_pct_of(request.volume))
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -488,7 +504,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                  headers={"X-Audio-Sample-Rate": str(fmt.sample_rate), "X-Audio-Encoding": fmt.encoding,
                                           "X-Audio-Speed": f"{fmt.speed_pct / 100:.2f}",
                                           "X-Audio-Pitch": f"{fmt.speed_pct / fmt.stretch_pct:.4f}",
-                                          "X-Audio-Join": "1" if fmt.join else "0"})
+                                          "X-Audio-Join": "1" if fmt.join else "0",
+                                          "X-Audio-Volume": f"{fmt.volume_pct / 100:.2f}"})
 
     @app.get("/health")
     def health():
@@ -534,6 +551,8 @@ def arg_parser():
                     help="speaking rate of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
     ap.add_argument("--pitch", type=float, default=1.0,
                     help="pitch factor of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
+    ap.add_argument("--volume", type=float, default=1.0,
+                    help="volume factor of requests that name none (0.0 .. 4.0; 1.0: as spoken; peak-limited at -1 dBFS)")
     ap.add_argument("--join", action="store_true",
                     help="click-free dump joins for requests that do not name `join` (context frames and a crossfade)")
     return ap
@@ -544,7 +563,7 @@ def app_options(a) -> dict:
     return dict(temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate, encoding=a.encoding,
                 container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
                 repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch,
-                join=a.join)
+                join=a.join, volume=a.volume)
 
 
 def main(argv=None):

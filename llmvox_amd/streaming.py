@@ -527,7 +527,7 @@ class _PcmPass:
     """The PCM output-stage calls of one chunk's dumps (streams opened with ``audio``). A slot's calls
     must reach the engine in dump order, whatever order the codec groups are decoded in, and no call may
     name a slot twice: ``run()`` converts, in rounds, every dump that is the next one of its stream and
-    whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch, join), and
+    whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch, join, volume), and
     leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
 
     def __init__(self, sched, dumps, finals):
@@ -561,7 +561,8 @@ class _PcmPass:
                     eng.pcm_reset(st.slot)
                     continue
                 buckets.setdefault((id(self.where[i][0]), st.audio.sample_rate, st.audio.encoding,
-                                    st.audio.speed_pct, st.audio.pitch_pct, st.audio.join), []).append(i)
+                                    st.audio.speed_pct, st.audio.pitch_pct, st.audio.join, st.audio.volume_pct),
+                                   []).append(i)
             if not buckets:
                 return calls
             for idx in buckets.values():
@@ -669,8 +670,8 @@ class FusedScheduler:
         """sampling: a ``sampling.Sampling`` (temperature > 0) makes the stream draw its tokens, every
         sentence from ``segment_seed(seed, index, sentence)``; None (or temperature 0): greedy, and the
         engine's ``set_sampling`` is never called.
-        audio: an ``audio.AudioFormat`` with another speed, pitch, rate or encoding than f32le at 24 kHz as spoken: every dump of
-        the stream is converted on the device (``Engine.pcm_convert``), behind its codec call on the same
+        audio: an ``audio.AudioFormat`` with another speed, pitch, volume, rate or encoding than f32le at 24 kHz as
+        spoken: every dump of the stream is converted on the device (``Engine.pcm_convert``), behind its codec call on the same
         stream, each sentence as a signal of its own, and the stream's items are those samples (int16 /
         float32 arrays with ``to_bytes=False``). None (or 24 kHz f32le): today's items, and the engine's
         ``pcm_*`` are never called. A format with ``join``: every dump of a sentence after its first is decoded
