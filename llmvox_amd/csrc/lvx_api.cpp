@@ -186,143 +186,6 @@ static uint8_t f32_to_e4m3_host(float x) {
   return sign | (uint8_t)code;
 }
 
-// ---- PCM dump join: the window tables and the counts (llmvox.h) ----
-// wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / 320), wf = 1 - wr in double; each table rounded once
-static void join_design(float* wr, float* wf) {
-  const double pi = 3.14159265358979323846;
-  for (int n = 0; n < JOIN_HOLD; ++n) {
-    const double r = 0.5 - 0.5 * std::cos(pi * (n + 0.5) / JOIN_HOLD);
-    wr[n] = (float)r;
-    wf[n] = (float)(1.0 - r);
-  }
-}
-
-// samples a join call emits, -1 where the call is not one the rule admits (llmvox.h: the LVX_E_ARG cases)
-static int join_emitted(bool open, int c, int n_in, bool final) {
-  if (n_in < 0 || n_in % JOIN_HOLD || c < 0 || c > JOIN_CTX) return -1;
-  if (n_in == 0) return (final && c == 0) ? (open ? JOIN_HOLD : 0) : -1;
-  if ((long long)JOIN_HOLD * c >= n_in || (c > 0 && !open)) return -1;
-  return (open ? JOIN_HOLD : 0) + n_in - JOIN_HOLD * c - (final ? 0 : JOIN_HOLD);
-}
-
-// ---- PCM output stage: the rates, their prototype filters and the streaming counts (llmvox.h) ----
-struct PcmRate {
-  int rate, L, M, N;
-  int tap_off;  // float offset of the rate's taps in lvx_ctx::pcm_taps
-};
-static const PcmRate kPcmRates[] = {{16000, 2, 3, 72, 0}, {8000, 1, 3, 72, 145}, {48000, 2, 1, 48, 290}};
-static const PcmRate kPcmNoFilter = {24000, 1, 1, 0, 0};
-
-static const PcmRate* pcm_rate_of(int sample_rate) {
-  if (sample_rate == 24000) return &kPcmNoFilter;
-  for (const PcmRate& pr : kPcmRates)
-    if (pr.rate == sample_rate) return &pr;
-  return nullptr;
-}
-
-static double bessel_i0(double x) {  // the power series: sum ((x / 2)^k / k!)^2
-  double sum = 1.0, term = 1.0;
-  const double q = x * x / 4.0;
-  for (int k = 1; k < 200; ++k) {
-    term *= q / ((double)k * k);
-    sum += term;
-    if (term < 1e-17 * sum) break;
-  }
-  return sum;
-}
-
-// h[n] = L 2 fc sinc(2 fc n) kaiser(2 N + 1, 9.0)[n + N], n = -N .. N, designed in double, stored as fp32:
-// the three fixed rates and every ratio of the pitch control (llmvox.h, "PCM pitch shift")
-static std::vector<float> pcm_design(int L, int M, int N) {
-  if (N == 0) return {1.f};
-  const double lo = std::min(1.0, (double)L / M), fc = 0.5 * lo * 0.85 / L, beta = 9.0, pi = 3.14159265358979323846;
-  std::vector<float> h(2 * N + 1);
-  for (int n = -N; n <= N; ++n) {
-    const double a = 2.0 * fc * n, sinc = n == 0 ? 1.0 : std::sin(pi * a) / (pi * a);
-    const double u = (double)n / N;
-    const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / bessel_i0(beta);
-    h[n + N] = (float)(L * 2.0 * fc * sinc * w);
-  }
-  return h;
-}
-static std::vector<float> pcm_design(const PcmRate& pr) { return pcm_design(pr.L, pr.M, pr.N); }
-
-// outputs of a segment emitted once T inputs are consumed
-static long long pcm_emitted_upto(int L, int M, int N, long long T, bool final) {
-  const long long all = (T * L + M - 1) / M;  // ceil(T L / M)
-  if (final || N == 0) return all;
-  const long long a = (T - 1) * L - N;
-  return a < 0 ? 0 : std::min(a / M + 1, all);
-}
-static long long pcm_emitted_upto(const PcmRate& pr, long long T, bool final) {
-  return pcm_emitted_upto(pr.L, pr.M, pr.N, T, final);
-}
-
-// ---- PCM pitch shift: the plan and the ratios the resampler takes (llmvox.h) ----
-static int gcd_of(int a, int b) {
-  while (b) {
-    const int t = a % b;
-    a = b;
-    b = t;
-  }
-  return a;
-}
-// coprime 1 <= L, M <= 200 with M <= 4 L and L <= 4 M
-static bool ratio_ok(int L, int M) {
-  return L >= 1 && M >= 1 && L <= RAT_MAX && M <= RAT_MAX && M <= 4 * L && L <= 4 * M && gcd_of(L, M) == 1;
-}
-static int ratio_N(int L, int M) { return L == M ? 0 : 24 * std::max(L, M); }  // (coprime: L == M is 1 / 1, the identity)
-static std::string ratio_msg(int L, int M) {
-  return "L / M must be coprime, each in 1 .. 200, with M <= 4 L and L <= 4 M, got " + std::to_string(L) + " / " + std::to_string(M);
-}
-
-// ---- PCM time stretch: the window tables and the streaming counts (llmvox.h) ----
-// wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / H), wf[n] = 1 - wr[n] (in double), each rounded to fp32 once
-static void stretch_design(float* wr, float* wf) {
-  const double pi = 3.14159265358979323846;
-  for (int n = 0; n < STR_H; ++n) {
-    const double r = 0.5 - 0.5 * std::cos(pi * (n + 0.5) / STR_H);
-    wr[n] = (float)r;
-    wf[n] = (float)(1.0 - r);
-  }
-}
-
-static long long stretch_a(long long j, int pct) { return (j * STR_H * pct) / 100; }
-
-// inputs of the segment hop j reads: the exclusive upper end of its search and its output
-static long long stretch_need(long long j, int pct) {
-  if (j == 0) return 2 * STR_H;
-  return std::max(stretch_a(j, pct) + STR_D + 2 * STR_H, stretch_a(j - 1, pct) + STR_D + 3 * STR_H);
-}
-
-// how many hops j have need_j <= T (need_j does not decrease with j)
-static long long stretch_hops(int pct, long long T) {
-  long long n = std::max(0ll, (T - 3 * STR_H) * 100 / ((long long)STR_H * pct)) + 2;
-  while (n > 0 && stretch_need(n - 1, pct) > T) --n;
-  while (stretch_need(n, pct) <= T) ++n;
-  return n;
-}
-
-// samples of a segment emitted once T inputs are consumed
-static long long stretch_emitted_upto(int pct, long long T, bool final) {
-  if (pct == 100) return T;
-  if (final) return (T * 100 + pct - 1) / pct;
-  return STR_H * stretch_hops(pct, T);
-}
-
-// ---- PCM level: the window table and the streaming counts (llmvox.h) ----
-// w[k] = (0.5 + 0.5 cos(pi k / (A + 1))) / (A + 1), k = -A .. A, in double, each tap rounded to fp32 once
-static void level_design(float* w) {
-  const double pi = 3.14159265358979323846;
-  for (int k = -LVL_A; k <= LVL_A; ++k) w[k + LVL_A] = (float)((0.5 + 0.5 * std::cos(pi * k / (LVL_A + 1))) / (LVL_A + 1));
-}
-
-// samples of a segment emitted once T inputs are consumed: the last 2 A wait for their right-hand inputs
-static long long level_emitted_upto(int pct, long long T, bool final) {
-  if (pct == 100 || final) return T;
-  return std::max(0ll, T - 2 * LVL_A);
-}
-
 // the second record of ArState::smp for a slot that asks for none of the extended controls: top_p 1, min_p 0 (lnminp -inf),
 // repetition_penalty 1.0f, repetition_window 64
 static const uint4 kSamplingNeutral{1u << 24, 0xff800000u, 0x3f800000u, 64u};
@@ -347,47 +210,26 @@ struct lvx_ctx {
   hipStream_t own_capture_stream = nullptr;  // created for null-stream callers only (cached_graph)
   std::vector<float> smp_temp;  // host mirror of the slots' temperatures (lvx_stream_sampling, under mu)
   int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
-  // PCM output stage: the device taps of the three resampling rates, the slots' history pool
-  // [2][max_streams][PCM_HIST] and the host mirror of every slot's segment (lvx_pcm_convert, under mu)
-  float* pcm_taps = nullptr;
+  // The PCM stages (pcm_host.h: the skeleton of their calls). Each has its device tables, a pool of two buffers per
+  // slot [2][max_streams][*_HIST] and, in seg (under mu), the host mirror of every slot's segment.
+  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_STAGES };
+  std::vector<PcmSeg> seg[SEG_STAGES];
+  float* pcm_taps = nullptr;  // rate and encoding: the taps of the three resampling rates
   float* pcm_hist = nullptr;
-  std::vector<long long> pcm_t0;  // inputs of the slot's segment consumed so far
-  std::vector<int> pcm_rate;      // rate of the slot's open segment, 0: none open
-  std::vector<uint8_t> pcm_par;   // which of the slot's two history buffers is current
-  // PCM time stretch: the device window tables (wr then wf), the slots' history pool
-  // [2][max_streams][STR_HIST], their d_{j-1} (one int per slot, device only) and the host mirror of every
-  // slot's segment (lvx_pcm_stretch, under mu)
-  float* str_win = nullptr;
+  float* str_win = nullptr;  // time stretch: the window tables (wr then wf)
   float* str_hist = nullptr;
-  int* str_d = nullptr;
-  std::vector<long long> str_t0;  // inputs of the slot's segment consumed so far
-  std::vector<long long> str_hops;  // hops of it emitted so far
-  std::vector<int> str_pct;       // speed of the slot's open segment, 0: none open
-  std::vector<uint8_t> str_par;   // which of the slot's two history buffers is current
-  // PCM pitch shift: every slot's device table region [max_streams][RAT_TAPS_STRIDE] and the ratio it holds,
-  // the slots' history pool [2][max_streams][RAT_HIST], the host cache of the designed tables (never
-  // evicted: a stream-ordered copy may still read an entry) and the host mirror of every slot's segment
-  // (lvx_pcm_ratio, under mu)
+  int* str_d = nullptr;      // the slots' d_{j-1} (one int per slot, device only)
+  // pitch shift: every slot's table region [max_streams][RAT_TAPS_STRIDE] and the ratio it holds (it outlives the
+  // segment and lvx_pcm_reset), and the host cache of the designed tables (never evicted: a stream-ordered copy may
+  // still read an entry)
   float* rat_taps = nullptr;
   float* rat_hist = nullptr;
   std::map<std::pair<int, int>, std::vector<float>> rat_cache;
   std::vector<std::pair<int, int>> rat_tab;  // (L, M) of the table in the slot's region, (0, 0): none
-  std::vector<long long> rat_t0;  // inputs of the slot's segment consumed so far
-  std::vector<std::pair<int, int>> rat_lm;  // ratio of the slot's open segment, (0, 0): none open
-  std::vector<uint8_t> rat_par;   // which of the slot's two history buffers is current
-  // PCM dump join: the device window tables (wr then wf), the slots' tail pool [2][max_streams][JOIN_HOLD]
-  // and the host mirror of every slot's segment (lvx_pcm_join, under mu)
-  float* join_win = nullptr;
-  float* join_tail = nullptr;
-  std::vector<uint8_t> join_open;  // the slot's segment is open: its current tail buffer holds 320 samples not emitted
-  std::vector<uint8_t> join_par;   // which of the slot's two tail buffers is current
-  // PCM level: the device window table w[-A .. A], the slots' pool of raw-input histories
-  // [2][max_streams][LVL_HIST] and the host mirror of every slot's segment (lvx_pcm_level, under mu)
-  float* lvl_win = nullptr;
-  float* lvl_hist = nullptr;
-  std::vector<long long> lvl_t0;  // inputs of the slot's segment consumed so far
-  std::vector<int> lvl_pct;       // volume of the slot's open segment, -1: none open (0 is a volume)
-  std::vector<uint8_t> lvl_par;   // which of the slot's two history buffers is current
+  float* join_win = nullptr;  // dump join: the window tables (wr then wf)
+  float* join_tail = nullptr;  // an open segment's current buffer holds the 320 samples not emitted yet
+  float* lvl_win = nullptr;  // level: the window table w[-A .. A]
+  float* lvl_hist = nullptr;  // (raw inputs)
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -523,6 +365,26 @@ static std::vector<float> pack_frag32(const std::vector<float>& w, int N, int K)
       for (int l = 0; l < 64; ++l)
         for (int e = 0; e < 4; ++e) o[q++] = w[(size_t)(16 * t + l % 16) * K + 16 * j + 4 * (l / 16) + e];
   return o;
+}
+
+// ---- the PCM stages' entries (below) ----
+// The arguments every stage's entry takes (arrays: the host arrays, null if one is missing); out_dev only where the
+// call launches. Then the entry runs pcm_host.h's skeleton: pcm_plan under mu (the mirror only: released before the
+// launches), pcm_launches behind it.
+static int pcm_args(int B, int n_in, const void* pcm, const void* arrays, bool launch, const void* out, long long out_stride) {
+  if (B < 1 || n_in < 0 || !arrays) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
+  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
+  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
+    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  return LVX_OK;
+}
+
+template <class Rows, class Row, class Launch>
+static int pcm_launches(lvx_ctx* c, const std::vector<Row>& rows, Launch launch) {
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  pcm_chunks<Rows>(rows, launch);
+  HIP_TRY(hipGetLastError());
+  return LVX_OK;
 }
 
 extern "C" {
@@ -837,9 +699,6 @@ int lvx_finalize(lvx_ctx* c) {
     if ((r = c->dalloc(&c->pcm_taps, taps.size())) || (r = c->dalloc(&c->pcm_hist, (size_t)2 * S * PCM_HIST))) return r;
     HIP_TRY(hipMemcpy(c->pcm_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->pcm_hist, 0, (size_t)2 * S * PCM_HIST * 4));
-    c->pcm_t0.assign(S, 0);
-    c->pcm_rate.assign(S, 0);
-    c->pcm_par.assign(S, 0);
     float win[2 * STR_H];
     stretch_design(win, win + STR_H);
     if ((r = c->dalloc(&c->str_win, 2 * STR_H)) || (r = c->dalloc(&c->str_hist, (size_t)2 * S * STR_HIST)) ||
@@ -848,10 +707,6 @@ int lvx_finalize(lvx_ctx* c) {
     HIP_TRY(hipMemcpy(c->str_win, win, sizeof(win), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->str_hist, 0, (size_t)2 * S * STR_HIST * 4));
     HIP_TRY(hipMemset(c->str_d, 0, (size_t)S * 4));
-    c->str_t0.assign(S, 0);
-    c->str_hops.assign(S, 0);
-    c->str_pct.assign(S, 0);
-    c->str_par.assign(S, 0);
   }
   // ---- the slots' token history (S * P * 2 bytes; allocated last: every other buffer stays where it was) ----
   if ((r = c->dalloc(&st.hist, (size_t)S * P)) || (r = c->dalloc(&st.hist_from, S))) return r;
@@ -863,9 +718,6 @@ int lvx_finalize(lvx_ctx* c) {
   HIP_TRY(hipMemset(c->rat_taps, 0, (size_t)S * RAT_TAPS_STRIDE * 4));
   HIP_TRY(hipMemset(c->rat_hist, 0, (size_t)2 * S * RAT_HIST * 4));
   c->rat_tab.assign(S, {0, 0});
-  c->rat_t0.assign(S, 0);
-  c->rat_lm.assign(S, {0, 0});
-  c->rat_par.assign(S, 0);
   // ---- PCM dump join (allocated last: every other buffer stays where it was) ----
   {
     float win[2 * JOIN_HOLD];
@@ -873,8 +725,6 @@ int lvx_finalize(lvx_ctx* c) {
     if ((r = c->dalloc(&c->join_win, 2 * JOIN_HOLD)) || (r = c->dalloc(&c->join_tail, (size_t)2 * S * JOIN_HOLD))) return r;
     HIP_TRY(hipMemcpy(c->join_win, win, sizeof(win), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->join_tail, 0, (size_t)2 * S * JOIN_HOLD * 4));
-    c->join_open.assign(S, 0);
-    c->join_par.assign(S, 0);
   }
   // ---- PCM level (allocated last: every other buffer stays where it was) ----
   {
@@ -883,9 +733,7 @@ int lvx_finalize(lvx_ctx* c) {
     if ((r = c->dalloc(&c->lvl_win, LVL_TAPS)) || (r = c->dalloc(&c->lvl_hist, (size_t)2 * S * LVL_HIST))) return r;
     HIP_TRY(hipMemcpy(c->lvl_win, win, sizeof(win), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->lvl_hist, 0, (size_t)2 * S * LVL_HIST * 4));
-    c->lvl_t0.assign(S, 0);
-    c->lvl_pct.assign(S, -1);
-    c->lvl_par.assign(S, 0);
+    for (auto& v : c->seg) v.assign(S, PcmSeg{});
   }
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
@@ -1408,16 +1256,7 @@ int lvx_pcm_reset(lvx_ctx* c, int slot, void* stream) {
   // here orders the reset behind every call already issued for the slot, on whatever stream
   (void)stream;
   std::lock_guard<std::mutex> lk(c->mu);
-  c->pcm_t0[slot] = 0;
-  c->pcm_rate[slot] = 0;
-  c->str_t0[slot] = 0;
-  c->str_hops[slot] = 0;
-  c->str_pct[slot] = 0;
-  c->rat_t0[slot] = 0;
-  c->rat_lm[slot] = {0, 0};
-  c->join_open[slot] = 0;
-  c->lvl_t0[slot] = 0;
-  c->lvl_pct[slot] = -1;
+  for (auto& v : c->seg) v[slot].close();
   return LVX_OK;
 }
 
@@ -1427,66 +1266,24 @@ int lvx_pcm_convert(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t
   const PcmRate* pr = pcm_rate_of(sample_rate);
   if (!pr) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate) + " (24000, 16000, 8000, 48000)");
   if (encoding != LVX_PCM_F32LE && encoding != LVX_PCM_S16LE) return fail(LVX_E_ARG, "encoding must be LVX_PCM_F32LE or LVX_PCM_S16LE");
-  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
-  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
   const bool launch = !(pr->N == 0 && encoding == LVX_PCM_F32LE);  // 24000 Hz f32le: the rows are the output
+  if (int r = pcm_args(B, n_in, pcm, slots && final_host && n_out_host ? slots : nullptr, launch, out, out_stride)) return r;
   const int bps = encoding == LVX_PCM_S16LE ? 2 : 4;
-  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
-    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
-  const int S = c->cfg.max_streams;
-  std::vector<PcmRow> rows(B);
+  std::vector<PcmRow> rows;
   {
-    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
-    // every row is checked before any slot's state changes
-    std::vector<uint8_t> seen(S, 0);
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
-      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
-      seen[s] = 1;
-      if (c->pcm_rate[s] && c->pcm_rate[s] != sample_rate)
-        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at " + std::to_string(c->pcm_rate[s]) + " Hz");
-      const long long t0 = c->pcm_t0[s];
-      const long long m0 = pcm_emitted_upto(*pr, t0, false), m1 = pcm_emitted_upto(*pr, t0 + n_in, final_host[b] != 0);
-      if (m1 - m0 > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
-      if (launch && (m1 - m0) * bps > out_stride)
-        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
-                                   std::to_string((m1 - m0) * bps) + " bytes)");
-      const int cur = (c->pcm_par[s] * S + s) * PCM_HIST, other = ((1 - c->pcm_par[s]) * S + s) * PCM_HIST;
-      const bool keep = pr->N > 0 && n_in > 0 && !final_host[b];  // a history for the segment's next call
-      rows[b] = PcmRow{t0, m0, (int)(m1 - m0), cur, keep ? other : -1, b};
-    }
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      n_out_host[b] = rows[b].n_out;
-      if (final_host[b]) {
-        c->pcm_t0[s] = 0;
-        c->pcm_rate[s] = 0;
-      } else {
-        c->pcm_t0[s] += n_in;
-        c->pcm_rate[s] = sample_rate;
-        if (rows[b].hist_out >= 0) c->pcm_par[s] ^= 1;
-      }
-    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    // (the one stage whose identity call advances the segment: the mirror of a 24 kHz f32le stream counts too)
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_CONVERT], PCM_HIST, B, n_in, slots, final_host, n_out_host, sample_rate, true,
+        [](long long k) { return std::to_string(k) + " Hz"; }, rows,
+        [&](const PcmCall& q, PcmRow& r) { return plan_convert(q, n_in, *pr, bps, launch, out_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
   }
   if (!launch) return LVX_OK;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
-    const int nr = std::min(PCM_ROWS, B - b0);
-    PcmRows pk{};
-    int max_out = 0;
-    bool any = false;
-    for (int k = 0; k < nr; ++k) {
-      pk.r[k] = rows[b0 + k];
-      max_out = std::max(max_out, pk.r[k].n_out);
-      any = any || pk.r[k].n_out > 0 || pk.r[k].hist_out >= 0;
-    }
-    if (!any) continue;  // (a flush with nothing left, or fewer inputs so far than the filter's delay and none to keep)
-    pcm_launch_convert(sample_rate, encoding, pk, nr, max_out, pcm, n_in, c->pcm_taps + pr->tap_off, c->pcm_hist, out,
-                       out_stride, (hipStream_t)stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return LVX_OK;
+  return pcm_launches<PcmRows>(c, rows, [&](const PcmRows& pk, int nr, int max_out) {
+    pcm_launch_convert(sample_rate, encoding, pk, nr, max_out, pcm, n_in, c->pcm_taps + pr->tap_off, c->pcm_hist, out, out_stride,
+                       (hipStream_t)stream);
+  });
 }
 
 // ---- PCM time stretch ----
@@ -1508,74 +1305,24 @@ int lvx_pcm_stretch(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t
                     void* stream) {
   NEED_FINAL(c);
   if (speed_pct < 50 || speed_pct > 200) return fail(LVX_E_ARG, "speed_pct must be in [50, 200], got " + std::to_string(speed_pct));
-  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
-  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
   const bool launch = speed_pct != 100;  // 100: the rows of pcm_dev are the output
-  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
-    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  if (int r = pcm_args(B, n_in, pcm, slots && final_host && n_out_host ? slots : nullptr, launch, out, out_stride)) return r;
   if (launch && d_out && ((reinterpret_cast<uintptr_t>(d_out) & 3) || d_stride < 0))
     return fail(LVX_E_ARG, "d_out_dev must be a multiple of 4 and d_stride >= 0");
-  const int S = c->cfg.max_streams;
-  std::vector<StretchRow> rows(B);
+  std::vector<StretchRow> rows;
   {
-    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
-    // every row is checked before any slot's state changes
-    std::vector<uint8_t> seen(S, 0);
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
-      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
-      seen[s] = 1;
-      if (c->str_pct[s] && c->str_pct[s] != speed_pct)
-        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at speed_pct " + std::to_string(c->str_pct[s]));
-      if (!launch) {
-        rows[b] = StretchRow{0, 0, 0, n_in, 0, -1, s, b};
-        continue;
-      }
-      const long long t0 = c->str_t0[s], j0 = c->str_hops[s];
-      const long long m1 = stretch_emitted_upto(speed_pct, t0 + n_in, final_host[b] != 0);
-      const long long n_out = std::max(0ll, m1 - j0 * STR_H), hops = (n_out + STR_H - 1) / STR_H;
-      if (n_out > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
-      if (n_out * 4 > out_stride)
-        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
-                                   std::to_string(n_out * 4) + " bytes)");
-      if (d_out && hops > d_stride)
-        return fail(LVX_E_ARG, "d_stride " + std::to_string(d_stride) + " is smaller than a row's hops (" + std::to_string(hops) + ")");
-      const int cur = (c->str_par[s] * S + s) * STR_HIST, other = ((1 - c->str_par[s]) * S + s) * STR_HIST;
-      const bool keep = n_in > 0 && !final_host[b];  // a history for the segment's next call
-      rows[b] = StretchRow{t0, j0, (int)hops, (int)n_out, cur, keep ? other : -1, s, b};
-    }
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      n_out_host[b] = rows[b].n_out;
-      if (final_host[b]) {
-        c->str_t0[s] = 0;
-        c->str_hops[s] = 0;
-        c->str_pct[s] = 0;
-      } else if (launch) {
-        c->str_t0[s] += n_in;
-        c->str_hops[s] += rows[b].n_hops;
-        c->str_pct[s] = speed_pct;
-        if (rows[b].hist_out >= 0) c->str_par[s] ^= 1;
-      }
-    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_STRETCH], STR_HIST, B, n_in, slots, final_host, n_out_host, speed_pct, launch,
+        [](long long k) { return "speed_pct " + std::to_string(k); }, rows,
+        [&](const PcmCall& q, StretchRow& r) { return plan_stretch(q, n_in, speed_pct, out_stride, d_out != nullptr, d_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
   }
   if (!launch) return LVX_OK;
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
-    const int nr = std::min(PCM_ROWS, B - b0);
-    StretchRows pk{};
-    bool any = false;
-    for (int k = 0; k < nr; ++k) {
-      pk.r[k] = rows[b0 + k];
-      any = any || pk.r[k].n_hops > 0 || pk.r[k].hist_out >= 0;
-    }
-    if (!any) continue;  // (a flush with nothing left)
+  return pcm_launches<StretchRows>(c, rows, [&](const StretchRows& pk, int nr, int) {
     pcm_launch_stretch(pk, nr, speed_pct, pcm, n_in, c->str_win, c->str_hist, c->str_d, out, out_stride, d_out, d_stride,
                        (hipStream_t)stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return LVX_OK;
+  });
 }
 
 // ---- PCM pitch shift ----
@@ -1616,59 +1363,25 @@ int lvx_pcm_ratio(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* 
                   int L, int M, float* out, long long out_stride, int32_t* n_out_host, void* stream) {
   NEED_FINAL(c);
   if (!ratio_ok(L, M)) return fail(LVX_E_ARG, ratio_msg(L, M));
-  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
-  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
   const int N = ratio_N(L, M);
   const bool launch = N != 0;  // 1 / 1: the rows of pcm_dev are the output
-  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
-    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
-  const int S = c->cfg.max_streams;
+  if (int r = pcm_args(B, n_in, pcm, slots && final_host && n_out_host ? slots : nullptr, launch, out, out_stride)) return r;
   const std::pair<int, int> lm{L, M};
-  std::vector<RatioRow> rows(B);
+  std::vector<RatioRow> rows;
   std::vector<int> upload;  // slots whose table region gets this ratio's table
   const std::vector<float>* table = nullptr;
   {
-    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror and the host cache: released before the launches)
-    // every row is checked before any slot's state changes
-    std::vector<uint8_t> seen(S, 0);
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
-      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
-      seen[s] = 1;
-      if (c->rat_lm[s].first && c->rat_lm[s] != lm)
-        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at the ratio " +
-                                   std::to_string(c->rat_lm[s].first) + " / " + std::to_string(c->rat_lm[s].second));
-      if (!launch) {
-        rows[b] = RatioRow{0, 0, n_in, 0, -1, b, 0};
-        continue;
+    std::lock_guard<std::mutex> lk(c->mu);  // (the host cache too)
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_RATIO], RAT_HIST, B, n_in, slots, final_host, n_out_host, ratio_key(L, M), launch,
+        [](long long k) { return "the ratio " + std::to_string(k >> 16) + " / " + std::to_string(k & 0xffff); }, rows,
+        [&](const PcmCall& q, RatioRow& r) { return plan_ratio(q, n_in, L, M, out_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
+    for (int b = 0; launch && b < B; ++b)
+      if (rows[b].n_out > 0 && c->rat_tab[slots[b]] != lm) {
+        c->rat_tab[slots[b]] = lm;
+        upload.push_back(slots[b]);
       }
-      const long long t0 = c->rat_t0[s];
-      const long long m0 = pcm_emitted_upto(L, M, N, t0, false), m1 = pcm_emitted_upto(L, M, N, t0 + n_in, final_host[b] != 0);
-      if (m1 - m0 > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
-      if ((m1 - m0) * 4 > out_stride)
-        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
-                                   std::to_string((m1 - m0) * 4) + " bytes)");
-      const int cur = (c->rat_par[s] * S + s) * RAT_HIST, other = ((1 - c->rat_par[s]) * S + s) * RAT_HIST;
-      const bool keep = n_in > 0 && !final_host[b];  // a history for the segment's next call
-      rows[b] = RatioRow{t0, m0, (int)(m1 - m0), cur, keep ? other : -1, b, s * RAT_TAPS_STRIDE};
-    }
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      n_out_host[b] = rows[b].n_out;
-      if (final_host[b]) {
-        c->rat_t0[s] = 0;
-        c->rat_lm[s] = {0, 0};
-      } else if (launch) {
-        c->rat_t0[s] += n_in;
-        c->rat_lm[s] = lm;
-        if (rows[b].hist_out >= 0) c->rat_par[s] ^= 1;
-      }
-      if (launch && rows[b].n_out > 0 && c->rat_tab[s] != lm) {
-        c->rat_tab[s] = lm;
-        upload.push_back(s);
-      }
-    }
     if (!upload.empty()) {  // designed once per ratio; an entry stays (and stays where it is) for the context's life
       auto it = c->rat_cache.find(lm);
       if (it == c->rat_cache.end()) it = c->rat_cache.emplace(lm, pcm_design(L, M, N)).first;
@@ -1682,21 +1395,9 @@ int lvx_pcm_ratio(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* 
   for (int s : upload)
     HIP_TRY(hipMemcpyAsync(c->rat_taps + (size_t)s * RAT_TAPS_STRIDE, table->data(), table->size() * 4, hipMemcpyHostToDevice,
                            (hipStream_t)stream));
-  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
-    const int nr = std::min(PCM_ROWS, B - b0);
-    RatioRows pk{};
-    int max_out = 0;
-    bool any = false;
-    for (int k = 0; k < nr; ++k) {
-      pk.r[k] = rows[b0 + k];
-      max_out = std::max(max_out, pk.r[k].n_out);
-      any = any || pk.r[k].n_out > 0 || pk.r[k].hist_out >= 0;
-    }
-    if (!any) continue;  // (a flush with nothing left)
+  return pcm_launches<RatioRows>(c, rows, [&](const RatioRows& pk, int nr, int max_out) {
     pcm_launch_ratio(pk, nr, max_out, L, M, N, pcm, n_in, c->rat_taps, c->rat_hist, out, out_stride, (hipStream_t)stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return LVX_OK;
+  });
 }
 
 // ---- PCM dump join ----
@@ -1705,13 +1406,6 @@ int lvx_pcm_join_window(float* wr_host, float* wf_host, int cap) {
   if (cap < JOIN_HOLD) return fail(LVX_E_ARG, "wr_host / wf_host hold fewer than 320 floats");
   join_design(wr_host, wf_host);
   return LVX_OK;
-}
-
-static std::string join_msg(bool open, int c, int n_in, bool final) {
-  return "not a join call: n_in " + std::to_string(n_in) + ", ctx_frames " + std::to_string(c) + (final ? ", final" : ", not final") +
-         (open ? ", open segment" : ", closed segment") +
-         " (n_in a multiple of 320; ctx_frames in [0, 16], 320 ctx_frames < n_in, 0 on a closed segment; n_in 0 only as a final "
-         "flush without context)";
 }
 
 int lvx_pcm_join_emitted(int open, int ctx_frames, int n_in, int final) {
@@ -1723,59 +1417,19 @@ int lvx_pcm_join_emitted(int open, int ctx_frames, int n_in, int final) {
 int lvx_pcm_join(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const int32_t* ctx_frames,
                  const uint8_t* final_host, float* out, long long out_stride, int32_t* n_out_host, void* stream) {
   NEED_FINAL(c);
-  if (B < 1 || n_in < 0 || !slots || !ctx_frames || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
-  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
-  if (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3))
-    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
-  const int S = c->cfg.max_streams;
-  std::vector<JoinRow> rows(B);
+  if (int r = pcm_args(B, n_in, pcm, slots && ctx_frames && final_host && n_out_host ? slots : nullptr, true, out, out_stride)) return r;
+  std::vector<JoinRow> rows;
   {
-    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
-    // every row is checked before any slot's state changes
-    std::vector<uint8_t> seen(S, 0);
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
-      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
-      seen[s] = 1;
-      const bool open = c->join_open[s] != 0, final = final_host[b] != 0;
-      const int cf = ctx_frames[b];
-      const int n_out = join_emitted(open, cf, n_in, final);
-      if (n_out < 0) return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": " + join_msg(open, cf, n_in, final));
-      if ((long long)n_out * 4 > out_stride)
-        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
-                                   std::to_string((long long)n_out * 4) + " bytes)");
-      const int cur = (c->join_par[s] * S + s) * JOIN_HOLD, other = ((1 - c->join_par[s]) * S + s) * JOIN_HOLD;
-      rows[b] = JoinRow{JOIN_HOLD * cf, !open ? JOIN_HEAD_NONE : cf > 0 ? JOIN_HEAD_FADE : JOIN_HEAD_TAIL, n_out, cur,
-                        final ? -1 : other, b};
-    }
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      n_out_host[b] = rows[b].n_out;
-      if (final_host[b]) {
-        c->join_open[s] = 0;
-      } else {
-        c->join_open[s] = 1;
-        c->join_par[s] ^= 1;
-      }
-    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    // (no parameter: every call's key is 0, which marks the segment open, and no call is an identity)
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_JOIN], JOIN_HOLD, B, n_in, slots, final_host, n_out_host, 0, true, [](long long) { return std::string(); },
+        rows, [&](const PcmCall& q, JoinRow& r) { return plan_join(q, n_in, ctx_frames[q.row], out_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
   }
-  HIP_TRY(hipSetDevice(c->cfg.device));
-  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
-    const int nr = std::min(PCM_ROWS, B - b0);
-    JoinRows pk{};
-    int max_out = 0;
-    bool any = false;
-    for (int k = 0; k < nr; ++k) {
-      pk.r[k] = rows[b0 + k];
-      max_out = std::max(max_out, pk.r[k].n_out);
-      any = any || pk.r[k].n_out > 0 || pk.r[k].tail_out >= 0;
-    }
-    if (!any) continue;  // (a flush of closed slots)
+  return pcm_launches<JoinRows>(c, rows, [&](const JoinRows& pk, int nr, int max_out) {
     pcm_launch_join(pk, nr, max_out, pcm, n_in, c->join_win, c->join_tail, out, out_stride, (hipStream_t)stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return LVX_OK;
+  });
 }
 
 // ---- PCM level ----
@@ -1797,76 +1451,25 @@ int lvx_pcm_level(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* 
                   void* stream) {
   NEED_FINAL(c);
   if (volume_pct < 0 || volume_pct > 400) return fail(LVX_E_ARG, "volume_pct must be in [0, 400], got " + std::to_string(volume_pct));
-  if (B < 1 || n_in < 0 || !slots || !final_host || !n_out_host) return fail(LVX_E_ARG, "bad B / n_in / host arrays");
-  if (n_in > 0 && !pcm) return fail(LVX_E_ARG, "null pcm_dev");
   const bool launch = volume_pct != 100;  // 100: the rows of pcm_dev are the output
-  if (launch && (!out || (reinterpret_cast<uintptr_t>(out) & 3) || out_stride < 0 || (out_stride & 3)))
-    return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 4");
+  if (int r = pcm_args(B, n_in, pcm, slots && final_host && n_out_host ? slots : nullptr, launch, out, out_stride)) return r;
   if (launch && g_out && ((reinterpret_cast<uintptr_t>(g_out) & 3) || g_stride < 0 || (g_stride & 3)))
     return fail(LVX_E_ARG, "g_out_dev and g_stride_bytes must be multiples of 4");
-  const int S = c->cfg.max_streams;
-  std::vector<PcmRow> rows(B);
+  std::vector<PcmRow> rows;
   {
-    std::lock_guard<std::mutex> lk(c->mu);  // (the mirror only: released before the launches)
-    // every row is checked before any slot's state changes
-    std::vector<uint8_t> seen(S, 0);
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      if (s < 0 || s >= S) return fail(LVX_E_ARG, "slot out of range");
-      if (seen[s]) return fail(LVX_E_ARG, "slot " + std::to_string(s) + " named twice in one call");
-      seen[s] = 1;
-      if (c->lvl_pct[s] >= 0 && c->lvl_pct[s] != volume_pct)
-        return fail(LVX_E_ARG, "slot " + std::to_string(s) + ": its segment is open at volume_pct " + std::to_string(c->lvl_pct[s]));
-      if (!launch) {
-        rows[b] = PcmRow{0, 0, n_in, 0, -1, b};
-        continue;
-      }
-      const long long t0 = c->lvl_t0[s];
-      const long long m0 = level_emitted_upto(volume_pct, t0, false);
-      const long long m1 = level_emitted_upto(volume_pct, t0 + n_in, final_host[b] != 0);
-      if (m1 - m0 > (1ll << 30)) return fail(LVX_E_ARG, "n_in too large");
-      if ((m1 - m0) * 4 > out_stride)
-        return fail(LVX_E_ARG, "out_stride_bytes " + std::to_string(out_stride) + " is smaller than a row's output (" +
-                                   std::to_string((m1 - m0) * 4) + " bytes)");
-      if (g_out && (m1 - m0) * 4 > g_stride)
-        return fail(LVX_E_ARG, "g_stride_bytes " + std::to_string(g_stride) + " is smaller than a row's output (" +
-                                   std::to_string((m1 - m0) * 4) + " bytes)");
-      const int cur = (c->lvl_par[s] * S + s) * LVL_HIST, other = ((1 - c->lvl_par[s]) * S + s) * LVL_HIST;
-      const bool keep = n_in > 0 && !final_host[b];  // a history for the segment's next call
-      rows[b] = PcmRow{t0, m0, (int)(m1 - m0), cur, keep ? other : -1, b};
-    }
-    for (int b = 0; b < B; ++b) {
-      const int s = slots[b];
-      n_out_host[b] = rows[b].n_out;
-      if (final_host[b]) {
-        c->lvl_t0[s] = 0;
-        c->lvl_pct[s] = -1;
-      } else if (launch) {
-        c->lvl_t0[s] += n_in;
-        c->lvl_pct[s] = volume_pct;
-        if (rows[b].hist_out >= 0) c->lvl_par[s] ^= 1;
-      }
-    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_LEVEL], LVL_HIST, B, n_in, slots, final_host, n_out_host, volume_pct, launch,
+        [](long long k) { return "volume_pct " + std::to_string(k); }, rows,
+        [&](const PcmCall& q, PcmRow& r) { return plan_level(q, n_in, volume_pct, out_stride, g_out != nullptr, g_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
   }
   if (!launch) return LVX_OK;
-  HIP_TRY(hipSetDevice(c->cfg.device));
   const float gain = (float)((double)volume_pct / 100.0);
-  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
-    const int nr = std::min(PCM_ROWS, B - b0);
-    PcmRows pk{};
-    int max_out = 0;
-    bool any = false;
-    for (int k = 0; k < nr; ++k) {
-      pk.r[k] = rows[b0 + k];
-      max_out = std::max(max_out, pk.r[k].n_out);
-      any = any || pk.r[k].n_out > 0 || pk.r[k].hist_out >= 0;
-    }
-    if (!any) continue;  // (a flush with nothing left)
+  return pcm_launches<PcmRows>(c, rows, [&](const PcmRows& pk, int nr, int max_out) {
     pcm_launch_level(pk, nr, max_out, gain, pcm, n_in, c->lvl_win, c->lvl_hist, out, out_stride, g_out, g_stride,
                      (hipStream_t)stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return LVX_OK;
+  });
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 
 #include "lvx_common.h"
 #include "llmvox.h"
+#include "pcm_host.h"
 
 namespace lvx {
 
@@ -259,97 +260,23 @@ void enc_launch_lstm_step(const float* gin, const float* whh, const float* bhh, 
 void enc_launch_vq(const float* emb, const float* scores, const float* esq, const float* cb, int32_t* codes,
                    float* feats, int B, int T, hipStream_t s);
 
-// ---------------- PCM output stage (pcm_kernels.hip) ----------------
-constexpr int PCM_HIST = 160;  // inputs of history a slot keeps between calls (the filters reach back <= 144)
-constexpr int PCM_ROWS = 32;   // rows of one launch (their descriptors travel as kernel arguments)
-struct PcmRow {
-  long long t0;  // inputs of the slot's segment consumed before this call
-  long long m0;  // outputs of the segment emitted before this call = index of the call's first output
-  int n_out;     // outputs of this call
-  int hist_in;   // float offset of the slot's history [PCM_HIST] (inputs t0 - 160 .. t0 - 1) in the pool
-  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
-  int row;       // row of pcm / out
-};
-struct PcmRows {
-  PcmRow r[PCM_ROWS];
-};
-// one launch for n_rows <= PCM_ROWS rows; sample_rate 24000 = no filter (elementwise quantisation)
+// ---------------- the PCM stages (pcm_kernels.hip; their constants and row packets: pcm_host.h) ----------------
+// Each launches n_rows <= PCM_ROWS rows.
+// sample_rate 24000 = no filter (elementwise quantisation)
 void pcm_launch_convert(int sample_rate, int enc, const PcmRows& rows, int n_rows, int max_out, const float* pcm,
                         int n_in, const float* taps, float* hist, void* out, long long out_stride, hipStream_t s);
-
-// ---------------- PCM pitch shift: the ratio resampler (pcm_kernels.hip; llmvox.h "PCM pitch shift") ----------------
-constexpr int RAT_HIST = 256;        // inputs of history a slot keeps between calls (an output reaches back <= 192)
-constexpr int RAT_MAX = 200;         // L and M of a ratio: 1 .. 200
-constexpr int RAT_TAPS = 2 * 24 * RAT_MAX + 1;  // the longest prototype: 2 N + 1 with N = 24 max(L, M)
-constexpr int RAT_TAPS_STRIDE = (RAT_TAPS + 63) / 64 * 64;  // floats of a slot's table region
-struct RatioRow {  // PcmRow and where the slot's table is
-  long long t0;  // inputs of the slot's segment consumed before this call
-  long long m0;  // outputs of the segment emitted before this call = index of the call's first output
-  int n_out;     // outputs of this call
-  int hist_in;   // float offset of the slot's history [RAT_HIST] (inputs t0 - 256 .. t0 - 1) in the pool
-  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
-  int row;       // row of pcm / out
-  int taps;      // float offset of the slot's table region (h[-N .. N]) in the table pool
-};
-struct RatioRows {
-  RatioRow r[PCM_ROWS];
-};
-// one launch for n_rows <= PCM_ROWS rows; 1 <= L, M <= RAT_MAX, M <= 4 L, N = 24 max(L, M)
+// 1 <= L, M <= RAT_MAX, M <= 4 L, N = 24 max(L, M)
 void pcm_launch_ratio(const RatioRows& rows, int n_rows, int max_out, int L, int M, int N, const float* pcm, int n_in,
                       const float* taps, float* hist, float* out, long long out_stride, hipStream_t s);
-
-// ---------------- PCM time stretch (pcm_kernels.hip; llmvox.h "PCM time stretch") ----------------
-constexpr int STR_H = 240;      // output hop
-constexpr int STR_D = 240;      // search radius
-constexpr int STR_C = 480;      // correlation length
-constexpr int STR_HIST = 1280;  // inputs of history a slot keeps between calls (a hop reaches back <= 1199)
-struct StretchRow {
-  long long t0;  // inputs of the slot's segment consumed before this call
-  long long j0;  // hops of the segment emitted before this call = index of the call's first hop
-  int n_hops;    // hops of this call
-  int n_out;     // samples of this call: n_hops * STR_H, less where a final call cuts the last hop
-  int hist_in;   // float offset of the slot's history [STR_HIST] (inputs t0 - 1280 .. t0 - 1) in the pool
-  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
-  int slot;      // the slot's word of the d_{j-1} state
-  int row;       // row of pcm / out / d_out
-};
-struct StretchRows {
-  StretchRow r[PCM_ROWS];
-};
-// one launch for n_rows <= PCM_ROWS rows, one block per row; win: wr [STR_H] then wf [STR_H]; dstate: the
-// slots' d_{j-1} (int per slot); d_out (optional): row b's chosen d_j at d_out + b * d_stride
+// one block per row; win: wr [STR_H] then wf [STR_H]; dstate: the slots' d_{j-1} (int per slot); d_out (optional):
+// row b's chosen d_j at d_out + b * d_stride
 void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, const float* pcm, int n_in,
                         const float* win, float* hist, int* dstate, float* out, long long out_stride, int* d_out,
                         int d_stride, hipStream_t s);
-
-// ---------------- PCM dump join (pcm_kernels.hip; llmvox.h "PCM dump join") ----------------
-constexpr int JOIN_HOLD = 320;  // samples held back and crossfaded: one codec frame
-constexpr int JOIN_CTX = 16;    // the most context frames of a call
-enum { JOIN_HEAD_NONE = 0, JOIN_HEAD_TAIL = 1, JOIN_HEAD_FADE = 2 };
-struct JoinRow {
-  int s;         // samples of context in front of the row: 320 c
-  int head;      // JOIN_HEAD_*: nothing, the slot's tail as it is, the tail crossfaded with r[s - 320 .. s)
-  int n_out;     // samples of this call: the head's 320 (if any), then r[s .. s + n_out - head's)
-  int tail_in;   // float offset of the slot's current tail [JOIN_HOLD] in the pool
-  int tail_out;  // where r[n_in - 320 .. n_in) goes (the slot's other buffer); -1: none kept
-  int row;       // row of pcm / out
-};
-struct JoinRows {
-  JoinRow r[PCM_ROWS];
-};
-// one launch for n_rows <= PCM_ROWS rows; win: wr [JOIN_HOLD] then wf [JOIN_HOLD]
+// win: wr [JOIN_HOLD] then wf [JOIN_HOLD]
 void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float* pcm, int n_in, const float* win,
                      float* tails, float* out, long long out_stride, hipStream_t s);
-
-// ---------------- PCM level (pcm_kernels.hip; llmvox.h "PCM level") ----------------
-constexpr int LVL_A = LVX_LEVEL_A;   // attack half-window
-constexpr int LVL_R = LVX_LEVEL_R;   // hold
-constexpr int LVL_TAPS = 2 * LVL_A + 1;
-constexpr int LVL_HIST = 1600;       // raw inputs of history a slot keeps between calls (an output reaches back <= 3 A + R = 1560)
-// The rows travel as PcmRows: t0 the inputs consumed before the call, m0 the outputs emitted before it (the index
-// of the call's first output: max(0, t0 - 2 A)), hist_in / hist_out float offsets of [LVL_HIST] buffers.
-// one launch for n_rows <= PCM_ROWS rows; gain: G; win: w[-A .. A]; g_out (optional): row b's g[n] at
-// g_out + b * g_stride bytes
+// gain: G; win: w[-A .. A]; g_out (optional): row b's g[n] at g_out + b * g_stride bytes
 void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, const float* pcm, int n_in,
                       const float* win, float* hist, float* out, long long out_stride, float* g_out, long long g_stride,
                       hipStream_t s);

@@ -1,0 +1,391 @@
+// Host side of the PCM stages (include/llmvox.h: "PCM output stage", "PCM time stretch", "PCM pitch shift", "PCM dump
+// join", "PCM level"): the stages' constants and kernel row packets, the tables and streaming counts of llmvox.h's
+// rules in double, and the one skeleton every stage's entry point runs (lvx_api.cpp). No HIP header and no device:
+// tests/host/pcm_stage_check.cpp drives all of it with the system compiler.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "llmvox.h"
+
+namespace lvx {
+
+// ---------------- the row packets (kernel arguments of pcm_kernels.hip: their layouts are the device's) ----------------
+constexpr int PCM_HIST = 160;  // inputs of history a slot keeps between calls (the filters reach back <= 144)
+constexpr int PCM_ROWS = 32;   // rows of one launch (their descriptors travel as kernel arguments)
+struct PcmRow {
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long m0;  // outputs of the segment emitted before this call = index of the call's first output
+  int n_out;     // outputs of this call
+  int hist_in;   // float offset of the slot's history [PCM_HIST] (inputs t0 - 160 .. t0 - 1) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int row;       // row of pcm / out
+};
+struct PcmRows {
+  PcmRow r[PCM_ROWS];
+};
+
+// PCM pitch shift: the ratio resampler
+constexpr int RAT_HIST = 256;        // inputs of history a slot keeps between calls (an output reaches back <= 192)
+constexpr int RAT_MAX = 200;         // L and M of a ratio: 1 .. 200
+constexpr int RAT_TAPS = 2 * 24 * RAT_MAX + 1;  // the longest prototype: 2 N + 1 with N = 24 max(L, M)
+constexpr int RAT_TAPS_STRIDE = (RAT_TAPS + 63) / 64 * 64;  // floats of a slot's table region
+struct RatioRow {  // PcmRow and where the slot's table is
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long m0;  // outputs of the segment emitted before this call = index of the call's first output
+  int n_out;     // outputs of this call
+  int hist_in;   // float offset of the slot's history [RAT_HIST] (inputs t0 - 256 .. t0 - 1) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int row;       // row of pcm / out
+  int taps;      // float offset of the slot's table region (h[-N .. N]) in the table pool
+};
+struct RatioRows {
+  RatioRow r[PCM_ROWS];
+};
+
+// PCM time stretch
+constexpr int STR_H = 240;      // output hop
+constexpr int STR_D = 240;      // search radius
+constexpr int STR_C = 480;      // correlation length
+constexpr int STR_HIST = 1280;  // inputs of history a slot keeps between calls (a hop reaches back <= 1199)
+struct StretchRow {
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long j0;  // hops of the segment emitted before this call = index of the call's first hop
+  int n_hops;    // hops of this call
+  int n_out;     // samples of this call: n_hops * STR_H, less where a final call cuts the last hop
+  int hist_in;   // float offset of the slot's history [STR_HIST] (inputs t0 - 1280 .. t0 - 1) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int slot;      // the slot's word of the d_{j-1} state
+  int row;       // row of pcm / out / d_out
+};
+struct StretchRows {
+  StretchRow r[PCM_ROWS];
+};
+
+// PCM dump join
+constexpr int JOIN_HOLD = 320;  // samples held back and crossfaded: one codec frame
+constexpr int JOIN_CTX = 16;    // the most context frames of a call
+enum { JOIN_HEAD_NONE = 0, JOIN_HEAD_TAIL = 1, JOIN_HEAD_FADE = 2 };
+struct JoinRow {
+  int s;         // samples of context in front of the row: 320 c
+  int head;      // JOIN_HEAD_*: nothing, the slot's tail as it is, the tail crossfaded with r[s - 320 .. s)
+  int n_out;     // samples of this call: the head's 320 (if any), then r[s .. s + n_out - head's)
+  int tail_in;   // float offset of the slot's current tail [JOIN_HOLD] in the pool
+  int tail_out;  // where r[n_in - 320 .. n_in) goes (the slot's other buffer); -1: none kept
+  int row;       // row of pcm / out
+};
+struct JoinRows {
+  JoinRow r[PCM_ROWS];
+};
+
+// PCM level. The rows travel as PcmRows: t0 the inputs consumed before the call, m0 the outputs emitted before it (the
+// index of the call's first output: max(0, t0 - 2 A)), hist_in / hist_out float offsets of [LVL_HIST] buffers.
+constexpr int LVL_A = LVX_LEVEL_A;   // attack half-window
+constexpr int LVL_R = LVX_LEVEL_R;   // hold
+constexpr int LVL_TAPS = 2 * LVL_A + 1;
+constexpr int LVL_HIST = 1600;       // raw inputs of history a slot keeps between calls (an output reaches back <= 3 A + R = 1560)
+
+// ---------------- the rules' tables and counts ----------------
+// ---- PCM dump join: the window tables and the counts (llmvox.h) ----
+// wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / 320), wf = 1 - wr in double; each table rounded once
+inline void join_design(float* wr, float* wf) {
+  const double pi = 3.14159265358979323846;
+  for (int n = 0; n < JOIN_HOLD; ++n) {
+    const double r = 0.5 - 0.5 * std::cos(pi * (n + 0.5) / JOIN_HOLD);
+    wr[n] = (float)r;
+    wf[n] = (float)(1.0 - r);
+  }
+}
+
+// samples a join call emits, -1 where the call is not one the rule admits (llmvox.h: the LVX_E_ARG cases)
+inline int join_emitted(bool open, int c, int n_in, bool final) {
+  if (n_in < 0 || n_in % JOIN_HOLD || c < 0 || c > JOIN_CTX) return -1;
+  if (n_in == 0) return (final && c == 0) ? (open ? JOIN_HOLD : 0) : -1;
+  if ((long long)JOIN_HOLD * c >= n_in || (c > 0 && !open)) return -1;
+  return (open ? JOIN_HOLD : 0) + n_in - JOIN_HOLD * c - (final ? 0 : JOIN_HOLD);
+}
+
+inline std::string join_msg(bool open, int c, int n_in, bool final) {
+  return "not a join call: n_in " + std::to_string(n_in) + ", ctx_frames " + std::to_string(c) + (final ? ", final" : ", not final") +
+         (open ? ", open segment" : ", closed segment") +
+         " (n_in a multiple of 320; ctx_frames in [0, 16], 320 ctx_frames < n_in, 0 on a closed segment; n_in 0 only as a final "
+         "flush without context)";
+}
+
+// ---- PCM output stage: the rates, their prototype filters and the streaming counts (llmvox.h) ----
+struct PcmRate {
+  int rate, L, M, N;
+  int tap_off;  // float offset of the rate's taps in lvx_ctx::pcm_taps
+};
+inline constexpr PcmRate kPcmRates[] = {{16000, 2, 3, 72, 0}, {8000, 1, 3, 72, 145}, {48000, 2, 1, 48, 290}};
+inline constexpr PcmRate kPcmNoFilter = {24000, 1, 1, 0, 0};
+
+inline const PcmRate* pcm_rate_of(int sample_rate) {
+  if (sample_rate == 24000) return &kPcmNoFilter;
+  for (const PcmRate& pr : kPcmRates)
+    if (pr.rate == sample_rate) return &pr;
+  return nullptr;
+}
+
+inline double bessel_i0(double x) {  // the power series: sum ((x / 2)^k / k!)^2
+  double sum = 1.0, term = 1.0;
+  const double q = x * x / 4.0;
+  for (int k = 1; k < 200; ++k) {
+    term *= q / ((double)k * k);
+    sum += term;
+    if (term < 1e-17 * sum) break;
+  }
+  return sum;
+}
+
+// h[n] = L 2 fc sinc(2 fc n) kaiser(2 N + 1, 9.0)[n + N], n = -N .. N, designed in double, stored as fp32:
+// the three fixed rates and every ratio of the pitch control (llmvox.h, "PCM pitch shift")
+inline std::vector<float> pcm_design(int L, int M, int N) {
+  if (N == 0) return {1.f};
+  const double lo = std::min(1.0, (double)L / M), fc = 0.5 * lo * 0.85 / L, beta = 9.0, pi = 3.14159265358979323846;
+  std::vector<float> h(2 * N + 1);
+  for (int n = -N; n <= N; ++n) {
+    const double a = 2.0 * fc * n, sinc = n == 0 ? 1.0 : std::sin(pi * a) / (pi * a);
+    const double u = (double)n / N;
+    const double w = bessel_i0(beta * std::sqrt(std::max(0.0, 1.0 - u * u))) / bessel_i0(beta);
+    h[n + N] = (float)(L * 2.0 * fc * sinc * w);
+  }
+  return h;
+}
+inline std::vector<float> pcm_design(const PcmRate& pr) { return pcm_design(pr.L, pr.M, pr.N); }
+
+// outputs of a segment emitted once T inputs are consumed
+inline long long pcm_emitted_upto(int L, int M, int N, long long T, bool final) {
+  const long long all = (T * L + M - 1) / M;  // ceil(T L / M)
+  if (final || N == 0) return all;
+  const long long a = (T - 1) * L - N;
+  return a < 0 ? 0 : std::min(a / M + 1, all);
+}
+inline long long pcm_emitted_upto(const PcmRate& pr, long long T, bool final) {
+  return pcm_emitted_upto(pr.L, pr.M, pr.N, T, final);
+}
+
+// ---- PCM pitch shift: the plan and the ratios the resampler takes (llmvox.h) ----
+inline int gcd_of(int a, int b) {
+  while (b) {
+    const int t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+// coprime 1 <= L, M <= 200 with M <= 4 L and L <= 4 M
+inline bool ratio_ok(int L, int M) {
+  return L >= 1 && M >= 1 && L <= RAT_MAX && M <= RAT_MAX && M <= 4 * L && L <= 4 * M && gcd_of(L, M) == 1;
+}
+inline int ratio_N(int L, int M) { return L == M ? 0 : 24 * std::max(L, M); }  // (coprime: L == M is 1 / 1, the identity)
+inline std::string ratio_msg(int L, int M) {
+  return "L / M must be coprime, each in 1 .. 200, with M <= 4 L and L <= 4 M, got " + std::to_string(L) + " / " + std::to_string(M);
+}
+
+// ---- PCM time stretch: the window tables and the streaming counts (llmvox.h) ----
+// wr[n] = 0.5 - 0.5 cos(pi (n + 0.5) / H), wf[n] = 1 - wr[n] (in double), each rounded to fp32 once
+inline void stretch_design(float* wr, float* wf) {
+  const double pi = 3.14159265358979323846;
+  for (int n = 0; n < STR_H; ++n) {
+    const double r = 0.5 - 0.5 * std::cos(pi * (n + 0.5) / STR_H);
+    wr[n] = (float)r;
+    wf[n] = (float)(1.0 - r);
+  }
+}
+
+inline long long stretch_a(long long j, int pct) { return (j * STR_H * pct) / 100; }
+
+// inputs of the segment hop j reads: the exclusive upper end of its search and its output
+inline long long stretch_need(long long j, int pct) {
+  if (j == 0) return 2 * STR_H;
+  return std::max(stretch_a(j, pct) + STR_D + 2 * STR_H, stretch_a(j - 1, pct) + STR_D + 3 * STR_H);
+}
+
+// how many hops j have need_j <= T (need_j does not decrease with j)
+inline long long stretch_hops(int pct, long long T) {
+  long long n = std::max(0ll, (T - 3 * STR_H) * 100 / ((long long)STR_H * pct)) + 2;
+  while (n > 0 && stretch_need(n - 1, pct) > T) --n;
+  while (stretch_need(n, pct) <= T) ++n;
+  return n;
+}
+
+// samples of a segment emitted once T inputs are consumed
+inline long long stretch_emitted_upto(int pct, long long T, bool final) {
+  if (pct == 100) return T;
+  if (final) return (T * 100 + pct - 1) / pct;
+  return STR_H * stretch_hops(pct, T);
+}
+
+// ---- PCM level: the window table and the streaming counts (llmvox.h) ----
+// w[k] = (0.5 + 0.5 cos(pi k / (A + 1))) / (A + 1), k = -A .. A, in double, each tap rounded to fp32 once
+inline void level_design(float* w) {
+  const double pi = 3.14159265358979323846;
+  for (int k = -LVL_A; k <= LVL_A; ++k) w[k + LVL_A] = (float)((0.5 + 0.5 * std::cos(pi * k / (LVL_A + 1))) / (LVL_A + 1));
+}
+
+// samples of a segment emitted once T inputs are consumed: the last 2 A wait for their right-hand inputs
+inline long long level_emitted_upto(int pct, long long T, bool final) {
+  if (pct == 100 || final) return T;
+  return std::max(0ll, T - 2 * LVL_A);
+}
+
+// ---------------- the skeleton of a stage's call ----------------
+// A stage keeps one record per slot, the host mirror of the slot's open segment, and two history buffers per slot in a
+// device pool [2][slots][hist]: a call reads the current one and writes the other, so no launch reads what it writes.
+struct PcmSeg {
+  static constexpr long long NONE = -1;  // no segment open (not 0: 0 is a volume)
+  long long t0 = 0;      // inputs of the segment consumed so far
+  long long aux = 0;     // the work of its calls so far in the stage's unit (row_work; the stretch's hops emitted)
+  long long key = NONE;  // the parameter the segment is open at: rate, speed, ratio_key, volume; the join has none (0)
+  uint8_t par = 0;       // which of the slot's two buffers is current: outlives the segment and lvx_pcm_reset
+  void close() {
+    t0 = aux = 0;
+    key = NONE;
+  }
+};
+inline long long ratio_key(int L, int M) { return ((long long)L << 16) | M; }
+
+// what a stage's planning function is given for one row of a call
+struct PcmCall {
+  const PcmSeg& seg;
+  bool final;
+  int cur, other;  // float offsets of the slot's current and other buffer in the stage's pool
+  int slot, row;
+};
+
+// a row's work in its stage's unit, and where it keeps a history (-1: nowhere)
+template <class Row> int row_work(const Row& r) { return r.n_out; }
+inline int row_work(const StretchRow& r) { return r.n_hops; }
+template <class Row> int row_kept(const Row& r) { return r.hist_out; }
+inline int row_kept(const JoinRow& r) { return r.tail_out; }
+
+// The part of a call under the context's lock; returns the error's text, empty when the call went through. Per row, in
+// this order: the slot's range, a slot named twice, a segment open at another key (key_text(key) names it), then
+// plan(PcmCall, Row&), the stage's own checks and its kernel row. Only when every row has passed do the records move
+// and n_out_host fill: a final row closes its segment; any other, where the call advances (an identity call of the
+// stretch, the ratio or the level does not), consumes n_in, takes the key and turns to the other buffer if the row
+// keeps a history there.
+template <class Row, class KeyText, class Plan>
+std::string pcm_plan(std::vector<PcmSeg>& segs, int hist, int B, int n_in, const int32_t* slots, const uint8_t* final_host,
+                     int32_t* n_out_host, long long key, bool advance, KeyText key_text, std::vector<Row>& rows, Plan plan) {
+  const int S = (int)segs.size();
+  rows.assign(B, Row{});
+  std::vector<uint8_t> seen(S, 0);
+  for (int b = 0; b < B; ++b) {
+    const int s = slots[b];
+    if (s < 0 || s >= S) return "slot out of range";
+    if (seen[s]) return "slot " + std::to_string(s) + " named twice in one call";
+    seen[s] = 1;
+    const PcmSeg& g = segs[s];
+    if (g.key != PcmSeg::NONE && g.key != key) return "slot " + std::to_string(s) + ": its segment is open at " + key_text(g.key);
+    const std::string e = plan(PcmCall{g, final_host[b] != 0, (g.par * S + s) * hist, ((1 - g.par) * S + s) * hist, s, b}, rows[b]);
+    if (!e.empty()) return e;
+  }
+  for (int b = 0; b < B; ++b) {
+    PcmSeg& g = segs[slots[b]];
+    n_out_host[b] = rows[b].n_out;
+    if (final_host[b]) {
+      g.close();
+    } else if (advance) {
+      g.t0 += n_in;
+      g.aux += row_work(rows[b]);
+      g.key = key;
+      if (row_kept(rows[b]) >= 0) g.par ^= 1;
+    }
+  }
+  return {};
+}
+
+// The part after the lock is dropped: the rows in packets of PCM_ROWS, launch(packet, rows, the most outputs of one);
+// a packet none of whose rows has work or keeps a history (a flush with nothing left) is not launched.
+template <class Rows, class Row, class Launch>
+void pcm_chunks(const std::vector<Row>& rows, Launch launch) {
+  const int B = (int)rows.size();
+  for (int b0 = 0; b0 < B; b0 += PCM_ROWS) {
+    const int nr = std::min(PCM_ROWS, B - b0);
+    Rows pk{};
+    int max_out = 0;
+    bool any = false;
+    for (int k = 0; k < nr; ++k) {
+      pk.r[k] = rows[b0 + k];
+      max_out = std::max(max_out, pk.r[k].n_out);
+      any = any || row_work(pk.r[k]) > 0 || row_kept(pk.r[k]) >= 0;
+    }
+    if (any) launch(pk, nr, max_out);
+  }
+}
+
+// ---------------- the stages' planning functions ----------------
+inline std::string stride_msg(const char* what, long long stride, long long bytes) {
+  return std::string(what) + " " + std::to_string(stride) + " is smaller than a row's output (" + std::to_string(bytes) + " bytes)";
+}
+
+// the row of a stage whose outputs are a closed form upto(T, final) of the inputs consumed (rate, ratio, level);
+// filtered: the stage has a history to keep for the segment's next call
+template <class Row, class Upto>
+std::string plan_counted(const PcmCall& c, int n_in, Upto upto, bool filtered, bool check_stride, int bps, long long out_stride,
+                         Row& r) {
+  const long long t0 = c.seg.t0, m0 = upto(t0, false), m1 = upto(t0 + n_in, c.final);
+  if (m1 - m0 > (1ll << 30)) return "n_in too large";
+  if (check_stride && (m1 - m0) * bps > out_stride) return stride_msg("out_stride_bytes", out_stride, (m1 - m0) * bps);
+  r.t0 = t0;
+  r.m0 = m0;
+  r.n_out = (int)(m1 - m0);
+  r.hist_in = c.cur;
+  r.hist_out = filtered && n_in > 0 && !c.final ? c.other : -1;
+  r.row = c.row;
+  return {};
+}
+
+// launch false (24 kHz f32le): the rows are the output and no stride is asked for, but the segment advances all the same
+inline std::string plan_convert(const PcmCall& c, int n_in, const PcmRate& pr, int bps, bool launch, long long out_stride, PcmRow& r) {
+  return plan_counted(c, n_in, [&](long long T, bool f) { return pcm_emitted_upto(pr, T, f); }, pr.N > 0, launch, bps, out_stride, r);
+}
+
+inline std::string plan_ratio(const PcmCall& c, int n_in, int L, int M, long long out_stride, RatioRow& r) {
+  const int N = ratio_N(L, M);
+  r = RatioRow{0, 0, n_in, 0, -1, c.row, 0};
+  if (N == 0) return {};  // 1 / 1: the rows of pcm_dev are the output
+  r.taps = c.slot * RAT_TAPS_STRIDE;
+  return plan_counted(c, n_in, [&](long long T, bool f) { return pcm_emitted_upto(L, M, N, T, f); }, true, true, 4, out_stride, r);
+}
+
+inline std::string plan_level(const PcmCall& c, int n_in, int pct, long long out_stride, bool want_g, long long g_stride, PcmRow& r) {
+  r = PcmRow{0, 0, n_in, 0, -1, c.row};
+  if (pct == 100) return {};  // the rows of pcm_dev are the output
+  std::string e = plan_counted(c, n_in, [&](long long T, bool f) { return level_emitted_upto(pct, T, f); }, true, true, 4, out_stride, r);
+  if (e.empty() && want_g && r.n_out * 4ll > g_stride) e = stride_msg("g_stride_bytes", g_stride, r.n_out * 4ll);
+  return e;
+}
+
+inline std::string plan_stretch(const PcmCall& c, int n_in, int pct, long long out_stride, bool want_d, int d_stride, StretchRow& r) {
+  r = StretchRow{0, 0, 0, n_in, 0, -1, c.slot, c.row};
+  if (pct == 100) return {};  // the rows of pcm_dev are the output
+  const long long t0 = c.seg.t0, j0 = c.seg.aux;
+  const long long m1 = stretch_emitted_upto(pct, t0 + n_in, c.final);
+  const long long n_out = std::max(0ll, m1 - j0 * STR_H), hops = (n_out + STR_H - 1) / STR_H;
+  if (n_out > (1ll << 30)) return "n_in too large";
+  if (n_out * 4 > out_stride) return stride_msg("out_stride_bytes", out_stride, n_out * 4);
+  if (want_d && hops > d_stride)
+    return "d_stride " + std::to_string(d_stride) + " is smaller than a row's hops (" + std::to_string(hops) + ")";
+  r = StretchRow{t0, j0, (int)hops, (int)n_out, c.cur, n_in > 0 && !c.final ? c.other : -1, c.slot, c.row};
+  return {};
+}
+
+// no key, and every call that is not final keeps a tail (so it always advances and always turns the buffers)
+inline std::string plan_join(const PcmCall& c, int n_in, int ctx_frames, long long out_stride, JoinRow& r) {
+  const bool open = c.seg.key != PcmSeg::NONE;
+  const int n_out = join_emitted(open, ctx_frames, n_in, c.final);
+  if (n_out < 0) return "slot " + std::to_string(c.slot) + ": " + join_msg(open, ctx_frames, n_in, c.final);
+  if (n_out * 4ll > out_stride) return stride_msg("out_stride_bytes", out_stride, n_out * 4ll);
+  r = JoinRow{JOIN_HOLD * ctx_frames, !open ? JOIN_HEAD_NONE : ctx_frames > 0 ? JOIN_HEAD_FADE : JOIN_HEAD_TAIL, n_out, c.cur,
+              c.final ? -1 : c.other, c.row};
+  return {};
+}
+
+}  // namespace lvx

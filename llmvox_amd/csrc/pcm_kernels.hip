@@ -32,6 +32,54 @@ __device__ __forceinline__ int pcm_q16(float v) {
 __device__ __forceinline__ long long ceil_div(long long a, int d) { return a >= 0 ? (a + d - 1) / d : -((-a) / d); }
 __device__ __forceinline__ long long floor_div(long long a, int d) { return a >= 0 ? a / d : -((-a + d - 1) / d); }
 
+// Segment input g (t0 - HIST <= g < t1) of a row: from the call's row x (inputs t0 .. t1 - 1) or the slot's history
+// [HIST] (inputs t0 - HIST .. t0 - 1); zero outside the segment
+template <int HIST>
+struct SegInput {
+  const float* __restrict__ x;
+  const float* hist;  // the pool; the slot's current buffer at hist_in (the launch writes the other one)
+  long long t0, t1;
+  int hist_in;
+  __device__ __forceinline__ float operator()(long long g) const {
+    if (g < 0 || g >= t1) return 0.f;
+    if (g >= t0) return x[g - t0];
+    const long long back = t0 - g;
+    return back <= HIST ? hist[hist_in + HIST - back] : 0.f;
+  }
+};
+
+// a thread's PCM_PER_THREAD consecutive floats, outputs ml .. of a block's nb: those below nb are stored, as one
+// 16-byte store where all are and the address allows
+__device__ __forceinline__ void store4(float* o, const float (&v)[PCM_PER_THREAD], int ml, int nb) {
+  if (ml + PCM_PER_THREAD <= nb && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int e = 0; e < PCM_PER_THREAD; ++e)
+      if (ml + e < nb) o[e] = v[e];
+  }
+}
+
+// The polyphase rule of llmvox.h for output m of the ratio L / M: the prototype h[-N .. N] in s_h; the output's first
+// input, ilo = ceil((m M - N) / L), at s_x[k]; its first tap index t = m M - ilo L, in (N - L, N]. Inputs in ascending
+// order, each product and each sum rounded to fp32 (no fused multiply-add: the compiler would contract the pair,
+// __fmul_rn / __fadd_rn included, without the pragma): the rule's fixed order, which a host evaluation in fp32
+// reproduces bit for bit.
+__device__ __forceinline__ float polyphase(const float* s_x, const float* s_h, int k, int t, int L, int N) {
+  float acc = 0.f;
+  for (; t >= -N; t -= L, ++k) {
+#pragma clang fp contract(off)
+    const float prod = s_x[k] * s_h[t + N];
+    acc = acc + prod;
+  }
+  return acc;
+}
+
+// blocks of PCM_OB outputs by the rows of the launch
+dim3 pcm_grid(int max_out, int n_rows) {
+  return dim3((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
+}
+
 // Grid (blocks of PCM_OB outputs, rows of the launch). Block (x, y) writes outputs
 // [x * PCM_OB, min((x + 1) * PCM_OB, n_out)) of row y's call; block (0, y) also writes the slot's next
 // history (into the buffer the launch does not read).
@@ -43,13 +91,7 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_convert_kernel(PcmRows rows, 
   const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
   const int tid = threadIdx.x;
   const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
-  // segment input g (t0 - PCM_HIST <= g < t1) from the call's row or the slot's history; zero outside the segment
-  auto input = [&](long long g) -> float {
-    if (g < 0 || g >= t1) return 0.f;
-    if (g >= r.t0) return x[g - r.t0];
-    const long long back = r.t0 - g;
-    return back <= PCM_HIST ? hist[r.hist_in + PCM_HIST - back] : 0.f;
-  };
+  const SegInput<PCM_HIST> input{x, hist, r.t0, t1, r.hist_in};
   if (N > 0 && blockIdx.x == 0 && r.hist_out >= 0 && tid < PCM_HIST) hist[r.hist_out + tid] = input(t1 - PCM_HIST + tid);
 
   const int mb = blockIdx.x * PCM_OB;
@@ -75,28 +117,20 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_convert_kernel(PcmRows rows, 
     for (int e = 0; e < PCM_PER_THREAD; ++e) {
       float acc = 0.f;
       if (ml + e < nb) {
+        // (the division by L stays here, where L is the template's constant: inside polyphase() the L = 2 kernels
+        // came out eight instructions longer and 0.1 us slower)
         const long long mm = (m_first + ml + e) * M;
-        const long long ilo = ceil_div(mm - N, L);
-        int t = (int)(mm - ilo * L);  // the first tap index: in (N - L, N]
-        int k = (int)(ilo - i0);
-        // inputs in ascending order, each product and each sum rounded to fp32 (no fused multiply-add:
-        // the compiler would contract the pair, __fmul_rn / __fadd_rn included, without the pragma): the
-        // rule's fixed order, which a host evaluation in fp32 reproduces bit for bit
-        for (; t >= -N; t -= L, ++k) {
-#pragma clang fp contract(off)
-          const float prod = s_x[k] * s_h[t + N];
-          acc = acc + prod;
-        }
+        const long long ilo = ceil_div(mm - N, L);  // the output's first input
+        acc = polyphase(s_x, s_h, (int)(ilo - i0), (int)(mm - ilo * L), L, N);
       }
       v[e] = acc;
     }
   }
 
   unsigned char* orow = out + (size_t)r.row * (size_t)out_stride;
-  const bool full = ml + PCM_PER_THREAD <= nb;
   if constexpr (ENC == LVX_PCM_S16LE) {
     int16_t* o = reinterpret_cast<int16_t*>(orow) + mb + ml;
-    if (full && (reinterpret_cast<uintptr_t>(o) & 7) == 0) {
+    if (ml + PCM_PER_THREAD <= nb && (reinterpret_cast<uintptr_t>(o) & 7) == 0) {
       uint2 w;
       w.x = (uint32_t)(uint16_t)pcm_q16(v[0]) | ((uint32_t)(uint16_t)pcm_q16(v[1]) << 16);
       w.y = (uint32_t)(uint16_t)pcm_q16(v[2]) | ((uint32_t)(uint16_t)pcm_q16(v[3]) << 16);
@@ -107,21 +141,14 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_convert_kernel(PcmRows rows, 
         if (ml + e < nb) o[e] = (int16_t)pcm_q16(v[e]);
     }
   } else {
-    float* o = reinterpret_cast<float*>(orow) + mb + ml;
-    if (full && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-      *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < PCM_PER_THREAD; ++e)
-        if (ml + e < nb) o[e] = v[e];
-    }
+    store4(reinterpret_cast<float*>(orow) + mb + ml, v, ml, nb);
   }
 }
 
 template <int L, int M, int N>
 void launch_enc(const PcmRows& rows, int n_rows, int max_out, int enc, const float* pcm, int n_in, const float* taps,
                 float* hist, void* out, long long out_stride, hipStream_t s) {
-  const dim3 grid((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
+  const dim3 grid = pcm_grid(max_out, n_rows);
   if (enc == LVX_PCM_S16LE)
     pcm_convert_kernel<L, M, N, LVX_PCM_S16LE><<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, taps, hist,
                                                                             (unsigned char*)out, out_stride);
@@ -144,13 +171,7 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_ratio_kernel(RatioRows rows, 
   const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
   const int tid = threadIdx.x;
   const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
-  // segment input g (t0 - RAT_HIST <= g < t1) from the call's row or the slot's history; zero outside the segment
-  auto input = [&](long long g) -> float {
-    if (g < 0 || g >= t1) return 0.f;
-    if (g >= r.t0) return x[g - r.t0];
-    const long long back = r.t0 - g;
-    return back <= RAT_HIST ? hist[r.hist_in + RAT_HIST - back] : 0.f;
-  };
+  const SegInput<RAT_HIST> input{x, hist, r.t0, t1, r.hist_in};
   if (blockIdx.x == 0 && r.hist_out >= 0 && tid < RAT_HIST) hist[r.hist_out + tid] = input(t1 - RAT_HIST + tid);
 
   const int mb = blockIdx.x * PCM_OB;
@@ -174,28 +195,12 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_ratio_kernel(RatioRows rows, 
     float acc = 0.f;
     if (ml + e < nb) {
       const long long mm = (m_first + ml + e) * M;
-      const long long ilo = ceil_div(mm - N, L);
-      int t = (int)(mm - ilo * L);  // the first tap index: in (N - L, N]
-      int k = (int)(ilo - i0);
-      // inputs in ascending order, each product and each sum rounded to fp32 (no fused multiply-add): the
-      // rule's fixed order, as in pcm_convert_kernel
-      for (; t >= -N; t -= L, ++k) {
-#pragma clang fp contract(off)
-        const float prod = s_x[k] * s_h[t + N];
-        acc = acc + prod;
-      }
+      const long long ilo = ceil_div(mm - N, L);  // the output's first input
+      acc = polyphase(s_x, s_h, (int)(ilo - i0), (int)(mm - ilo * L), L, N);
     }
     v[e] = acc;
   }
-
-  float* o = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride) + mb + ml;
-  if (ml + PCM_PER_THREAD <= nb && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-    *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < PCM_PER_THREAD; ++e)
-      if (ml + e < nb) o[e] = v[e];
-  }
+  store4(reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride) + mb + ml, v, ml, nb);
 }
 
 // ---- PCM time stretch (llmvox.h, "PCM time stretch"): WSOLA on the 24 kHz rows ----
@@ -227,9 +232,9 @@ __global__ __launch_bounds__(STR_THREADS) void pcm_stretch_kernel(StretchRows ro
   const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
   const int tid = threadIdx.x;
   const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
-  // segment input g from the call's row or the slot's history; zero outside the segment. Without a
-  // branch (an input outside loads a word of the window table and drops it), so that the loads of a hop's
-  // staging are all in flight together: a hop waits for one memory latency, not for six in turn.
+  // segment input g from the call's row or the slot's history; zero outside the segment. Its own form, not
+  // SegInput: without a branch (an input outside loads a word of the window table and drops it), so that the
+  // loads of a hop's staging are all in flight together: a hop waits for one memory latency, not for six in turn.
   auto input = [&](long long g) -> float {
     const long long back = r.t0 - g;
     const bool in_row = g >= r.t0 && g < t1, in_hist = g >= 0 && back >= 1 && back <= STR_HIST;
@@ -456,13 +461,7 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_level_kernel(PcmRows rows, fl
   const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
   const int tid = threadIdx.x;
   const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
-  // segment input g (t0 - LVL_HIST <= g < t1) from the call's row or the slot's history; zero outside the segment
-  auto input = [&](long long g) -> float {
-    if (g < 0 || g >= t1) return 0.f;
-    if (g >= r.t0) return x[g - r.t0];
-    const long long back = r.t0 - g;
-    return back <= LVL_HIST ? hist[r.hist_in + LVL_HIST - back] : 0.f;
-  };
+  const SegInput<LVL_HIST> input{x, hist, r.t0, t1, r.hist_in};
   if (blockIdx.x == 0 && r.hist_out >= 0)
     for (int i = tid; i < LVL_HIST; i += PCM_THREADS) hist[r.hist_out + i] = input(t1 - LVL_HIST + i);
 
@@ -533,25 +532,8 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_level_kernel(PcmRows rows, fl
     y[e] = __fmul_rn(v, gg[e]);
   }
 
-  const bool full = ml + PCM_PER_THREAD <= nb;
-  float* o = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride) + mb + ml;
-  if (full && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-    *reinterpret_cast<float4*>(o) = make_float4(y[0], y[1], y[2], y[3]);
-  } else {
-#pragma unroll
-    for (int e = 0; e < PCM_PER_THREAD; ++e)
-      if (ml + e < nb) o[e] = y[e];
-  }
-  if (g_out) {
-    float* go = reinterpret_cast<float*>(g_out + (size_t)r.row * (size_t)g_stride) + mb + ml;
-    if (full && (reinterpret_cast<uintptr_t>(go) & 15) == 0) {
-      *reinterpret_cast<float4*>(go) = make_float4(gg[0], gg[1], gg[2], gg[3]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < PCM_PER_THREAD; ++e)
-        if (ml + e < nb) go[e] = gg[e];
-    }
-  }
+  store4(reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride) + mb + ml, y, ml, nb);
+  if (g_out) store4(reinterpret_cast<float*>(g_out + (size_t)r.row * (size_t)g_stride) + mb + ml, gg, ml, nb);
 }
 
 }  // namespace
@@ -559,15 +541,14 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_level_kernel(PcmRows rows, fl
 void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, const float* pcm, int n_in,
                       const float* win, float* hist, float* out, long long out_stride, float* g_out, long long g_stride,
                       hipStream_t s) {
-  const dim3 grid((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
-  pcm_level_kernel<<<grid, PCM_THREADS, 0, s>>>(rows, gain, pcm, n_in, win, hist, (unsigned char*)out, out_stride,
-                                                (unsigned char*)g_out, g_stride);
+  pcm_level_kernel<<<pcm_grid(max_out, n_rows), PCM_THREADS, 0, s>>>(rows, gain, pcm, n_in, win, hist, (unsigned char*)out,
+                                                                     out_stride, (unsigned char*)g_out, g_stride);
 }
 
 void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float* pcm, int n_in, const float* win,
                      float* tails, float* out, long long out_stride, hipStream_t s) {
-  const dim3 grid((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
-  pcm_join_kernel<<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, win, tails, (unsigned char*)out, out_stride);
+  pcm_join_kernel<<<pcm_grid(max_out, n_rows), PCM_THREADS, 0, s>>>(rows, pcm, n_in, win, tails, (unsigned char*)out,
+                                                                    out_stride);
 }
 
 void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, const float* pcm, int n_in,
@@ -579,8 +560,8 @@ void pcm_launch_stretch(const StretchRows& rows, int n_rows, int speed_pct, cons
 
 void pcm_launch_ratio(const RatioRows& rows, int n_rows, int max_out, int L, int M, int N, const float* pcm, int n_in,
                       const float* taps, float* hist, float* out, long long out_stride, hipStream_t s) {
-  const dim3 grid((unsigned)std::max(1, (max_out + PCM_OB - 1) / PCM_OB), (unsigned)n_rows);
-  pcm_ratio_kernel<<<grid, PCM_THREADS, 0, s>>>(rows, L, M, N, pcm, n_in, taps, hist, (unsigned char*)out, out_stride);
+  pcm_ratio_kernel<<<pcm_grid(max_out, n_rows), PCM_THREADS, 0, s>>>(rows, L, M, N, pcm, n_in, taps, hist,
+                                                                     (unsigned char*)out, out_stride);
 }
 
 void pcm_launch_convert(int sample_rate, int enc, const PcmRows& rows, int n_rows, int max_out, const float* pcm,

@@ -6,7 +6,6 @@ returns torch device tensors (torch is only the allocator and the stream provide
 from __future__ import annotations
 
 import ctypes
-import dataclasses
 from typing import Dict, Optional
 
 import numpy as np
@@ -305,12 +304,22 @@ class Engine:
         return wr, wf
 
     def _pcm_rows(self, pcm: Optional[torch.Tensor], B: int):
-        n_in = 0 if pcm is None else int(pcm.shape[1])
-        if pcm is not None:
-            if pcm.shape[0] != B or pcm.dtype != torch.float32 or pcm.device != self.device:
-                raise ValueError(f"pcm must be a float32 [{B}, n_in] tensor on {self.device}")
-            pcm = pcm.contiguous()
-        return pcm, n_in
+        """(rows, n_in) of a stage's input, checked; None: no rows, a flush."""
+        if pcm is None:
+            return None, 0
+        if pcm.shape[0] != B or pcm.dtype != torch.float32 or pcm.device != self.device:
+            raise ValueError(f"pcm must be a float32 [{B}, n_in] tensor on {self.device}")
+        return pcm.contiguous(), int(pcm.shape[1])
+
+    def _pcm_args(self, pcm: Optional[torch.Tensor], slots, finals):
+        """What every stage's library call takes: (rows, n_in, B, slots as c_int32, finals as c_uint8, the counts array
+        to fill) and the output of a stage with nothing to do, the rows themselves."""
+        slots = [int(s) for s in slots]
+        B = len(slots)
+        pcm, n_in = self._pcm_rows(pcm, B)
+        same = pcm if pcm is not None else torch.empty(B, 0, device=self.device, dtype=torch.float32)
+        return (pcm, n_in, B, (ctypes.c_int32 * B)(*slots), (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals]),
+                (ctypes.c_int32 * B)(), same)
 
     def pcm_stretch(self, pcm: Optional[torch.Tensor], slots, finals, speed_pct: int, want_d: bool = False):
         """The time stretch alone (lvx_pcm_stretch): rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None
@@ -319,14 +328,12 @@ class Engine:
         float32 tensor [B, width] whose row b holds counts[b] samples, and (``want_d``) a device int32 tensor
         whose row b holds the chosen d_j of the hops the call emitted (else None). speed_pct 100: the rows
         themselves. Asynchronous on the current stream; a slot's calls must be issued in order on one stream."""
-        slots = [int(s) for s in slots]
-        B = len(slots)
-        pcm, n_in = self._pcm_rows(pcm, B)
+        pcm, n_in, B, sl, fl, cnt, same = self._pcm_args(pcm, slots, finals)
         speed_pct = int(speed_pct)
         out = d = None
         width = dw = 0
         if speed_pct == 100:
-            out = pcm if pcm is not None else torch.empty(B, 0, device=self.device, dtype=torch.float32)
+            out = same
         elif 50 <= speed_pct <= 200:
             # a call emits at most the hops that waited for their right-hand inputs (<= 960 inputs' worth)
             # and its own inputs' worth, cut to whole hops; rows start on 16-byte boundaries
@@ -335,9 +342,6 @@ class Engine:
             if want_d:
                 dw = width // 240 + 1
                 d = torch.zeros(B, dw, device=self.device, dtype=torch.int32)
-        sl = (ctypes.c_int32 * B)(*slots)
-        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
-        cnt = (ctypes.c_int32 * B)()
         _lib.check(self.lib.lvx_pcm_stretch(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, speed_pct, _ptr(out),
                                             width * 4, cnt, _ptr(d), dw, self.stream_handle()))
         return out, list(cnt), d
@@ -363,21 +367,16 @@ class Engine:
         true ``finals[b]`` emits the rest of row b's segment and ends it. Returns (out, counts): a device
         float32 tensor [B, width] whose row b holds counts[b] samples. 1 / 1: the rows themselves. Asynchronous
         on the current stream; a slot's calls must be issued in order on one stream."""
-        slots = [int(s) for s in slots]
-        B = len(slots)
-        pcm, n_in = self._pcm_rows(pcm, B)
+        pcm, n_in, B, sl, fl, cnt, same = self._pcm_args(pcm, slots, finals)
         L, M = int(L), int(M)
         out, width = None, 0
         if L == M == 1:
-            out = pcm if pcm is not None else torch.empty(B, 0, device=self.device, dtype=torch.float32)
+            out = same
         elif 1 <= L <= 200 and 1 <= M <= 200:
             # a call emits at most (n_in L + L + N) / M + 2 samples, N = 24 max(L, M) (a final call of a segment
             # whose earlier outputs waited for their right-hand inputs); rows start on 16-byte boundaries
             width = ((n_in * L + L + 24 * max(L, M)) // M + 3 + 7) // 8 * 8
             out = torch.empty(B, width, device=self.device, dtype=torch.float32)
-        sl = (ctypes.c_int32 * B)(*slots)
-        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
-        cnt = (ctypes.c_int32 * B)()
         _lib.check(self.lib.lvx_pcm_ratio(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, L, M, _ptr(out), width * 4,
                                           cnt, self.stream_handle()))
         return out, list(cnt)
@@ -397,15 +396,10 @@ class Engine:
         ``finals[b]`` emits the row to its end and closes the segment. Returns (out, counts): a device float32
         tensor [B, width] whose row b holds counts[b] samples. Asynchronous on the current stream; a slot's
         calls must be issued in order on one stream."""
-        slots = [int(s) for s in slots]
-        B = len(slots)
-        pcm, n_in = self._pcm_rows(pcm, B)
+        pcm, n_in, B, sl, fl, cnt, _ = self._pcm_args(pcm, slots, finals)
         width = n_in + 320  # (the most a call emits: its row and the held-back frame; rows on 16-byte boundaries)
         out = torch.empty(B, width, device=self.device, dtype=torch.float32)
-        sl = (ctypes.c_int32 * B)(*slots)
         cf = (ctypes.c_int32 * B)(*[int(c) for c in ctx_frames])
-        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
-        cnt = (ctypes.c_int32 * B)()
         _lib.check(self.lib.lvx_pcm_join(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, cf, fl, _ptr(out), width * 4,
                                          cnt, self.stream_handle()))
         return out, list(cnt)
@@ -424,22 +418,17 @@ class Engine:
         (``want_g``) a device float32 tensor whose row b holds the limiter's gain of each (else None). volume_pct
         100: the rows themselves. Asynchronous on the current stream; a slot's calls must be issued in order on
         one stream."""
-        slots = [int(s) for s in slots]
-        B = len(slots)
-        pcm, n_in = self._pcm_rows(pcm, B)
+        pcm, n_in, B, sl, fl, cnt, same = self._pcm_args(pcm, slots, finals)
         volume_pct = int(volume_pct)
         out = g = None
         width = 0
         if volume_pct == 100:
-            out = pcm if pcm is not None else torch.empty(B, 0, device=self.device, dtype=torch.float32)
+            out = same
         elif 0 <= volume_pct <= 400:
             width = (n_in + 240 + 7) // 8 * 8  # (the call's inputs and the held-back 240; rows on 16-byte boundaries)
             out = torch.empty(B, width, device=self.device, dtype=torch.float32)
             if want_g:
                 g = torch.zeros(B, width, device=self.device, dtype=torch.float32)
-        sl = (ctypes.c_int32 * B)(*slots)
-        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
-        cnt = (ctypes.c_int32 * B)()
         _lib.check(self.lib.lvx_pcm_level(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, volume_pct, _ptr(out),
                                           width * 4, cnt, _ptr(g), width * 4, self.stream_handle()))
         return out, list(cnt), g
@@ -448,51 +437,41 @@ class Engine:
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
         ``audio.AudioFormat`` (its speed, pitch, volume, rate and encoding). Returns (out, counts): a device tensor
-        [B, width] of int16 or float32 whose row b holds counts[b] samples. Four stages, each only where the
-        format needs it: the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the
-        plan's L / M (lvx_pcm_ratio), the gain and limiter at volume_pct (lvx_pcm_level; a format at 100 makes
-        exactly the calls it made before there was one), the rate and the encoding (lvx_pcm_convert). Rows may leave a stage with
-        different counts: they pass the next one grouped by count. A format without a pitch makes the calls it
-        made before there was one. A format with ``join`` passes the dump join first (lvx_pcm_join), row b with
-        ``ctx_frames[b]`` frames of context in front (None: none anywhere); one without makes exactly the calls
-        it made before there was a join. Asynchronous on the current stream; a slot's calls must be issued in
-        order on one stream."""
-        stretch_pct, (L, M) = fmt.stretch_pct, fmt.ratio
-        vol = fmt.volume_pct
-        plain = fmt.sample_rate == 24000 and fmt.encoding == "f32le"  # the last stage has nothing to do
-        dtype = torch.int16 if fmt.encoding == "s16le" else torch.float32
-        if fmt.join:
-            slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
-            jo, cnt = self.pcm_join(pcm, slots, ctx_frames if ctx_frames is not None else [0] * len(slots), finals)
-            rest = dataclasses.replace(fmt, join=False)
-            if stretch_pct == 100 and L == M and vol == 100 and plain:
-                return jo, cnt
-            return self._pcm_grouped(jo, cnt, slots, finals, lambda sub, sl, fl: self.pcm_convert(sub, sl, fl, rest), dtype)
-        if ctx_frames is not None and any(ctx_frames):
-            raise ValueError("ctx_frames without a joined format")
-
-        def last(sub, sl, fl):
-            return self._pcm_resample(sub, sl, fl, fmt)
-
-        def level(sub, sl, fl):
-            if vol == 100:
-                return last(sub, sl, fl)
-            o, c, _ = self.pcm_level(sub, sl, fl, vol)
-            return (o, c) if plain else self._pcm_grouped(o, c, sl, fl, last, dtype)
-
-        def ratio(sub, sl, fl):
-            if L == M:
-                return level(sub, sl, fl)
-            o, c = self.pcm_ratio(sub, sl, fl, L, M)
-            return (o, c) if plain and vol == 100 else self._pcm_grouped(o, c, sl, fl, level, dtype)
-
-        if stretch_pct == 100:
-            return ratio(pcm, slots, finals)
+        [B, width] of int16 or float32 whose row b holds counts[b] samples. Five stages in this order, each only
+        where the format needs it, so that a format makes exactly the calls of the stages it uses: the dump join
+        (lvx_pcm_join, a format with ``join``: row b with ``ctx_frames[b]`` frames of context in front, None: none
+        anywhere), the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the plan's L / M
+        (lvx_pcm_ratio), the gain and limiter at volume_pct (lvx_pcm_level), the rate and the encoding
+        (lvx_pcm_convert). Rows may leave a stage with different counts: they pass the next one grouped by count.
+        Asynchronous on the current stream; a slot's calls must be issued in order on one stream."""
+        stretch_pct, (L, M), vol = fmt.stretch_pct, fmt.ratio, fmt.volume_pct
         slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
-        st, cnt, _ = self.pcm_stretch(pcm, slots, finals, stretch_pct)
-        if L == M and vol == 100 and plain:
-            return st, cnt
-        return self._pcm_grouped(st, cnt, slots, finals, ratio, dtype)
+        if not fmt.join and ctx_frames is not None and any(ctx_frames):
+            raise ValueError("ctx_frames without a joined format")
+        ctx = ctx_frames if ctx_frames is not None else [0] * len(slots)
+        stages = []  # the stages this format needs, in the order the rows pass them (the join sees every row at once)
+        if fmt.join:
+            stages.append(lambda sub, sl, fl: self.pcm_join(sub, sl, ctx, fl))
+        if stretch_pct != 100:
+            stages.append(lambda sub, sl, fl: self.pcm_stretch(sub, sl, fl, stretch_pct)[:2])
+        if L != M:
+            stages.append(lambda sub, sl, fl: self.pcm_ratio(sub, sl, fl, L, M))
+        if vol != 100:
+            stages.append(lambda sub, sl, fl: self.pcm_level(sub, sl, fl, vol)[:2])
+        # The rate and the encoding come last. At 24 kHz f32le they have nothing to do and the output of the stage
+        # before them is the result: they are skipped, unless no other stage runs (the library's mirror of the
+        # segment still has to advance).
+        if not stages or not (fmt.sample_rate == 24000 and fmt.encoding == "f32le"):
+            stages.append(lambda sub, sl, fl: self._pcm_resample(sub, sl, fl, fmt))
+        dtype = torch.int16 if fmt.encoding == "s16le" else torch.float32
+
+        def run(i, sub, sl, fl):  # stage i and, grouped by what it hands on, the stages behind it
+            out, cnt = stages[i](sub, sl, fl)
+            if i + 1 == len(stages):
+                return out, cnt
+            return self._pcm_grouped(out, cnt, sl, fl, lambda *rows: run(i + 1, *rows), dtype)
+
+        return run(0, pcm, slots, finals)
 
     def _pcm_grouped(self, st, cnt, slots, finals, stage, dtype):
         """The hand-over between two stages: row b of ``st`` holds cnt[b] samples; the rows pass
@@ -521,18 +500,10 @@ class Engine:
 
     def _pcm_resample(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
         """pcm_convert without the speed and the pitch: the rate and the encoding (lvx_pcm_convert)."""
-        slots = [int(s) for s in slots]
-        B = len(slots)
-        n_in = 0 if pcm is None else int(pcm.shape[1])
-        if pcm is not None:
-            if pcm.shape[0] != B or pcm.dtype != torch.float32 or pcm.device != self.device:
-                raise ValueError(f"pcm must be a float32 [{B}, n_in] tensor on {self.device}")
-            pcm = pcm.contiguous()
+        pcm, n_in, B, sl, fl, cnt, same = self._pcm_args(pcm, slots, finals)
         s16 = fmt.encoding == "s16le"
         if fmt.sample_rate == 24000 and not s16:  # 24 kHz f32le: the rows are the output (nothing is launched)
-            if pcm is None:
-                pcm = torch.empty(B, 0, device=self.device, dtype=torch.float32)
-            out, width = pcm, n_in
+            out, width = same, n_in
         else:
             L, M, N = (ctypes.c_int() for _ in range(3))
             _lib.check(self.lib.lvx_pcm_filter(fmt.sample_rate, ctypes.byref(L), ctypes.byref(M), ctypes.byref(N), None, 0))
@@ -540,9 +511,6 @@ class Engine:
             # outputs waited for their right-hand inputs); rows start on 16-byte boundaries
             width = ((n_in * L.value + L.value + N.value) // M.value + 3 + 7) // 8 * 8
             out = torch.empty(B, width, device=self.device, dtype=torch.int16 if s16 else torch.float32)
-        sl = (ctypes.c_int32 * B)(*slots)
-        fl = (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
-        cnt = (ctypes.c_int32 * B)()
         _lib.check(self.lib.lvx_pcm_convert(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, fmt.sample_rate,
                                             _lib.LVX_PCM_S16LE if s16 else _lib.LVX_PCM_F32LE, _ptr(out),
                                             width * (2 if s16 else 4), cnt, self.stream_handle()))

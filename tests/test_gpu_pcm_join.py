@@ -140,6 +140,32 @@ def test_rows_that_are_not_16_byte_aligned(eng):
     eng.check_errors()
 
 
+def test_33_rows_are_two_launches_of_the_same_rows():
+    """One more row than a launch's packet holds, a non-final call and a final one with a context frame: every
+    row's bits, the second launch's row 32 among them, are the numpy rule's."""
+    from llmvox_amd.engine import build_engine
+    e = build_engine(0, "fp32", "fp32", max_streams=40, max_positions=64, max_codec_frames=64)
+    try:
+        rows = 33
+        rng = np.random.default_rng(33)
+        a, b = _rows(rng, rows, 2), _rows(rng, rows, 2)
+        slots = [(7 * r + 3) % 40 for r in range(rows)]
+        assert len(set(slots)) == rows
+        windows = e.pcm_join_window()
+        got = []
+        for x, c, final in [(a, 0, False), (b, 1, True)]:
+            out, cnt = e.pcm_join(torch.from_numpy(x).to(e.device), slots, [c] * rows, [final] * rows)
+            got.append((out.cpu().numpy(), cnt))
+        e.check_errors()
+        assert got[0][1] == [H] * rows and got[1][1] == [2 * H] * rows
+        for r in range(rows):
+            want = A.join_ref([a[r], b[r]], [0, 1], windows)
+            for k in range(2):
+                assert np.array_equal(_bits(got[k][0][r, :got[k][1][r]]), _bits(want[k])), (r, k)
+    finally:
+        e.close()
+
+
 def test_argument_errors_move_no_slot(eng):
     from llmvox_amd import _lib
     rng = np.random.default_rng(14)

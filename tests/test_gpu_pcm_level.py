@@ -409,3 +409,49 @@ def test_scheduler_end_to_end(sched_eng):
     want = A.convert_ref(xs, fmt, level_win=sched_eng.pcm_level_window())
     assert got.size == want.size == xs.size and np.array_equal(_bits(got), _bits(want))
     assert not np.array_equal(_bits(got), _bits(xs))
+
+
+STAGES = ("pcm_join", "pcm_stretch", "pcm_ratio", "pcm_level", "_pcm_resample")
+J, S, P, V, R = STAGES
+# per format: the stages each of the two calls passes, in order (every one with all three slots). In the last format
+# the first call's join hands 320 samples on, fewer than the stretch's first hop needs: nothing passes the stretch
+# and the stages behind it are not called.
+PIPELINES = [
+    (A.AudioFormat(), [[R], [R]]),
+    (A.AudioFormat(16000, "s16le"), [[R], [R]]),
+    (A.AudioFormat(speed_pct=130), [[S], [S]]),
+    (A.AudioFormat(pitch_pct=90), [[S, P], [S, P]]),
+    (A.AudioFormat(volume_pct=250), [[V], [V]]),
+    (A.AudioFormat(join=True), [[J], [J]]),
+    (A.AudioFormat(8000, "s16le", "raw", 130, 90, True, 250), [[J, S], [J, S, P, V, R]]),
+]
+
+
+def test_a_format_makes_exactly_the_stage_calls_it_needs(sched_eng):
+    """Engine.pcm_convert with every stage of the engine recorded: per format and call the sequence of (stage, slots).
+    A format that does not use a stage never enters it, and the rate / encoding stage runs after another stage only
+    where the format is not 24 kHz f32le."""
+    eng, slots = sched_eng, [2, 0, 3]
+    log = []
+
+    def recorder(name, inner):
+        def call(pcm, slots, *args, **kwargs):
+            log.append((name, [int(s) for s in slots]))
+            return inner(pcm, slots, *args, **kwargs)
+        return call
+
+    xd = torch.from_numpy(make_x()[:, :1280].copy()).to(eng.device)
+    try:
+        for name in STAGES:
+            setattr(eng, name, recorder(name, getattr(eng, name)))
+        for fmt, want in PIPELINES:
+            for k in range(2):
+                del log[:]
+                eng.pcm_convert(xd[:, 640 * k:640 * (k + 1)].contiguous(), slots, [k == 1] * B, fmt)
+                assert log == [(name, slots) for name in want[k]], (fmt, k, log)
+        eng.check_errors()
+    finally:
+        for name in STAGES:
+            eng.__dict__.pop(name, None)
+        for s in slots:
+            eng.pcm_reset(s)

@@ -165,6 +165,28 @@ def test_flush_only_emits_the_rest(eng, x, one_shot, rate):
         assert np.array_equal(again[b], one_shot[rate, "s16le"][b])
 
 
+def test_33_rows_are_two_launches_of_the_same_rows():
+    """One more row than a launch's packet holds, a non-final and a final call: every row's bits, the second
+    launch's row 32 among them, are the numpy rule's."""
+    from llmvox_amd.engine import build_engine
+    e = build_engine(0, "fp32", "fp32", max_streams=40, max_positions=64, max_codec_frames=64)
+    try:
+        rows = 33
+        v = np.random.default_rng(33).uniform(-1, 1, (rows, 1280)).astype(np.float32)
+        slots = [(7 * r + 3) % 40 for r in range(rows)]
+        assert len(set(slots)) == rows
+        for rate, enc in [(16000, "f32le"), (8000, "s16le")]:
+            got, counts = _run(e, v, slots, [640, 640], A.AudioFormat(rate, enc))
+            assert counts == [[A.emitted(rate, 0, 640, False)] * rows, [A.emitted(rate, 640, 640, True)] * rows]
+            want = A.resample_ref(v, rate, e.pcm_filter(rate)[3])
+            if enc == "s16le":
+                want = A.quantize_s16(want)
+            for r in range(rows):
+                assert got[r].dtype == want.dtype and np.array_equal(got[r], want[r]), (rate, enc, r)
+    finally:
+        e.close()
+
+
 def test_argument_errors(eng, x):
     from llmvox_amd import _lib
     lib = eng.lib

@@ -170,6 +170,30 @@ def test_rows_do_not_depend_on_their_neighbours(eng, x, one_shot, pct):
     assert np.array_equal(_bits(np.concatenate(parts)), _bits(want[0]))
 
 
+def test_33_rows_are_two_launches_of_the_same_rows():
+    """One more row than a launch's packet holds, a non-final and a final call: the rows on both sides of the
+    launches' edge, the second launch's row 32 among them, carry the numpy rule's bits."""
+    from llmvox_amd.engine import build_engine
+    e = build_engine(0, "fp32", "fp32", max_streams=40, max_positions=64, max_codec_frames=64)
+    try:
+        rows, pct = 33, 130
+        rng = np.random.default_rng(33)
+        t = np.arange(1280, dtype=np.float64)
+        v = np.stack([0.3 * np.sin(2 * np.pi * t / (90 + 2 * r)) + rng.uniform(-0.1, 0.1, t.size)
+                      for r in range(rows)]).astype(np.float32)
+        slots = [(7 * r + 3) % 40 for r in range(rows)]
+        assert len(set(slots)) == rows
+        got, got_d, counts = _run(e, v, slots, [640, 640], pct)
+        assert counts == [[A.stretch_emitted(pct, 0, 640, False)] * rows, [A.stretch_emitted(pct, 640, 640, True)] * rows]
+        assert counts[0][0] > 0
+        windows = e.pcm_stretch_window()
+        for r in (0, 31, 32):
+            want, want_d = A.stretch_ref(v[r], pct, windows)
+            assert np.array_equal(_bits(got[r]), _bits(want)) and np.array_equal(got_d[r], want_d), r
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize("pct", [77, 130])
 @pytest.mark.parametrize("rate,enc", [(16000, "s16le"), (48000, "f32le")])
 def test_composition_through_pcm_convert(eng, x, windows, rate, enc, pct):
