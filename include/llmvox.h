@@ -278,12 +278,50 @@ int lvx_kv_read(lvx_ctx* ctx, int slot, int layer, int pos0, int n, float* k_dev
  *           partials are copied out as the attention left them, part_o_dev float32 [B][8][16][96] and
  *           part_ml_dev float32 [B][8][16][2] (running max, sum); row b has min(nsplit, ceil((P_b + 1)
  *           / 64)) valid splits, the others are not written. The prologue merges themselves are not
- *           run by this hook: they stay covered at the logit level only.
+ *           run by this hook: lvx_ar_ops runs them (a window from this attention through c_proj).
  * LVX_E_STATE where the plan's attention takes no q rows (the fp32 K-split c_attn; option "exp" 1024
  * selects the one-launch form). form_out is written before the call returns; the device buffers are
  * written in stream order. */
 int lvx_attn_probe(lvx_ctx* ctx, int B, const int32_t* slots_dev, int layer, const float* q_dev, float* out_dev,
                    float* part_o_dev, float* part_ml_dev, int* form_out, void* stream);
+/* Test hook (tests/test_gpu_ar_ops.py): ops [first, last] of ONE decode step on caller-supplied input, each
+ * launched as the step plan at this B under the context's options launches it (the form with the argmax
+ * kernel: no deferred select, no layer-0 record copy), kernel by kernel, never captured into a graph; the
+ * counterpart of lvx_codec_stages for the AR step. It adds nothing to a step.
+ * Ops are numbered 5 * layer + {0 c_attn (layer 0: + embedding), 1 attention, 2 c_proj (+ split merge),
+ * 3 c_fc, 4 mlp c_proj}; op 20 (LVX_AR_OPS - 1) is lm_head. A window starts
+ *   at a layer boundary, first = 5 l: for l >= 1 (and for 20) x_in_dev float32 [B][768] is the final residual
+ *     entering the layer, and the pending mlp c_proj copies are zeroed; for l = 0 the embedding builds x from
+ *     the slots' positions and previous tokens (lvx_stream_set) and text_ids_dev int32 [B], and with
+ *     poison != 0 the pending copies are first filled with the byte 0x7f, which layer 0 must ignore;
+ *   or at an attention, first = 5 l + 1: x_in_dev and q_in_dev float32 [B][768], over the KV rows of the slots
+ *     up to their positions, as lvx_attn_probe (LVX_E_STATE where the plan's attention takes no q rows).
+ * It ends at any op >= first and hands out what that op left, widened exactly to float32:
+ *   LVX_AR_OUT_Q           c_attn: q in out_dev [B][768] (k, v: lvx_kv_read at the slots' positions)
+ *   LVX_AR_OUT_QKV_PARTS   c_attn of the fp32 K split: its four partials, out_dev [4][B][2304]
+ *   LVX_AR_OUT_ATTN_ROWS / LVX_AR_OUT_ATTN_PARTS   attention: forms 0 / 1 of lvx_attn_probe
+ *   LVX_AR_OUT_X           c_proj, mlp c_proj: x in out_dev [B][768]; after mlp c_proj also the info[11]
+ *                          copies the plan holds pending, raw: copies_dev float32 [B][n][768], or, for the
+ *                          fused MLP (info[10]), copies_fx_dev int64 [B][n][768] in 2^-32 fixed point
+ *   LVX_AR_OUT_H           c_fc: gelu(c_fc) in out_dev [B][3072] (LVX_E_STATE inside the fused MLP, which
+ *                          has no c_fc kernel: end at mlp c_proj)
+ *   LVX_AR_OUT_LOGITS      lm_head: out_dev [B][4096]
+ * out_dev holds 4 * B * 2304 floats, copies_dev B * 4 * 768 floats, copies_fx_dev as many int64.
+ * info is int[LVX_AR_INFO], written before the call returns: {output form, path (0 GEMV, 1 LayerNorm-
+ * prologue MFMA, 2 rows kernel + MFMA, 3 v3, 4 fp32 MFMA), fused_mlp, nsplit, attn_direct, attn8, xpk, ksplit,
+ * qsplit, pending copies of the plan, 1 if they are fixed point, copies pending at the exit}. */
+#define LVX_AR_OPS 21
+#define LVX_AR_INFO 12
+#define LVX_AR_OUT_Q 0
+#define LVX_AR_OUT_QKV_PARTS 1
+#define LVX_AR_OUT_ATTN_ROWS 2
+#define LVX_AR_OUT_ATTN_PARTS 3
+#define LVX_AR_OUT_X 4
+#define LVX_AR_OUT_H 5
+#define LVX_AR_OUT_LOGITS 6
+int lvx_ar_ops(lvx_ctx* ctx, int B, const int32_t* slots_dev, int first, int last, const float* x_in_dev,
+               const float* q_in_dev, const int32_t* text_ids_dev, int poison, float* out_dev, float* copies_dev,
+               int64_t* copies_fx_dev, float* part_o_dev, float* part_ml_dev, int* info, void* stream);
 /* Test hook: stages [first, last] of the codec decode on caller-supplied input, through the decode's own
  * launch helpers and scratch (so kernel routing, split-K choice and the split-image decisions are exactly
  * those of lvx_codec_decode_codes at this B, L and these options). Never part of a step or a graph.

@@ -104,6 +104,7 @@ _SIGS = {
     "lvx_kv_write_raw": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "lvx_kv_read": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "lvx_attn_probe": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, ctypes.POINTER(_I), _P]),
+    "lvx_ar_ops": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(_I), _P]),
     "lvx_stream_position": (_I, [_P, _I, ctypes.POINTER(_I), _P]),
     "lvx_set_graphs": (_I, [_P, _I]),
     "lvx_set_capture_stream": (_I, [_P, _P]),
@@ -164,6 +165,9 @@ ERRW_CODEC = 2  # LVX_ERRW_CODEC: the codec's error word
 BIT_NUMERIC = 32  # AR word: the fused MLP's fixed-point range check
 # LVX_ROUTE_*: the GEMM family of a route record of lvx_codec_stages
 ROUTE_MFMA64, ROUTE_BF16_128, ROUTE_GLDS, ROUTE_SKINNY = 0, 1, 2, 3
+# LVX_AR_OUT_*: what a window of lvx_ar_ops hands out; LVX_AR_INFO ints of plan per call
+AR_OUT_Q, AR_OUT_QKV_PARTS, AR_OUT_ATTN_ROWS, AR_OUT_ATTN_PARTS, AR_OUT_X, AR_OUT_H, AR_OUT_LOGITS = range(7)
+AR_OPS, AR_INFO = 21, 12
 CODEC_STAGES = 21  # LVX_CODEC_STAGES
 
 

@@ -3819,12 +3819,31 @@ __global__ __launch_bounds__(256) void attn_probe_rows_kernel(ArState st, int B,
   else out[i] = bf16_to_f32(st.xn[src == 1 ? xfrag(b, e, D) : (size_t)i]);
 }
 
+// After the plan's attention: its merge kernel where it has one (as launch_op's OP_CPROJ runs it), then the
+// normalised rows into `out`. Returns the source the rows were read from (attn_probe_rows_kernel's src), or
+// -1 where the plan merges its partials inside c_proj's prologue (nothing launched).
+static int attn_rows_out(const ArState& st, const ArStepPlan& p, int B, float* out, hipStream_t s) {
+  const bool mf = p.path == PATH_MFMA_LN || p.path == PATH_MFMA_ROWS;
+  int src = -1;
+  if (p.path == PATH_BT) {
+    launch_merge_bf16(st, B, p.nsplit, s);
+    src = 0;
+  } else if (mf && p.nsplit > 1) {
+    launch_merge_bf16(st, B, p.nsplit, s, p.xpk);
+    src = p.xpk ? 1 : 0;
+  } else if (p.attn_direct != ATTN_PARTIALS) {
+    src = p.attn_direct == ATTN_F32_ROWS ? 2 : p.attn_direct == ATTN_XN_PACKED ? 1 : 0;
+  }
+  if (src >= 0) hipLaunchKernelGGL(attn_probe_rows_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, st, B, src, out);
+  return src;
+}
+
 // The production attention of the plan at this B under the bound options, over the q rows in st.q and the
 // slots' current positions (row b attends over keys [0, pos]: what a step at that position sees after its
 // append): the step's own launch (launch_op OP_ATTN) without the layer-0 record copy, then the plan's merge
 // kernel where it has one. The merges inside c_proj's prologue (GIN_MERGE, FIN_MERGE) are NOT run: for
-// those plans the caller gets the partials and merges them itself, so the prologue merges stay covered
-// at the logit level only. info: {form, nsplit, attn_direct, attn8}; form 0: rows in `out`, 1: partials
+// those plans the caller gets the partials and merges them itself (the prologue merges run under ar_ops,
+// window (attention, c_proj) with given q). info: {form, nsplit, attn_direct, attn8}; form 0: rows in `out`, 1: partials
 // left in st.part_o / st.part_ml. Returns 1 where the plan's attention takes no st.q (qsplit).
 int ar_attn_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int layer, float* out,
                   int info[4], hipStream_t s) {
@@ -3836,22 +3855,104 @@ int ar_attn_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
   if (p.bf16) launch_op<bf16_t>(OP_ATTN, a, w, layer, p, s);
   else launch_op<float>(OP_ATTN, a, w, layer, p, s);
-  const bool mf = p.path == PATH_MFMA_LN || p.path == PATH_MFMA_ROWS;
-  int src = -1;  // as launch_op's OP_CPROJ runs the merge kernel
-  if (p.path == PATH_BT) {
-    launch_merge_bf16(st, B, p.nsplit, s);
-    src = 0;
-  } else if (mf && p.nsplit > 1) {
-    launch_merge_bf16(st, B, p.nsplit, s, p.xpk);
-    src = p.xpk ? 1 : 0;
-  } else if (p.attn_direct != ATTN_PARTIALS) {
-    src = p.attn_direct == ATTN_F32_ROWS ? 2 : p.attn_direct == ATTN_XN_PACKED ? 1 : 0;
-  }
-  if (src >= 0) hipLaunchKernelGGL(attn_probe_rows_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, st, B, src, out);
+  const int src = attn_rows_out(st, p, B, out, s);
   info[0] = src >= 0 ? 0 : 1;
   info[1] = p.nsplit;
   info[2] = p.attn_direct;
   info[3] = p.attn8 ? 1 : 0;
+  return 0;
+}
+
+// Test hook (lvx_ar_ops): what the last op of a window left, widened exactly to fp32 (the fused MLP's
+// fixed-point copies: as int64). kind: LVX_AR_OUT_*. Q: st.q. QKV_PARTS: the four K-slice partials of the
+// fp32 K-split c_attn, [4][B][2304]. X: st.x, then the nc pending copies of every row, raw, [B][nc][768]
+// into copies (fp32 st.yacc) or copies_fx (st.yfx). H: hsrc 0 st.h (fp32), 1 st.hb row-major, 2 st.hb
+// fragment-packed (xfrag). LOGITS: st.logits.
+__global__ __launch_bounds__(256) void ar_ops_out_kernel(ArState st, int B, int kind, int hsrc, int nc, int fx,
+                                                         float* __restrict__ out, float* __restrict__ copies,
+                                                         long long* __restrict__ copies_fx) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (kind == LVX_AR_OUT_Q) {
+    if (i < (size_t)B * D) out[i] = st.q[i];
+  } else if (kind == LVX_AR_OUT_QKV_PARTS) {
+    if (i >= (size_t)4 * B * 3 * D) return;
+    const size_t ks = i / ((size_t)B * 3 * D), r = i - ks * B * 3 * D;
+    out[i] = st.qkvp[ks * st.max_streams * (3 * D) + r];
+  } else if (kind == LVX_AR_OUT_X) {
+    if (i < (size_t)B * D) {
+      out[i] = st.x[i];
+    } else if (i < (size_t)B * D * (1 + nc)) {
+      const size_t j = i - (size_t)B * D;
+      if (fx) copies_fx[j] = (long long)st.yfx[j];
+      else copies[j] = st.yacc[j];
+    }
+  } else if (kind == LVX_AR_OUT_H) {
+    if (i >= (size_t)B * DFF) return;
+    const int b = (int)(i / DFF), n = (int)(i % DFF);
+    out[i] = hsrc == 0 ? st.h[i] : bf16_to_f32(st.hb[hsrc == 2 ? xfrag(b, n, DFF) : i]);
+  } else {
+    if (i < (size_t)B * VOCAB) out[i] = st.logits[i];
+  }
+}
+
+// Ops first .. last of one decode step (op 5 l + OP_QKV .. OP_MPROJ of layer l, 20 = lm_head), each launched
+// as the step launches it (launch_op under the plan of ar_plan_step at this B and the bound options, in the
+// argmax-kernel form: sel SEL_ARGMAX, no layer-0 record copy), on caller-given input: the counterpart of
+// codec_launch_stages. Entry at a layer boundary (first = 5 l): l >= 1 (and lm_head alone) start from x_in
+// [B][768] as the final residual with the pending copies zeroed; l = 0 builds x itself (embedding of the
+// slots' positions and previous tokens and st.text_plan, one text id per row), and `poison` first fills
+// the pending copies with the byte 0x7f (a huge finite fp32 / int64), which layer 0 must ignore. Entry at
+// an attention (first = 5 l + 1): x_in and q_in [B][768], over the slots' cache rows up to their positions.
+// After `last`: the plan's merge kernel if last is an attention (as ar_attn_probe), then one copy kernel.
+// info: LVX_AR_INFO ints (llmvox.h). Returns 1 where the window starts at an attention that takes no q
+// rows (qsplit), 2 where it ends at c_fc inside the fused MLP, 0 otherwise.
+int ar_ops(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int first, int last,
+           const float* x_in, const float* q_in, bool poison, float* out, float* copies, long long* copies_fx,
+           int* info, hipStream_t s) {
+  ArStepPlan p = ar_plan_step(opts(), wdtype, kvdtype, B, false, false);
+  p.sel = SEL_ARGMAX;
+  p.selcopy = false;
+  // the pending copies of the plan: the fused MLP's 4 fixed-point accumulators, YCS K slices under the
+  // LayerNorm-prologue GEMMs, 4 under the rows kernel and the fp32 K split
+  const int nc = p.fused_mlp ? YCOPIES : p.path == PATH_MFMA_LN ? (YCS < YCOPIES ? YCS : YCOPIES)
+                 : (p.path == PATH_MFMA_ROWS || p.ksplit) ? YCOPIES : 0;
+  const int op_last = last == 5 * N_LAYER ? OP_LM_HEAD : last % 5;
+  const int kind = op_last == OP_QKV ? (p.qsplit ? LVX_AR_OUT_QKV_PARTS : LVX_AR_OUT_Q)
+                   : op_last == OP_ATTN ? LVX_AR_OUT_ATTN_ROWS
+                   : op_last == OP_FC ? LVX_AR_OUT_H : op_last == OP_LM_HEAD ? LVX_AR_OUT_LOGITS : LVX_AR_OUT_X;
+  info[1] = p.path; info[2] = p.fused_mlp; info[3] = p.nsplit; info[4] = p.attn_direct; info[5] = p.attn8;
+  info[6] = p.xpk; info[7] = p.ksplit; info[8] = p.qsplit; info[9] = nc; info[10] = p.fused_mlp;
+  info[11] = op_last == OP_MPROJ ? nc : 0;  // copies still pending at the exit (c_proj has folded them)
+  if (first % 5 == OP_ATTN && p.qsplit) return 1;
+  if (op_last == OP_FC && p.fused_mlp) return 2;
+  GemvArgs a = make_args<float>(w, st, kvdtype, B, nullptr);
+  a.defer_sel = p.sel;
+  a.dst = st.logits;
+  hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
+  if (first > 0) {
+    hipMemcpyAsync(st.x, x_in, (size_t)B * D * 4, hipMemcpyDeviceToDevice, s);
+    if (first % 5 == OP_ATTN) hipMemcpyAsync(st.q, q_in, (size_t)B * D * 4, hipMemcpyDeviceToDevice, s);
+  }
+  if (first > 0 || poison) {
+    hipMemsetAsync(st.yacc, first > 0 ? 0 : 0x7f, (size_t)B * YCOPIES * D * sizeof(float), s);
+    hipMemsetAsync(st.yfx, first > 0 ? 0 : 0x7f, (size_t)B * YCOPIES * D * sizeof(unsigned long long), s);
+  }
+  for (int i = first; i <= last; ++i) {
+    const int op = i == 5 * N_LAYER ? OP_LM_HEAD : i % 5, l = i == 5 * N_LAYER ? N_LAYER - 1 : i / 5;
+    if (p.bf16) launch_op<bf16_t>(op, a, w, l, p, s);
+    else launch_op<float>(op, a, w, l, p, s);
+  }
+  if (kind == LVX_AR_OUT_ATTN_ROWS) {
+    info[0] = attn_rows_out(st, p, B, out, s) >= 0 ? LVX_AR_OUT_ATTN_ROWS : LVX_AR_OUT_ATTN_PARTS;
+    return 0;
+  }
+  info[0] = kind;
+  const int hsrc = (p.path == PATH_GEMV || p.path == PATH_F32B) ? 0 : p.xpk ? 2 : 1;
+  const size_t n = kind == LVX_AR_OUT_Q ? (size_t)B * D : kind == LVX_AR_OUT_QKV_PARTS ? (size_t)4 * B * 3 * D
+                   : kind == LVX_AR_OUT_X ? (size_t)B * D * (1 + info[11]) : kind == LVX_AR_OUT_H ? (size_t)B * DFF
+                   : (size_t)B * VOCAB;
+  hipLaunchKernelGGL(ar_ops_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, st, B, kind, hsrc, info[11],
+                     p.fused_mlp ? 1 : 0, out, copies, copies_fx);
   return 0;
 }
 

@@ -1174,6 +1174,38 @@ int lvx_attn_probe(lvx_ctx* c, int B, const int32_t* slots, int layer, const flo
   return LVX_OK;
 }
 
+int lvx_ar_ops(lvx_ctx* c, int B, const int32_t* slots, int first, int last, const float* x_in, const float* q_in,
+               const int32_t* text_ids, int poison, float* out, float* copies, int64_t* copies_fx, float* part_o,
+               float* part_ml, int* info, void* stream) {
+  NEED_FINAL(c);
+  if (B < 1 || B > c->cfg.max_streams) return fail(LVX_E_ARG, "B out of range");
+  if (first < 0 || last < first || last >= LVX_AR_OPS) return fail(LVX_E_ARG, "need 0 <= first <= last < LVX_AR_OPS");
+  const bool at_attn = first < 5 * N_LAYER && first % 5 == 1;
+  if (first % 5 != 0 && !at_attn) return fail(LVX_E_ARG, "a window starts at a layer boundary (5 l) or at an attention (5 l + 1)");
+  if (!slots || !out || !copies || !copies_fx || !part_o || !part_ml || !info) return fail(LVX_E_ARG, "null argument");
+  if (first == 0 ? !text_ids : !x_in) return fail(LVX_E_ARG, "layer 0 takes text ids, every other entry x_in");
+  if (at_attn && !q_in) return fail(LVX_E_ARG, "an entry at the attention takes q_in");
+  HIP_TRY(hipSetDevice(c->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  ArState st = c->st;  // no plan bound but the rows' text ids: rowstep / tok_plan stay null
+  st.slots = const_cast<int32_t*>(slots);
+  st.text_plan = first == 0 ? text_ids : nullptr;
+  st.plan_stride = 1;
+  const Opts o = c->opts_snapshot();
+  OptScope os(&o);
+  // launched kernel by kernel, never captured into a graph
+  const int r = ar_ops(c->arw, st, c->cfg.weight_dtype, c->cfg.kv_dtype, B, first, last, x_in, q_in, poison != 0, out,
+                       copies, reinterpret_cast<long long*>(copies_fx), info, s);
+  if (r == 1) return fail(LVX_E_STATE, "the plan's attention at this B takes its q from the K-split c_attn (fp32: set option exp 1024)");
+  if (r == 2) return fail(LVX_E_STATE, "c_fc has no kernel of its own at this B (fused MLP): end the window at mlp c_proj");
+  HIP_TRY(hipGetLastError());
+  if (info[0] == LVX_AR_OUT_ATTN_PARTS) {  // merged in c_proj's prologue: the partials as the kernel left them
+    HIP_TRY(hipMemcpyAsync(part_o, st.part_o, (size_t)B * N_HEAD * NSPLIT * HD * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(part_ml, st.part_ml, (size_t)B * N_HEAD * NSPLIT * 2 * 4, hipMemcpyDeviceToDevice, s));
+  }
+  return LVX_OK;
+}
+
 static int codec_check(lvx_ctx* c, int B, int L, int bw) {
   if (B < 1 || L < 1) return fail(LVX_E_ARG, "B and L must be >= 1");
   if ((long long)B * L > c->cfg.max_codec_frames)

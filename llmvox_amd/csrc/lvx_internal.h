@@ -174,6 +174,10 @@ void ar_launch_kv_read(const ArState& st, int kvdtype, int slot, int layer, int 
                        hipStream_t s);
 int ar_attn_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int layer, float* out,
                   int info[4], hipStream_t s);
+// test hook (lvx_ar_ops): ops first .. last of one step on given input, what the last one left copied out
+int ar_ops(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B, int first, int last,
+           const float* x_in, const float* q_in, bool poison, float* out, float* copies, long long* copies_fx,
+           int* info, hipStream_t s);
 // ArWeights::q0_text / q0_code / q0_pos from the bf16 c_attn weight of layer 0 (lvx_finalize)
 void ar_launch_q0_tables(const ArWeights& w, int max_pos, float* text, float* code, float* pos, hipStream_t s);
 void launch_set_slot(const ArState& st, int slot, int p, int tok, hipStream_t s);

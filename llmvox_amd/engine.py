@@ -195,6 +195,44 @@ class Engine:
         torch.cuda.current_stream(self.device).synchronize()
         return info[0], out, po, pml, (info[1], info[2], info[3])
 
+    def ar_ops(self, slots: torch.Tensor, first: int, last: int, x_in: Optional[torch.Tensor] = None,
+               q_in: Optional[torch.Tensor] = None, text_ids: Optional[torch.Tensor] = None, poison: bool = False):
+        """Test hook: ops ``first .. last`` of one decode step (5 * layer + {0 c_attn, 1 attention, 2 c_proj,
+        3 c_fc, 4 mlp c_proj}, 20 lm_head) as the plan at B = len(slots) launches them, on given input
+        (lvx_ar_ops in llmvox.h): ``x_in`` float32 [B, 768] for every entry but op 0, ``q_in`` for an entry at
+        an attention, ``text_ids`` int32 [B] for op 0. Returns a dict: ``form`` (``_lib.AR_OUT_*``), ``out``
+        (the rows of that form; the K-split partials as [4, B, 2304]), ``copies`` (the pending copies at the
+        exit, float32 or int64 [B, n, 768], n may be 0), ``part_o`` / ``part_ml`` (attention partials) and
+        ``plan``: (path, fused_mlp, nsplit, attn_direct, attn8, xpk, ksplit, qsplit, copies, fixed point).
+        Synchronises the stream."""
+        B = int(slots.numel())
+
+        def rows(t, dtype, shape):
+            if t is None:
+                return None
+            t = t.to(self.device, dtype).contiguous()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"expected a tensor of shape {shape}, got {tuple(t.shape)}")
+            return t
+
+        x_in, q_in = rows(x_in, torch.float32, (B, 768)), rows(q_in, torch.float32, (B, 768))
+        text_ids = rows(text_ids, torch.int32, (B,))
+        out = torch.zeros(4 * B * 2304, device=self.device, dtype=torch.float32)
+        cp = torch.zeros(B, 4, 768, device=self.device, dtype=torch.float32)
+        cfx = torch.zeros(B, 4, 768, device=self.device, dtype=torch.int64)
+        po = torch.zeros(B, 8, 16, 96, device=self.device, dtype=torch.float32)
+        pml = torch.zeros(B, 8, 16, 2, device=self.device, dtype=torch.float32)
+        info = (ctypes.c_int * _lib.AR_INFO)()
+        _lib.check(self.lib.lvx_ar_ops(self.h, B, _ptr(slots), int(first), int(last), _ptr(x_in), _ptr(q_in),
+                                       _ptr(text_ids), int(bool(poison)), _ptr(out), _ptr(cp), _ptr(cfx), _ptr(po),
+                                       _ptr(pml), info, self.stream_handle()))
+        torch.cuda.current_stream(self.device).synchronize()
+        form, n = info[0], info[11]
+        width = {_lib.AR_OUT_H: 3072, _lib.AR_OUT_LOGITS: 4096}.get(form, 768)
+        o = out[:4 * B * 2304].view(4, B, 2304) if form == _lib.AR_OUT_QKV_PARTS else out[:B * width].view(B, width)
+        copies = (cfx if info[10] else cp).view(-1)[:B * n * 768].view(B, n, 768)
+        return dict(form=form, out=o, copies=copies, part_o=po, part_ml=pml, plan=tuple(info[1:11]))
+
     def last_logits(self, B: int) -> torch.Tensor:
         out = torch.empty(B, 4096, device=self.device, dtype=torch.float32)
         _lib.check(self.lib.lvx_ar_logits(self.h, B, _ptr(out), self.stream_handle()))
