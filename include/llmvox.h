@@ -425,7 +425,8 @@ int lvx_codec_decode_codes(lvx_ctx* ctx, const int32_t* codes_dev, int B, int L,
  * asks for nothing never comes here: 24000 Hz f32le is the codec's own output, and lvx_pcm_convert
  * launches nothing for it.
  *
- * Output sample rates: 24000 (no resampling), 16000, 8000, 48000. Encodings: f32le, s16le.
+ * Output sample rates: 24000 (no resampling), 16000, 8000, 48000. Encodings: f32le, s16le, and the 8-bit
+ * G.711 mu-law and A-law of "PCM G.711" below.
  *
  * Resampling is a rational polyphase FIR with fixed L / M (output rate = 24000 L / M):
  *   16000: L / M = 2 / 3, N = 72 (145 prototype taps, <= 73 per output);
@@ -459,6 +460,8 @@ int lvx_codec_decode_codes(lvx_ctx* ctx, const int32_t* codes_dev, int B, int L,
  * not); NaN -> 0. Exact in fp32. 24000 Hz s16le is the same kernel without a filter: elementwise, stateless. */
 #define LVX_PCM_F32LE 0
 #define LVX_PCM_S16LE 1
+#define LVX_PCM_ALAW 6 /* G.711 A-law and mu-law ("PCM G.711" below): the WAVE format tags; 2 .. 5 are no encodings */
+#define LVX_PCM_ULAW 7
 /* host only: L, M, N and the 2 N + 1 fp32 taps h[-N .. N] of a rate (24000: 1, 1, 0 and the tap 1).
  * taps_host may be NULL (only L, M, N). LVX_E_ARG for an unsupported rate or cap < 2 N + 1. */
 int lvx_pcm_filter(int sample_rate, int* L, int* M, int* N, float* taps_host, int cap);
@@ -469,11 +472,12 @@ int lvx_pcm_emitted(int sample_rate, long long t0, int n_in, int final);
 int lvx_pcm_reset(lvx_ctx* ctx, int slot, void* stream);
 /* rows b of pcm_dev [B][n_in] f32 continue the segments of slots_host[b]; final_host[b] != 0 flushes and
  * resets the slot. n_in may be 0 with final (flush only). out row b starts at out_dev + b * out_stride_bytes
- * (int16 or float32 samples); n_out_host[b] = samples written. Host arrays are consumed before the call
- * returns. 24000 Hz f32le: nothing is launched and nothing written, the rows of pcm_dev are the output
- * (n_out_host[b] = n_in; out_dev may be NULL). LVX_E_ARG (and no slot's state changed): a bad rate or
- * encoding, B < 1, n_in < 0, a slot out of range or named twice, out_dev or out_stride_bytes not a
- * multiple of 4, out_stride_bytes smaller than a row's output. */
+ * (float32, int16 or, G.711, uint8 samples); n_out_host[b] = samples written. Host arrays are consumed
+ * before the call returns. 24000 Hz f32le: nothing is launched and nothing written, the rows of pcm_dev are
+ * the output (n_out_host[b] = n_in; out_dev may be NULL). 24000 Hz in another encoding: the kernel without a
+ * filter. LVX_E_ARG (and no slot's state changed): a bad rate or encoding, B < 1, n_in < 0, a slot out of
+ * range or named twice, out_dev or out_stride_bytes not a multiple of 4 (G.711's byte rows too),
+ * out_stride_bytes smaller than a row's output. */
 int lvx_pcm_convert(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
                     const uint8_t* final_host, int sample_rate, int encoding, void* out_dev,
                     long long out_stride_bytes, int32_t* n_out_host, void* stream);
@@ -656,6 +660,36 @@ int lvx_pcm_join_emitted(int open, int ctx_frames, int n_in, int final);
 int lvx_pcm_join(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
                  const int32_t* ctx_frames_host, const uint8_t* final_host, float* out_dev,
                  long long out_stride_bytes, int32_t* n_out_host, void* stream);
+
+/* ---- PCM G.711 ----------------------------------------------------------------
+ * Telephony's encodings: 8-bit mu-law (PCMU, LVX_PCM_ULAW) and A-law (PCMA, LVX_PCM_ALAW), two further
+ * encodings of lvx_pcm_convert at every rate. Integer arithmetic only, so THE DEVICE'S BYTES ARE THOSE OF A HOST
+ * EVALUATION (llmvox_amd/audio.py: g711_encode) and, like every stage but the join, do not depend on how a
+ * sentence was cut into dumps. A per-sample epilogue of the kernel: slot state, history, counts and
+ * lvx_pcm_emitted are those of the other encodings.
+ *
+ * Quantisation first: q is the s16le rule above applied to the fp32 sample (resampled or not), NaN -> 0, the
+ * same clamp. So a G.711 stream's bytes are the G.711 codes of the s16le stream's samples.
+ *
+ * Companding: the ITU-T G.191 STL form. A negative q is taken in one's complement (~q); every shift is
+ * arithmetic on a 32-bit int.
+ *   mu-law:  a = min(((q < 0 ? ~q : q) >> 2) + 33, 0x1FFF);  seg = 1 + the bit length of (a >> 6), so 1 .. 8;
+ *            code = ((8 - seg) << 4) | (0xF - ((a >> seg) & 0xF)), with 0x80 or-ed in when q >= 0.
+ *   A-law:   x = (q < 0 ? ~q : q) >> 4;  if x > 15: e = 1; while x > 31: x >>= 1, e += 1; then
+ *            x = x - 16 + (e << 4);  0x80 or-ed in when q >= 0;  code = x ^ 0x55.
+ * (The loop's e is the bit length of the first x >> 4: the library and the kernel count leading zeros.)
+ * Decoders (host only, for clients and tests):
+ *   mu-law:  m = ~c & 0xFF;  e = (m >> 4) & 7;  step = 4 << (e + 1);
+ *            lin = sgn ((0x80 << e) + step (m & 0xF) + step / 2 - 132),  sgn = -1 for c < 0x80.
+ *   A-law:   i = c ^ 0x55;  e = (i & 0x7F) >> 4;  m = i & 0xF;  if e > 0: m += 16;  m = (m << 4) + 8;
+ *            if e > 1: m <<= e - 1;  negative when (i & 0x80) == 0.
+ * Silence (q = 0) is 0xFF in mu-law and 0xD5 in A-law, not 0. All 256 codes occur; enc(~q) = enc(q) ^ 0x80;
+ * dec(enc(q)) does not decrease with q; enc(dec(c)) = c but for mu-law's 0x7F (negative zero, which decodes
+ * to 0); |dec(enc(q)) - q| <= 512 for A-law and, for mu-law, on |q| <= 32124 (644 at its clip). */
+/* host only: the codes of n s16 samples, and back. encoding: LVX_PCM_ULAW or LVX_PCM_ALAW. LVX_E_ARG: another
+ * encoding, n < 0, a null pointer with n > 0. */
+int lvx_pcm_g711_encode(int encoding, const int16_t* in, long long n, uint8_t* out);
+int lvx_pcm_g711_decode(int encoding, const uint8_t* in, long long n, int16_t* out);
 
 /* ---- PCM level ----------------------------------------------------------------
  * The volume control: a gain followed by a peak limiter, because louder speech clips. It runs AFTER the join,

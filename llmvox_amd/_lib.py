@@ -26,6 +26,8 @@ LVX_DTYPE_BF16 = 1
 LVX_DTYPE_FP8 = 2  # kv_dtype only (OCP e4m3fn)
 LVX_PCM_F32LE = 0
 LVX_PCM_S16LE = 1
+LVX_PCM_ALAW = 6  # G.711: the WAVE format tags
+LVX_PCM_ULAW = 7
 
 DTYPES = {"fp32": LVX_DTYPE_F32, "f32": LVX_DTYPE_F32, "float32": LVX_DTYPE_F32,
           "bf16": LVX_DTYPE_BF16, "bfloat16": LVX_DTYPE_BF16,
@@ -116,6 +118,8 @@ _SIGS = {
     "lvx_pcm_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
     "lvx_pcm_reset": (_I, [_P, _I, _P]),
     "lvx_pcm_convert": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, ctypes.c_longlong, _P, _P]),
+    "lvx_pcm_g711_encode": (_I, [_I, _P, ctypes.c_longlong, _P]),
+    "lvx_pcm_g711_decode": (_I, [_I, _P, ctypes.c_longlong, _P]),
     "lvx_pcm_stretch_window": (_I, [_P, _P, _I]),
     "lvx_pcm_stretch_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
     "lvx_pcm_stretch": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, ctypes.c_longlong, _P, _P, _I, _P]),

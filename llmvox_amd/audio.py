@@ -8,7 +8,8 @@ pitch into a stretch and a resampling ratio L / M, and the resampler of that rat
 rate conversion): ``pitch_plan``, ``ratio_ref``. And the join of a sentence's dumps ("PCM dump join": a held-back
 frame crossfaded with the next dump's rendering of it, in front of the other three): ``join_ref``. And the volume
 control ("PCM level": a gain and a feed-forward peak limiter, between the ratio and the rate conversion):
-``level_ref``."""
+``level_ref``. And the G.711 encodings ("PCM G.711": the s16 quantisation companded to 8-bit mu-law or A-law, integer
+arithmetic only): ``g711_encode``, ``g711_decode``."""
 from __future__ import annotations
 
 import struct
@@ -20,8 +21,13 @@ import numpy as np
 
 BASE_RATE = 24000  # the codec's output rate
 RATES = {24000: (1, 1, 0), 16000: (2, 3, 72), 8000: (1, 3, 72), 48000: (2, 1, 48)}  # rate: (L, M, N)
-ENCODINGS = ("f32le", "s16le")
+ENCODINGS = ("f32le", "s16le", "ulaw", "alaw")
+G711_LAWS = ("ulaw", "alaw")  # the 8-bit companded encodings (LVX_PCM_ULAW, LVX_PCM_ALAW)
+_SAMPLE_DTYPE = {"f32le": np.dtype("<f4"), "s16le": np.dtype("<i2"), "ulaw": np.dtype("u1"), "alaw": np.dtype("u1")}
+_G711_TAG = {"ulaw": 7, "alaw": 6}   # WAVE format tags, the values of LVX_PCM_ULAW / LVX_PCM_ALAW
+_G711_SILENCE = {"ulaw": 0xFF, "alaw": 0xD5}  # the codes of q = 0
 CONTAINERS = ("raw", "wav")
+FRAME_MS = (10, 20, 30, 40, 60)  # the fixed frame durations a request may ask its byte stream to be cut into
 HISTORY = 160  # inputs of history a slot keeps between calls
 SPEED_MIN, SPEED_MAX = 50, 200  # speed_pct of a stream (100: no stretch)
 STRETCH_H = 240         # output hop of the time stretch (10 ms)
@@ -112,11 +118,11 @@ class AudioFormat:
 
     @property
     def sample_bytes(self) -> int:
-        return 2 if self.encoding == "s16le" else 4
+        return _SAMPLE_DTYPE[self.encoding].itemsize
 
     @property
     def dtype(self):
-        return np.dtype("<i2") if self.encoding == "s16le" else np.dtype("<f4")
+        return _SAMPLE_DTYPE[self.encoding]
 
     @property
     def media_type(self) -> str:
@@ -125,7 +131,13 @@ class AudioFormat:
 
 def wav_header(fmt: AudioFormat) -> bytes:
     """The 44-byte RIFF / WAVE header of a mono stream of unknown length: both sizes 0xFFFFFFFF, format
-    tag 1 (integer PCM) or 3 (IEEE float)."""
+    tag 1 (integer PCM) or 3 (IEEE float). G.711 (tag 7 mu-law, 6 A-law) takes the 58-byte form the WAVE
+    specification asks of a non-PCM tag: an 18-byte fmt chunk (cbSize 0) and a fact chunk, its sample count
+    unknown too (0xFFFFFFFF)."""
+    if fmt.encoding in G711_LAWS:
+        return (b"RIFF" + struct.pack("<I", 0xFFFFFFFF) + b"WAVE" + b"fmt "
+                + struct.pack("<IHHIIHHH", 18, _G711_TAG[fmt.encoding], 1, fmt.sample_rate, fmt.sample_rate, 1, 8, 0)
+                + b"fact" + struct.pack("<II", 4, 0xFFFFFFFF) + b"data" + struct.pack("<I", 0xFFFFFFFF))
     tag, nbytes = (1, 2) if fmt.encoding == "s16le" else (3, 4)
     return (b"RIFF" + struct.pack("<I", 0xFFFFFFFF) + b"WAVE" + b"fmt "
             + struct.pack("<IHHIIHH", 16, tag, 1, fmt.sample_rate, fmt.sample_rate * nbytes, nbytes, 8 * nbytes)
@@ -250,7 +262,102 @@ def quantize_s16(v) -> np.ndarray:
         return np.where(np.isnan(v), np.float32(0), np.rint(s)).astype(np.int16)
 
 
+# ---- the G.711 rule (include/llmvox.h, "PCM G.711"), in numpy: integers only ---------------------------
+
+def _bit_length7(t) -> np.ndarray:
+    """The bit length of t, an int32 array in 0 .. 127."""
+    n = np.zeros_like(t)
+    for k in range(7):
+        n += (t >> k) > 0
+    return n
+
+
+def _check_law(law: str):
+    if law not in G711_LAWS:
+        raise ValueError(f"law must be one of {G711_LAWS}, got {law!r}")
+
+
+def g711_encode(q, law: str) -> np.ndarray:
+    """The 8-bit codes (uint8) of the s16 samples q at ``law`` ("ulaw" / "alaw"): the ITU-T G.191 STL form, a
+    negative q taken in one's complement (``lvx_pcm_g711_encode``; the device's epilogue after ``quantize_s16``)."""
+    _check_law(law)
+    q = np.asarray(q)
+    if q.dtype.kind not in "iu" or (q.size and (q.min() < -32768 or q.max() > 32767)):
+        raise ValueError("q must hold integers in -32768 .. 32767")
+    q = q.astype(np.int32)
+    sign = np.where(q >= 0, 0x80, 0).astype(np.int32)
+    m = np.where(q >= 0, q, ~q)
+    if law == "ulaw":
+        a = np.minimum((m >> 2) + 33, 0x1FFF)
+        seg = 1 + _bit_length7(a >> 6)
+        return (((8 - seg) << 4) | (0xF - ((a >> seg) & 0xF)) | sign).astype(np.uint8)
+    x = m >> 4
+    e = _bit_length7(x >> 4)  # 0: x <= 15, the linear segment; else the loop's e
+    x = np.where(e > 0, (x >> np.maximum(e - 1, 0)) - 16 + (e << 4), x)
+    return ((x | sign) ^ 0x55).astype(np.uint8)
+
+
+def g711_decode(codes, law: str) -> np.ndarray:
+    """The s16 samples (int16) of the 8-bit codes at ``law`` (``lvx_pcm_g711_decode``): host only, what a client
+    does with the stream."""
+    _check_law(law)
+    c = np.asarray(codes)
+    if c.dtype.kind not in "iu" or (c.size and (c.min() < 0 or c.max() > 255)):
+        raise ValueError("codes must hold integers in 0 .. 255")
+    c = c.astype(np.int32)
+    if law == "ulaw":
+        m = ~c & 0xFF
+        e = (m >> 4) & 7
+        step = 4 << (e + 1)
+        lin = (0x80 << e) + step * (m & 0xF) + step // 2 - 132
+        return np.where(c < 0x80, -lin, lin).astype(np.int16)
+    i = c ^ 0x55
+    e = (i & 0x7F) >> 4
+    m = (((i & 0xF) + np.where(e > 0, 16, 0)) << 4) + 8
+    m = np.where(e > 1, m << np.maximum(e - 1, 0), m)
+    return np.where(i & 0x80, m, -m).astype(np.int16)
+
+
+def silence_byte(fmt) -> int:
+    """The byte a stream of ``fmt`` (an AudioFormat or an encoding's name) is padded with: the G.711 code of
+    q = 0 (0xFF mu-law, 0xD5 A-law); 0 for the PCM encodings, whose zero sample is zero bytes."""
+    return _G711_SILENCE.get(getattr(fmt, "encoding", fmt), 0)
+
+
+def frame_ms_of(v) -> Optional[int]:
+    """A request's frame duration: None (today's chunking) or one of FRAME_MS, an integer; ValueError for anything
+    else, a bool and a float included."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, int) or v not in FRAME_MS:
+        raise ValueError(f"frame_ms must be one of {FRAME_MS} or null, got {v!r}")
+    return v
+
+
+def frame_bytes(fmt: AudioFormat, frame_ms: int) -> int:
+    """Bytes of one frame of ``frame_ms`` milliseconds of ``fmt``: a whole number at every rate and duration."""
+    return fmt.sample_rate * frame_ms_of(frame_ms) // 1000 * fmt.sample_bytes
+
+
+def frame_chunks(chunks, fmt: AudioFormat, frame_ms: int):
+    """The byte chunks of a stream of ``fmt`` re-cut on the host into whole frames of ``frame_ms`` milliseconds:
+    every chunk yielded is a multiple of ``frame_bytes``; what a chunk leaves over waits for the next one; at the
+    end the last partial frame is filled with the encoding's silence (``silence_byte``). The concatenation is the
+    input's, then that fill."""
+    size, rest = frame_bytes(fmt, frame_ms), b""
+    for c in chunks:
+        rest += c
+        n = len(rest) // size * size
+        if n:
+            yield rest[:n]
+            rest = rest[n:]
+    if rest:
+        yield rest + bytes([silence_byte(fmt)]) * (size - len(rest))
+
+
 def encode_ref(y, fmt: AudioFormat) -> np.ndarray:
+    if fmt.encoding in G711_LAWS:
+        return g711_encode(quantize_s16(y), fmt.encoding)
     return quantize_s16(y) if fmt.encoding == "s16le" else np.asarray(y, dtype=np.float32)
 
 
@@ -498,8 +605,8 @@ def level_ref(x, volume_pct: int, window=None, n0: int = 0, n1: Optional[int] = 
 
 
 def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, level_win=None) -> np.ndarray:
-    """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, volume, rate and encoding (int16 or
-    float32 array): stretched at the plan's stretch_pct, resampled by its L / M, levelled at its volume_pct, then
+    """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, volume, rate and encoding (a float32,
+    int16 or uint8 array): stretched at the plan's stretch_pct, resampled by its L / M, levelled at its volume_pct, then
     resampled to the rate and encoded. ``ratio_taps``: the fp32 table of the format's ratio (default: designed
     here); ``level_win``: the level stage's fp32 window (default: built here)."""
     stretch, (L, M) = fmt.stretch_pct, fmt.ratio
@@ -597,7 +704,8 @@ class StreamRef:
 
 
 __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "resample_ref", "quantize_s16",
-           "convert_ref", "StreamRef", "RATES", "ENCODINGS", "CONTAINERS", "BASE_RATE", "HISTORY",
+           "convert_ref", "StreamRef", "RATES", "ENCODINGS", "G711_LAWS", "g711_encode", "g711_decode", "silence_byte",
+           "FRAME_MS", "frame_ms_of", "frame_bytes", "frame_chunks", "CONTAINERS", "BASE_RATE", "HISTORY",
            "stretch_window", "stretch_ref", "stretch_emitted", "stretch_emitted_upto", "SPEED_MIN", "SPEED_MAX",
            "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY", "pitch_plan", "ratio_design", "ratio_emitted",
            "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY",

@@ -1297,10 +1297,10 @@ int lvx_pcm_convert(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t
   NEED_FINAL(c);
   const PcmRate* pr = pcm_rate_of(sample_rate);
   if (!pr) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate) + " (24000, 16000, 8000, 48000)");
-  if (encoding != LVX_PCM_F32LE && encoding != LVX_PCM_S16LE) return fail(LVX_E_ARG, "encoding must be LVX_PCM_F32LE or LVX_PCM_S16LE");
+  const int bps = pcm_sample_bytes(encoding);
+  if (!bps) return fail(LVX_E_ARG, "encoding must be LVX_PCM_F32LE, LVX_PCM_S16LE, LVX_PCM_ULAW or LVX_PCM_ALAW");
   const bool launch = !(pr->N == 0 && encoding == LVX_PCM_F32LE);  // 24000 Hz f32le: the rows are the output
   if (int r = pcm_args(B, n_in, pcm, slots && final_host && n_out_host ? slots : nullptr, launch, out, out_stride)) return r;
-  const int bps = encoding == LVX_PCM_S16LE ? 2 : 4;
   std::vector<PcmRow> rows;
   {
     std::lock_guard<std::mutex> lk(c->mu);
@@ -1316,6 +1316,17 @@ int lvx_pcm_convert(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t
     pcm_launch_convert(sample_rate, encoding, pk, nr, max_out, pcm, n_in, c->pcm_taps + pr->tap_off, c->pcm_hist, out, out_stride,
                        (hipStream_t)stream);
   });
+}
+
+// ---- PCM G.711 (host only) ----
+int lvx_pcm_g711_encode(int encoding, const int16_t* in, long long n, uint8_t* out) {
+  if (g711_encode(encoding, in, n, out)) return fail(LVX_E_ARG, "encoding must be LVX_PCM_ULAW or LVX_PCM_ALAW, n >= 0, in / out not null");
+  return LVX_OK;
+}
+
+int lvx_pcm_g711_decode(int encoding, const uint8_t* in, long long n, int16_t* out) {
+  if (g711_decode(encoding, in, n, out)) return fail(LVX_E_ARG, "encoding must be LVX_PCM_ULAW or LVX_PCM_ALAW, n >= 0, in / out not null");
+  return LVX_OK;
 }
 
 // ---- PCM time stretch ----

@@ -1,7 +1,8 @@
 // Host side of the PCM stages (include/llmvox.h: "PCM output stage", "PCM time stretch", "PCM pitch shift", "PCM dump
-// join", "PCM level"): the stages' constants and kernel row packets, the tables and streaming counts of llmvox.h's
-// rules in double, and the one skeleton every stage's entry point runs (lvx_api.cpp). No HIP header and no device:
-// tests/host/pcm_stage_check.cpp drives all of it with the system compiler.
+// join", "PCM level", "PCM G.711"): the stages' constants and kernel row packets, the tables and streaming counts of
+// llmvox.h's rules in double, the G.711 companding, and the one skeleton every stage's entry point runs (lvx_api.cpp).
+// No HIP header and no device: tests/host/pcm_stage_check.cpp and g711_check.cpp drive all of it with the system
+// compiler.
 #pragma once
 #include <stdint.h>
 
@@ -232,6 +233,67 @@ inline void level_design(float* w) {
 inline long long level_emitted_upto(int pct, long long T, bool final) {
   if (pct == 100 || final) return T;
   return std::max(0ll, T - 2 * LVL_A);
+}
+
+// ---- PCM G.711: the companding of an s16 sample and its inverse (llmvox.h), integers only ----
+// constexpr and nothing else: one statement for the host entries below and for pcm_convert_kernel's epilogue (a
+// constexpr function is callable from device code as it stands). The segment comes from the bit length, by a count of
+// leading zeros (one instruction on the device), not from llmvox.h's loops.
+constexpr int g711_bit_length(int t) { return 31 - __builtin_clz(2u * (unsigned)t + 1u); }  // of t >= 0 (0: 0)
+
+constexpr int g711_ulaw(int q) {  // q in [-32768, 32767] -> the code, 0 .. 255
+  const int b = ((q < 0 ? ~q : q) >> 2) + 33, a = b < 0x1FFF ? b : 0x1FFF;
+  const int seg = 1 + g711_bit_length(a >> 6);  // 1 .. 8
+  return ((8 - seg) << 4) | (0xF - ((a >> seg) & 0xF)) | (q >= 0 ? 0x80 : 0);
+}
+
+constexpr int g711_alaw(int q) {
+  int x = (q < 0 ? ~q : q) >> 4;
+  const int e = g711_bit_length(x >> 4);  // 0: x <= 15, the linear segment; else the e of llmvox.h's loop, 1 .. 7
+  if (e > 0) x = (x >> (e - 1)) - 16 + (e << 4);
+  return (x | (q >= 0 ? 0x80 : 0)) ^ 0x55;
+}
+
+constexpr int g711_ulaw_linear(int c) {  // c in [0, 255] -> the s16 sample
+  const int m = ~c & 0xFF, e = (m >> 4) & 7, step = 4 << (e + 1);
+  const int lin = (0x80 << e) + step * (m & 0xF) + step / 2 - 132;
+  return c < 0x80 ? -lin : lin;
+}
+
+constexpr int g711_alaw_linear(int c) {
+  const int i = c ^ 0x55, e = (i & 0x7F) >> 4;
+  int m = i & 0xF;
+  if (e > 0) m += 16;
+  m = (m << 4) + 8;
+  if (e > 1) m <<= e - 1;
+  return (i & 0x80) ? m : -m;
+}
+
+template <int ENC> constexpr int g711_code(int q) { return ENC == LVX_PCM_ULAW ? g711_ulaw(q) : g711_alaw(q); }
+constexpr bool is_g711(int encoding) { return encoding == LVX_PCM_ULAW || encoding == LVX_PCM_ALAW; }
+
+// lvx_pcm_g711_encode / lvx_pcm_g711_decode: LVX_OK, or LVX_E_ARG for another encoding, n < 0, a null pointer with n > 0
+inline int g711_encode(int encoding, const int16_t* in, long long n, uint8_t* out) {
+  if (!is_g711(encoding) || n < 0 || (n > 0 && (!in || !out))) return LVX_E_ARG;
+  if (encoding == LVX_PCM_ULAW)
+    for (long long i = 0; i < n; ++i) out[i] = (uint8_t)g711_ulaw(in[i]);
+  else
+    for (long long i = 0; i < n; ++i) out[i] = (uint8_t)g711_alaw(in[i]);
+  return LVX_OK;
+}
+
+inline int g711_decode(int encoding, const uint8_t* in, long long n, int16_t* out) {
+  if (!is_g711(encoding) || n < 0 || (n > 0 && (!in || !out))) return LVX_E_ARG;
+  if (encoding == LVX_PCM_ULAW)
+    for (long long i = 0; i < n; ++i) out[i] = (int16_t)g711_ulaw_linear(in[i]);
+  else
+    for (long long i = 0; i < n; ++i) out[i] = (int16_t)g711_alaw_linear(in[i]);
+  return LVX_OK;
+}
+
+// bytes of one output sample of an encoding lvx_pcm_convert takes; 0: not one
+constexpr int pcm_sample_bytes(int encoding) {
+  return encoding == LVX_PCM_F32LE ? 4 : encoding == LVX_PCM_S16LE ? 2 : is_g711(encoding) ? 1 : 0;
 }
 
 // ---------------- the skeleton of a stage's call ----------------

@@ -1,6 +1,7 @@
 // PCM output stage (include/llmvox.h, "PCM output stage"): rational polyphase resampling of the codec's
-// 24 kHz fp32 rows to 16 / 8 / 48 kHz and the s16le quantisation, one kernel family templated on
-// (L, M, N, encoding). Launched only for a stream that asked for another format than f32le at 24 kHz.
+// 24 kHz fp32 rows to 16 / 8 / 48 kHz and the s16le quantisation or, behind it, the G.711 companding
+// ("PCM G.711": 8-bit mu-law / A-law), one kernel family templated on (L, M, N, encoding). Launched only
+// for a stream that asked for another format than f32le at 24 kHz.
 // And the speaking-rate control in front of it ("PCM time stretch"): WSOLA on the 24 kHz rows, one block
 // per row, launched only for a stream that asked for another speed. And the pitch control between the two
 // ("PCM pitch shift"): the same polyphase rule with a run-time L / M, launched only for a pitched stream.
@@ -18,7 +19,7 @@ namespace lvx {
 namespace {
 
 constexpr int PCM_THREADS = 256;
-constexpr int PCM_PER_THREAD = 4;                        // consecutive outputs of a thread: one 8 / 16 byte store
+constexpr int PCM_PER_THREAD = 4;                        // consecutive outputs of a thread: one 4 / 8 / 16 byte store
 constexpr int PCM_OB = PCM_THREADS * PCM_PER_THREAD;     // outputs of a block
 
 // q = rint(clamp(v * 32768, -32768, 32767)), half to even (v_rndne_f32), NaN -> 0. v * 32768 is exact
@@ -140,6 +141,19 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_convert_kernel(PcmRows rows, 
       for (int e = 0; e < PCM_PER_THREAD; ++e)
         if (ml + e < nb) o[e] = (int16_t)pcm_q16(v[e]);
     }
+  } else if constexpr (is_g711(ENC)) {
+    // llmvox.h, "PCM G.711": the s16 quantisation, then the companding in integer ops (pcm_host.h's statement of it,
+    // the one the host entries run). A thread's four codes are one dword: its address is 4-aligned by construction
+    // (the row base and the stride are multiples of 4, and so is mb + ml).
+    uint8_t* o = orow + mb + ml;
+    if (ml + PCM_PER_THREAD <= nb) {
+      *reinterpret_cast<uint32_t*>(o) = (uint32_t)g711_code<ENC>(pcm_q16(v[0])) | ((uint32_t)g711_code<ENC>(pcm_q16(v[1])) << 8) |
+                                        ((uint32_t)g711_code<ENC>(pcm_q16(v[2])) << 16) | ((uint32_t)g711_code<ENC>(pcm_q16(v[3])) << 24);
+    } else {
+#pragma unroll
+      for (int e = 0; e < PCM_PER_THREAD; ++e)
+        if (ml + e < nb) o[e] = (uint8_t)g711_code<ENC>(pcm_q16(v[e]));
+    }
   } else {
     store4(reinterpret_cast<float*>(orow) + mb + ml, v, ml, nb);
   }
@@ -152,6 +166,12 @@ void launch_enc(const PcmRows& rows, int n_rows, int max_out, int enc, const flo
   if (enc == LVX_PCM_S16LE)
     pcm_convert_kernel<L, M, N, LVX_PCM_S16LE><<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, taps, hist,
                                                                             (unsigned char*)out, out_stride);
+  else if (enc == LVX_PCM_ULAW)
+    pcm_convert_kernel<L, M, N, LVX_PCM_ULAW><<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, taps, hist,
+                                                                           (unsigned char*)out, out_stride);
+  else if (enc == LVX_PCM_ALAW)
+    pcm_convert_kernel<L, M, N, LVX_PCM_ALAW><<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, taps, hist,
+                                                                           (unsigned char*)out, out_stride);
   else
     pcm_convert_kernel<L, M, N, LVX_PCM_F32LE><<<grid, PCM_THREADS, 0, s>>>(rows, pcm, n_in, taps, hist,
                                                                             (unsigned char*)out, out_stride);

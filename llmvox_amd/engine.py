@@ -475,7 +475,7 @@ class Engine:
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
         ``audio.AudioFormat`` (its speed, pitch, volume, rate and encoding). Returns (out, counts): a device tensor
-        [B, width] of int16 or float32 whose row b holds counts[b] samples. Five stages in this order, each only
+        [B, width] of float32, int16 or (G.711) uint8 whose row b holds counts[b] samples. Five stages in this order, each only
         where the format needs it, so that a format makes exactly the calls of the stages it uses: the dump join
         (lvx_pcm_join, a format with ``join``: row b with ``ctx_frames[b]`` frames of context in front, None: none
         anywhere), the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the plan's L / M
@@ -501,7 +501,7 @@ class Engine:
         # segment still has to advance).
         if not stages or not (fmt.sample_rate == 24000 and fmt.encoding == "f32le"):
             stages.append(lambda sub, sl, fl: self._pcm_resample(sub, sl, fl, fmt))
-        dtype = torch.int16 if fmt.encoding == "s16le" else torch.float32
+        dtype = _PCM_ENCODINGS[fmt.encoding][1]
 
         def run(i, sub, sl, fl):  # stage i and, grouped by what it hands on, the stages behind it
             out, cnt = stages[i](sub, sl, fl)
@@ -539,20 +539,38 @@ class Engine:
     def _pcm_resample(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
         """pcm_convert without the speed and the pitch: the rate and the encoding (lvx_pcm_convert)."""
         pcm, n_in, B, sl, fl, cnt, same = self._pcm_args(pcm, slots, finals)
-        s16 = fmt.encoding == "s16le"
-        if fmt.sample_rate == 24000 and not s16:  # 24 kHz f32le: the rows are the output (nothing is launched)
+        enc, dtype = _PCM_ENCODINGS[fmt.encoding]
+        if fmt.sample_rate == 24000 and fmt.encoding == "f32le":  # the rows are the output (nothing is launched)
             out, width = same, n_in
         else:
             L, M, N = (ctypes.c_int() for _ in range(3))
             _lib.check(self.lib.lvx_pcm_filter(fmt.sample_rate, ctypes.byref(L), ctypes.byref(M), ctypes.byref(N), None, 0))
             # a call emits at most (n_in L + L + N) / M + 2 samples (a final call of a segment whose earlier
-            # outputs waited for their right-hand inputs); rows start on 16-byte boundaries
-            width = ((n_in * L.value + L.value + N.value) // M.value + 3 + 7) // 8 * 8
-            out = torch.empty(B, width, device=self.device, dtype=torch.int16 if s16 else torch.float32)
-        _lib.check(self.lib.lvx_pcm_convert(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, fmt.sample_rate,
-                                            _lib.LVX_PCM_S16LE if s16 else _lib.LVX_PCM_F32LE, _ptr(out),
-                                            width * (2 if s16 else 4), cnt, self.stream_handle()))
+            # outputs waited for their right-hand inputs); rows start on 16-byte boundaries at any sample size, one
+            # byte included (a multiple of 16 elements)
+            width = ((n_in * L.value + L.value + N.value) // M.value + 3 + 15) // 16 * 16
+            out = torch.empty(B, width, device=self.device, dtype=dtype)
+        _lib.check(self.lib.lvx_pcm_convert(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, fmt.sample_rate, enc,
+                                            _ptr(out), width * out.element_size(), cnt, self.stream_handle()))
         return out, list(cnt)
+
+    def _g711(self, fn, src, law: str, src_dtype, dst_dtype):
+        if law not in ("ulaw", "alaw"):
+            raise ValueError(f"law must be 'ulaw' or 'alaw', got {law!r}")
+        src = np.ascontiguousarray(src, dtype=src_dtype)
+        dst = np.empty(src.shape, dtype=dst_dtype)
+        _lib.check(fn(_PCM_ENCODINGS[law][0], src.ctypes.data_as(ctypes.c_void_p), src.size,
+                      dst.ctypes.data_as(ctypes.c_void_p)))
+        return dst
+
+    def g711_encode(self, q, law: str):
+        """The G.711 codes (uint8) of the int16 samples ``q`` at ``law`` ("ulaw" / "alaw"), on the host
+        (lvx_pcm_g711_encode): the companding the device applies behind its s16 quantisation."""
+        return self._g711(self.lib.lvx_pcm_g711_encode, q, law, np.int16, np.uint8)
+
+    def g711_decode(self, codes, law: str):
+        """The int16 samples of the G.711 ``codes`` (uint8) at ``law``, on the host (lvx_pcm_g711_decode)."""
+        return self._g711(self.lib.lvx_pcm_g711_decode, codes, law, np.uint8, np.int16)
 
     def close(self):
         if getattr(self, "h", None):
@@ -564,6 +582,11 @@ class Engine:
             self.close()
         except Exception:
             pass
+
+
+# an audio.AudioFormat's encoding: (the LVX_PCM_* value, the dtype of the rows lvx_pcm_convert writes)
+_PCM_ENCODINGS = {"f32le": (_lib.LVX_PCM_F32LE, torch.float32), "s16le": (_lib.LVX_PCM_S16LE, torch.int16),
+                  "ulaw": (_lib.LVX_PCM_ULAW, torch.uint8), "alaw": (_lib.LVX_PCM_ALAW, torch.uint8)}
 
 
 def build_engine(device_index=0, weight_dtype="fp32", kv_dtype="fp32", seed=1234, max_streams=8,

@@ -317,14 +317,20 @@ class TTSService:
                 w.end(s, error=e)
                 w.lock.notify_all()
 
-    def chunks(self, session: _Session, timeout: float = 0.05):
+    def chunks(self, session: _Session, timeout: float = 0.05, frame_ms: Optional[int] = None):
+        """``frame_ms`` (one of ``audio.FRAME_MS``): the body behind the WAV header is re-cut on the host into whole
+        frames of that duration, the last one filled with the encoding's silence (``audio.frame_chunks``); None:
+        the scheduler's chunks as they come."""
         w = session.worker
         try:
             if session.audio is not None and session.audio.container == "wav":
                 from .audio import wav_header
                 yield wav_header(session.audio)
-            for item in audio_chunks(session.queues[0], session.queues[1], timeout=timeout,
-                                     stop=lambda: w.error is not None):
+            body = audio_chunks(session.queues[0], session.queues[1], timeout=timeout, stop=lambda: w.error is not None)
+            if frame_ms is not None:
+                from .audio import AudioFormat, frame_chunks
+                body = frame_chunks(body, session.audio if session.audio is not None else AudioFormat(), frame_ms)
+            for item in body:
                 yield item
         finally:
             self.close(session)
@@ -389,7 +395,7 @@ def volume_pct_of(volume) -> int:
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
                encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
                min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0,
-               join: bool = False, volume: float = 1.0):
+               join: bool = False, volume: float = 1.0, frame_ms: Optional[int] = None):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -401,7 +407,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     controls of ``sampling.Sampling`` (include/llmvox.h, lvx_stream_sampling_ex); a field it leaves out takes the
     default given here; out of range: 422. A request
     may also name its audio format: ``sample_rate`` (24000, 16000, 8000, 48000), ``encoding`` ("f32le",
-    "s16le") and ``container`` ("raw", "wav": a 44-byte header of a stream of unknown length first); a
+    "s16le", "ulaw", "alaw") and ``container`` ("raw", "wav": a 44-byte header of a stream of unknown length first); a
     field it leaves out takes the default given here; invalid values: 422. The response says what it
     carries in ``X-Audio-Sample-Rate`` / ``X-Audio-Encoding`` and its media type (audio/wav for the wav
     container). ``speed`` (a float in 0.5 .. 2.0; 1.0: as spoken) is the speaking rate: the PCM is
@@ -417,19 +423,28 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     (a float in 0.0 .. 4.0; 1.0: as spoken; a bool, a non-number, a non-finite or an out-of-range value: 422) is the
     loudness: the PCM is multiplied by round(volume * 100) percent and peak-limited at -1 dBFS on the device
     (``audio.level_ref``), which holds back 10 ms of every sentence until its end; the response carries it in
-    ``X-Audio-Volume``. The reference's /voicechat, /multimodalchat and /vlmschat differ from /tts only in the
+    ``X-Audio-Volume``. ``encoding`` also takes "ulaw" and "alaw": 8-bit G.711, the s16le samples companded on the
+    device (``audio.g711_encode``), at any of the four rates; their WAV header is the 58-byte form of a non-PCM tag.
+    ``frame_ms`` (10, 20, 30, 40 or 60; null or absent: the chunks as they come; anything else, a bool or a float
+    included: 422) cuts the body behind the WAV header, on the host, into chunks of whole frames of that duration, the
+    last frame filled with the encoding's silence (``audio.frame_chunks``); it reaches ``service.chunks`` as a keyword,
+    never ``submit``; the response carries it in ``X-Audio-Frame-Ms`` (0 without).
+    The reference's /voicechat, /multimodalchat and /vlmschat differ from /tts only in the
     producer (ASR / multimodal LLM, out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
     from fastapi.responses import StreamingResponse
+    from typing import Any
+
     from pydantic import BaseModel, StrictBool, StrictFloat, StrictInt
 
-    from .audio import AudioFormat
+    from .audio import AudioFormat, frame_ms_of
     from .sampling import Sampling
     Sampling(temperature, top_k, 0, top_p, min_p, repetition_penalty, repetition_window)  # (validated at start-up)
     extra_defaults = {"top_p": top_p, "min_p": min_p, "repetition_penalty": repetition_penalty,
                       "repetition_window": repetition_window}
     default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join,
                                 volume_pct_of(volume))
+    default_frame_ms = frame_ms_of(frame_ms)
 
     class TTSRequest(BaseModel):
         text: str
@@ -447,6 +462,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         pitch: Optional[float] = None
         join: Optional[StrictBool] = None
         volume: Optional[Union[StrictInt, StrictFloat]] = None  # (strict: true / false are not numbers here)
+        frame_ms: Any = None  # (checked by frame_ms_of: an integer of audio.FRAME_MS, no bool, no float)
 
     def audio_of(request):
         """The request's AudioFormat (the defaults for the fields it does not name)."""
@@ -458,6 +474,13 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                default_audio.pitch_pct if request.pitch is None else pitch_pct_of(request.pitch),
                                default_audio.join if request.join is None else request.join,
                                default_audio.volume_pct if request.volume is None else volume_pct_of(request.volume))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+
+    def frames_of(request):
+        """The request's frame duration in ms (the server's default where it names none), or None."""
+        try:
+            return default_frame_ms if request.frame_ms is None else frame_ms_of(request.frame_ms)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -493,6 +516,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     def tts(request: TTSRequest):
         sp = sampling_of(request)
         fmt = audio_of(request)
+        ms = frames_of(request)
         kw = {} if sp is None else {"sampling": sp}
         if not fmt.is_default:  # (a default request reaches submit exactly as it always did)
             kw["audio"] = fmt
@@ -500,12 +524,15 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
             session = service.submit(request.text, **kw)
         except RuntimeError as e:
             raise HTTPException(status_code=503, detail=str(e))
-        return StreamingResponse(service.chunks(session), media_type=fmt.media_type,
+        # (framing is the host's business: it reaches chunks, and only when a frame size was named)
+        body = service.chunks(session) if ms is None else service.chunks(session, frame_ms=ms)
+        return StreamingResponse(body, media_type=fmt.media_type,
                                  headers={"X-Audio-Sample-Rate": str(fmt.sample_rate), "X-Audio-Encoding": fmt.encoding,
                                           "X-Audio-Speed": f"{fmt.speed_pct / 100:.2f}",
                                           "X-Audio-Pitch": f"{fmt.speed_pct / fmt.stretch_pct:.4f}",
                                           "X-Audio-Join": "1" if fmt.join else "0",
-                                          "X-Audio-Volume": f"{fmt.volume_pct / 100:.2f}"})
+                                          "X-Audio-Volume": f"{fmt.volume_pct / 100:.2f}",
+                                          "X-Audio-Frame-Ms": str(ms or 0)})
 
     @app.get("/health")
     def health():
@@ -545,7 +572,10 @@ def arg_parser():
     ap.add_argument("--repetition-window", type=int, default=64, help="how many recent tokens it covers (1 .. 256)")
     ap.add_argument("--sample-rate", type=int, default=24000, choices=[24000, 16000, 8000, 48000],
                     help="output sample rate of requests that name none")
-    ap.add_argument("--encoding", default="f32le", choices=["f32le", "s16le"], help="their sample encoding")
+    ap.add_argument("--encoding", default="f32le", choices=["f32le", "s16le", "ulaw", "alaw"],
+                    help="their sample encoding (ulaw / alaw: 8-bit G.711)")
+    ap.add_argument("--frame-ms", type=int, default=None, choices=[10, 20, 30, 40, 60],
+                    help="cut the body of requests that name no frame_ms into whole frames of this duration (default: no framing)")
     ap.add_argument("--container", default="raw", choices=["raw", "wav"], help="their container (wav: a header first)")
     ap.add_argument("--speed", type=float, default=1.0,
                     help="speaking rate of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
@@ -563,7 +593,7 @@ def app_options(a) -> dict:
     return dict(temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate, encoding=a.encoding,
                 container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
                 repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch,
-                join=a.join, volume=a.volume)
+                join=a.join, volume=a.volume, frame_ms=a.frame_ms)
 
 
 def main(argv=None):

@@ -672,8 +672,8 @@ class FusedScheduler:
         engine's ``set_sampling`` is never called.
         audio: an ``audio.AudioFormat`` with another speed, pitch, volume, rate or encoding than f32le at 24 kHz as
         spoken: every dump of the stream is converted on the device (``Engine.pcm_convert``), behind its codec call on the same
-        stream, each sentence as a signal of its own, and the stream's items are those samples (int16 /
-        float32 arrays with ``to_bytes=False``). None (or 24 kHz f32le): today's items, and the engine's
+        stream, each sentence as a signal of its own, and the stream's items are those samples (float32,
+        int16 or, G.711, uint8 arrays with ``to_bytes=False``). None (or 24 kHz f32le): today's items, and the engine's
         ``pcm_*`` are never called. A format with ``join``: every dump of a sentence after its first is decoded
         with context in front, the last min(16, frames of the sentence dumped so far, max_codec_frames - the
         dump's length) tokens dumped before it (``_join_row``), and the output stage crossfades the seam."""
