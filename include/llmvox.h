@@ -397,7 +397,14 @@ int lvx_stream_position(lvx_ctx* ctx, int slot, int* pos_out, void* stream);
  *   "l0a"          1: "l0q" steps whose attention is one split per (row, head) in 4-wave blocks (bf16 KV
  *                     9 <= B <= 32, fp8 KV 17 <= B <= 32): the select and layer 0's q / k / v from the
  *                     tables run inside attention layer 0, one launch less per step; 0: the select +
- *                     table launch, then the attention (bit-identical: tests/test_gpu_l0_fused.py). */
+ *                     table launch, then the attention (bit-identical: tests/test_gpu_l0_fused.py);
+ *   "laf"          1: on the same steps ("l0a" 1), layers 1-3 have no LayerNorm-rows and no c_attn launch:
+ *                     every attention block (row, head) normalises its row and computes its head's 288
+ *                     c_attn rows itself while its first KV tiles are in flight, and c_proj folds the
+ *                     pending mlp copies into x (three launches and their gaps less per layer);
+ *                     0: the three launches (bit-identical: tests/test_gpu_la_fused.py). The per-op entry
+ *                     points (lvx_probe_kernel, lvx_attn_probe, lvx_ar_ops) plan without the tables, so
+ *                     they go on running and timing the separate kernels whatever this option says. */
 int lvx_set_option(lvx_ctx* ctx, const char* name, int value);
 /* The stream the decode graphs are captured on (then replayed on the caller's stream). NULL (default):
  * the caller's stream. Name another one when something may query, from another thread, an event

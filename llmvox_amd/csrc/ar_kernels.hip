@@ -1171,8 +1171,14 @@ __device__ __forceinline__ float slot_fold_wave(float m, float& l, float (&o)[24
 // two-launch form, so the slot states have the same bits; the block's own store is not read back). The
 // head-0 block of a row commits the select (ar_q0_rows_kernel's cx == 0 stores, records into the shadow
 // arrays since the row's other blocks read the old ones in this launch); layer 1's ar_rows_kernel copies
-// the records back (RMODE_LN_Y_COPY). Ordering inside the block is by LDS barriers alone.
+// the records back (RMODE_LN_Y_COPY; in a la_fused step, which has no such launch, layer 1's fused attention does:
+// selcopy). Ordering inside the block is by LDS barriers alone.
+// LA (ArStepPlan::la_fused, layers >= 1 of such a step): the block runs its row's LayerNorm and its head's c_attn
+// rows instead of the tables; described at ar_attn_la_kernel.
 __device__ __forceinline__ float4 q0_row_stats(const GemvArgs& a, int4 rn, int b, int lane, bool store_x);
+__device__ __forceinline__ uint2 pack4_bf16(float4 v);
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // plan_tok(st, b, jn + 1) from the plan element loaded at min(jn + 1, plan_stride - 1) (384 when no plan is bound)
 __device__ __forceinline__ int l0_next_tok(const ArState& st, int jn, int loaded) {
   if (!st.text_plan) return 384;
@@ -1185,7 +1191,7 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-template <typename TKV, int DEPTH, int NW, bool QKV, bool L0>
+template <typename TKV, int DEPTH, int NW, bool QKV, bool L0, bool LA = false, int RT = 1>
 __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns_max, int direct, int selcopy,
                                              const GemvArgs* a0) {
   // NW waves: a tile is NW x 16 keys (4 lanes per key); NW = 8 doubles the bytes in flight per
@@ -1194,7 +1200,9 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   constexpr bool SLOT = sizeof(TKV) < 4;  // per-key-slot online softmax (bf16 / fp8 KV)
   static_assert(!QKV || (NW == 4 && sizeof(TKV) == 4), "the K-split c_attn: the fp32 parity mode's 4-wave blocks");
   static_assert(!L0 || (NW == 4 && SLOT && !QKV), "the fused layer-0 form: bf16 / fp8 KV in 4-wave blocks");
-  constexpr bool NEWKV = QKV || L0;  // the block computes the new key's q / k / v itself
+  static_assert(!LA || (NW == 4 && SLOT && !QKV && !L0), "the fused layers form: bf16 / fp8 KV in 4-wave blocks");
+  constexpr bool NEWKV = QKV || L0 || LA;  // the block computes the new key's q / k / v itself
+  constexpr bool HIST = L0 || LA;          // the tile loop runs over the history; the new key comes from LDS after it
   constexpr int QH = NEWKV ? (3 * HD + NW * 64 - 1) / (NW * 64) : 1;  // q / k / v elements per thread (2 at 4 waves, 1 at 8)
   __shared__ float wm_s[NW], wl_s[NW];
   __shared__ float wo_s[NW][4][HD];  // [wave][16-lane row][part * 24 + i]
@@ -1203,6 +1211,10 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   __shared__ float sv_s[L0 ? 4 : 1], sv2_s[L0 ? 4 : 1];  // L0: the select's wave partials, the row statistics
   __shared__ int si_s[L0 ? 4 : 1];
   __shared__ float4 sst_s;
+  // LA: the LayerNorm'd bf16 operand row (one copy per wave: no block barrier ahead of the MFMAs) and the
+  // waves' K-slice partials of this head's 288 c_attn outputs
+  __shared__ __attribute__((aligned(16))) bf16_t xb_s[LA ? NW : 1][LA ? D : 8];
+  __shared__ float red_s[LA ? NW : 1][LA ? 3 * HD : 1];
   const int sp = blockIdx.x, head = blockIdx.y, b = blockIdx.z;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   TS_DECL;
@@ -1262,6 +1274,35 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   // (the next text id, a dependent plan load, is looked up at the end of the block, when every
   // other load has landed)
   const int4 ri = L0 ? ri0 : selcopy ? st.rowinfo_n[b] : st.rowinfo[b];
+  // LA: behind the control record, every wave issues ar_rows_kernel<RMODE_LN_Y>'s loads for row b (gamma, x, the
+  // pending copies: all four waves, so that no load sits under a branch; the row comes from this XCD's L2
+  // after its first fetch) and the first RT column tiles of its K slice of this head's c_attn weights
+  // (a.Wf, fragment-packed: tile i of the head's 18 is tile (i / 6) * 48 + head * 6 + i % 6 of the matrix,
+  // the wave's six k-steps 6 KB contiguous). None of them depends on the record. The B blocks of a head run in
+  // step on one XCD: were they to walk the slice in the same order, each line would be asked for by all of
+  // them at once and the XCD would have one block's bytes in flight towards the fabric; row b starts at tile
+  // 7 b mod 18 (the tiles are independent outputs: any order gives the same bits), so the blocks ask for
+  // different tiles first and find the others in L2.
+  XRow<LA ? GIN_LN_Y : GIN_LN> xr;
+  float4 gam[3];
+  uint4 wr[RT][6];
+  int2 rxn = make_int2(0, 0);
+  const uint4* wsl = nullptr;
+  const int rot = LA ? (b * 7) % 18 : 0;
+  auto la_tile = [&](int i) { const int j = i + rot; return j >= 18 ? j - 18 : j; };  // the i-th tile this block runs
+  auto la_woff = [&](int j) { return (size_t)((j / 6) * 48 + j % 6) * (D / 32) * 64; };
+  if constexpr (LA) {
+    rxn = st.rowx_n[b];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gam[j] = *reinterpret_cast<const float4*>(a0->ln_w + j * 256 + lane * 4);
+    xrow_issue(*a0, b, lane, xr);
+    wsl = reinterpret_cast<const uint4*>(a0->Wf) + ((size_t)head * 6 * (D / 32) + wave * 6) * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < RT; ++i)
+#pragma unroll
+      for (int kk = 0; kk < 6; ++kk) wr[i][kk] = wsl[la_woff(la_tile(i)) + kk * 64];
+    __builtin_amdgcn_sched_barrier(0);
+  }
   // QKV: thread tid owns elements e = tid and tid + 256 (tid < 32) of this head's (q, k, v) (element
   // e % 96 of q / k / v for e / 96 = 0 / 1 / 2); their four K-slice partials are issued with the
   // control record (clamped element: no load under a branch)
@@ -1278,7 +1319,8 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   const bool cp = selcopy && sp == 0 && head == 0 && tid == 0;
   int jn = 0;
   if (cp) {
-    jn = st.rowx_n[b].x;
+    if constexpr (LA) jn = rxn.x;  // (loaded with the record: no load under this branch)
+    else jn = st.rowx_n[b].x;
     st.rowinfo[b] = ri;
     st.selrow[b] = 1u;  // (ar_q0_rows_kernel's pending select of the next step; unused by the granule forms)
     if (b == 0) *st.selp = 0u;
@@ -1300,8 +1342,8 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   // lane's key address is the chunk base (wave-uniform) + a fixed lane offset (a trailing split
   // may be empty: it writes m = -inf, l = 0). fp32 KV keeps the unrounded ranges of the parity mode.
   const int chunk = SLOT ? (((t + ns - 1) / ns + ATK - 1) / ATK) * ATK : (t + ns - 1) / ns;
-  // (L0, one split: the tile loop runs over the history, keys 0 .. t - 2; key t - 1 comes from LDS after it)
-  const int k0 = sp * chunk, k1 = L0 ? t - 1 : min(t, k0 + chunk);
+  // (L0 / LA, one split: the tile loop runs over the history, keys 0 .. t - 2; key t - 1 comes from LDS after it)
+  const int k0 = sp * chunk, k1 = HIST ? t - 1 : min(t, k0 + chunk);
   // key k of this (slot, head): chunk k / KV_CHUNK (cstride elements apart), row k % KV_CHUNK
   const size_t base = kv_at(layer, st.kv_chunks, st.max_streams, s, head, 0);
   const size_t cstride = (size_t)st.max_streams * N_HEAD * KV_CHUNK * HD;
@@ -1430,6 +1472,78 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
 #pragma unroll
     for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
   }
+  if constexpr (LA) {
+    // the history's first tiles are in flight behind the row and the first weight tiles. ar_rows_kernel<RMODE_LN_Y>'s
+    // LayerNorm of x + the pending copies (same fold, reduction and rounding; every wave, its own LDS copy of
+    // the bf16 row), then this head's 18 column tiles of c_attn as ar_mfma2_kernel<768, 2, M2OUT_QKV> computes
+    // them: wave w owns k in [192 w, 192 w + 192), six k-steps in order, the batch operand the one row
+    // replicated over the MFMA's 16 columns (an output element depends on its weight row and its batch column
+    // alone), the four K-slice partials summed in wave order. The weights stream through a ring of RT tiles,
+    // every refill right behind its use.
+    {
+      float4 v[3];
+      xrow_sum(xr, v);
+      wave_ln_regs(v, gam);
+      uint2* dst = reinterpret_cast<uint2*>(xb_s[wave]);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dst[j * 64 + lane] = pack4_bf16(v[j]);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    uint4 xf[6];
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk)
+      xf[kk] = *reinterpret_cast<const uint4*>(xb_s[wave] + (wave * 6 + kk) * 32 + 8 * (lane >> 4));
+    f32x4_t accp = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 18; ++i) {
+      f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < 6; ++kk)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wr[i % RT][kk]),
+                                                      __builtin_bit_cast(bf16x8_t, xf[kk]), acc, 0, 0, 0);
+      if (i + RT < 18) {
+#pragma unroll
+        for (int kk = 0; kk < 6; ++kk)
+          wr[i % RT][kk] = wsl[la_woff(la_tile(i + RT)) + kk * 64];
+      }
+      // the previous tile's column 0 (rows 4 (lane / 16) + r) while this tile's MFMAs run
+      if (i > 0 && (lane & 15) == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red_s[wave][la_tile(i - 1) * 16 + 4 * (lane >> 4) + r] = accp[r];
+      }
+      accp = acc;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if ((lane & 15) == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red_s[wave][la_tile(17) * 16 + 4 * (lane >> 4) + r] = accp[r];
+    }
+    lds_barrier();
+#pragma unroll
+    for (int h = 0; h < QH; ++h) {
+      const int e = tid + NW * 64 * h;
+      if (e < 3 * HD) {  // element e % 96 of q / k / v (e / 96): output row e of the head's 18 tiles
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) v += red_s[w][e];
+        if (e < HD) {
+          qs_s[e] = v;
+        } else {  // K / V of the new key: appended at (slot, position), kept in LDS
+          const int which = e / HD - 1, d = e % HD;
+          TKV hv;  // the value store_kv stores
+          if constexpr (sizeof(TKV) == 2) hv = f32_to_bf16(v);
+          else hv = f32_to_fp8(v);
+          kvh_s[which][d] = hv;
+          reinterpret_cast<TKV*>(which ? st.vc : st.kc)[base + krow(ri.y) + d] = hv;
+        }
+      }
+    }
+    lds_barrier();
+#pragma unroll
+    for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
+    TS_MARK(1);
+  }
   if constexpr (L0) {
     // the history's first tiles are in flight; the select chain of ar_q0_rows_kernel, same code and order
     const GemvArgs& a = *a0;
@@ -1512,7 +1626,7 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
       if (DEPTH > 2) __builtin_amdgcn_sched_barrier(0);  // keep the refill right behind its tile
     }
   }
-  if constexpr (L0) {
+  if constexpr (HIST) {
     // key t - 1 from LDS, by the lane quad that owns it in the tile holding it (tiles start at multiples
     // of TK): the step the two-launch form takes last in that slot, with the bits its store holds
     const bool mine = kq == (t - 1) % TK;
@@ -1599,6 +1713,24 @@ __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int lay
 template <typename TKV>
 __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArgs a, int direct) {
   attn_v2_body<TKV, 2, 4, false, true>(a.st, 0, 1, direct, 0, &a);
+}
+
+// the fused layers form (LA above; ArStepPlan::la_fused): layers >= 1 of a step whose layer 0 is the fused
+// layer-0 form. Grid (1, 8 heads, B): block (row, head) runs ar_rows_kernel<RMODE_LN_Y>'s LayerNorm of its row and
+// its head's 288 of c_attn's 2,304 output rows itself, with the history's first KV tiles in flight, so the
+// step has neither of those two launches at these layers (the pending copies are then folded into x by
+// c_proj: M2OUT_RESID_STATS with add_y). The head's 442 KB weight slice is the same for the B blocks of a
+// head, which share an XCD (head = linear block id mod 8): one fetch per XCD, then L2 hits. selcopy (layer
+// 1): the records of the fused layer-0 attention are read from the shadow arrays and copied back by the
+// head-0 block, as layer 0 of the unfused deferred-select forms does.
+// One wave per SIMD (one block per CU at B <= 32): the row, the weight ring and two KV tiles need ~200 VGPRs.
+#ifndef LVX_LA_RT
+#define LVX_LA_RT 3  // weight tiles in flight per wave (6 x 16 B per lane each)
+#endif
+template <typename TKV>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void ar_attn_la_kernel(GemvArgs a, int direct,
+                                                                                                    int selcopy) {
+  attn_v2_body<TKV, 2, 4, false, false, true, LVX_LA_RT>(a.st, a.layer, 1, direct, selcopy, &a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1962,9 +2094,6 @@ static void launch_gemv(const GemvArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL((ar_gemv_kernel<TW, K, KW, RPW, BGMAX, IN, OUT>), grid, dim3(256), 0, s, a);
   }
 }
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint2 pack4_bf16(float4 v) {
   return make_uint2((uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16),
@@ -2523,7 +2652,22 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
     for (int k = 0; k < EPT; ++k) {
       const int e = min(tid + k * NW * 64, 16 * NT * 16 - 1), r = e / (NT * 16), b = e - r * (NT * 16);
       const int n = min(n0 + r, a.N - 1);
-      if constexpr (OUT == M2OUT_RESID_STATS) xpre[k] = a.st.x[(size_t)min(r0 + b, B - 1) * D + n];
+      if constexpr (OUT == M2OUT_RESID_STATS) {
+        // x, and with add_y (a step whose c_attn ran inside the attention: no rows kernel folded them) the
+        // mlp c_proj's pending copies, summed in ar_rows_kernel<RMODE_LN_Y>'s order (xrow_sum: x + c0 + c1 +
+        // c2 + c3). Loaded whether or not they are folded: no load under a branch.
+        const int br = min(r0 + b, B - 1);
+        float t = a.st.x[(size_t)br * D + n];
+        const float* yp = a.yacc ? a.yacc + (size_t)br * YCOPIES * D + n : a.st.x + (size_t)br * D + n;
+        const int ys = a.yacc ? D : 0;
+        float yc[YCOPIES];
+#pragma unroll
+        for (int c = 0; c < YCOPIES; ++c) yc[c] = yp[c * ys];
+        if (a.yacc && a.add_y)
+#pragma unroll
+          for (int c = 0; c < YCOPIES; ++c) t += yc[c];
+        xpre[k] = t;
+      }
       gpre[k] = OUT == M2OUT_RESID_STATS ? a.ln_w[n] : a.gsum[n];
     }
   }
@@ -3522,6 +3666,7 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
                                        : p.sel == SEL_GRAN)))
         ar_plan_bug(p, "c_attn");
       if (l == 0 && p.l0_fused) {  // no launch: attention layer 0 runs the select and the q0 tables itself
+      } else if (l > 0 && p.la_fused) {  // no launch: the attention runs the LayerNorm and its head's c_attn rows itself
       } else if (l == 0 && p.sel == SEL_LN_GRAN) {  // select + embedding in c_attn's prologue
         launch_mfma_ln<MLOUT_QKV, MLMODE_EMBED_SELECT>(a, s);
       } else if (l == 0 && p.sel == SEL_Q0_ROWS) {  // select + c_attn from the q0 tables, 9 slices per row
@@ -3558,12 +3703,22 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
         else ar_plan_bug(p, "fused layer-0 attention");
         break;
       }
+      if (l > 0 && p.la_fused) {  // LayerNorm + this head's c_attn rows + attention; layer 1 copies layer 0's shadow records back
+        a.Wf = w.f_attn[l]; a.ln_w = w.ln1[l];
+        if (p.kv_dtype == LVX_DTYPE_BF16)
+          hipLaunchKernelGGL(ar_attn_la_kernel<bf16_t>, dim3(1, N_HEAD, B), dim3(256), 0, s, a, p.attn_direct, (int)(l == 1));
+        else if (p.kv_dtype == LVX_DTYPE_FP8)
+          hipLaunchKernelGGL(ar_attn_la_kernel<fp8_t>, dim3(1, N_HEAD, B), dim3(256), 0, s, a, p.attn_direct, (int)(l == 1));
+        else ar_plan_bug(p, "fused layers attention");
+        break;
+      }
       launch_attn(a.st, p.kv_dtype, B, l, s, p.nsplit, p.attn_direct, p.selcopy && l == 0, false, p.attn8);
       break;
     case OP_CPROJ:
       a.W = w.w_aproj[l]; a.Wf = w.f_aproj[l]; a.N = D;
       if (mf) {
-        if (!ln) a.add_y = 0;  // ar_rows_kernel<RMODE_LN_Y> of this layer's c_attn folded them
+        // ar_rows_kernel<RMODE_LN_Y> of this layer's c_attn folded them; la_fused has no such launch: c_proj folds
+        if (!ln) a.add_y = p.la_fused && l > 0;
         if (p.nsplit > 1) launch_merge_bf16(a.st, B, p.nsplit, s, a.xpk);  // one split: the attention wrote xn itself
         a.ln_w = w.ln2[l];  // M2OUT_RESID_STATS: the bf16 copy is x * ln_2.weight (c_fc's operand)
         // + bf16 x and row statistics for c_fc; 16-row batch tiles (B = 32: 96 blocks of 49 KB operands

@@ -86,6 +86,10 @@ struct ArStepPlan {
   bool q0_gran;    // SEL_GRAN with layer 0's c_attn from the q0 tables (ar_q0_gran_kernel)
   int xpk;         // bf16 operand rows kept fragment-packed (GemvArgs::xpk)
   bool ksplit, qsplit;  // PATH_F32B: mlp c_proj / c_attn as K slices
+  // l0_fused steps with option laf: layers >= 1 have no ar_rows_kernel / c_attn launch either; their attention
+  // block (row, head) runs the row's LayerNorm and its head's c_attn rows itself (ar_attn_la_kernel), layer 1's
+  // copies the shadow records back, and c_proj folds the pending copies into x
+  bool la_fused;
 };
 
 constexpr int MFMA_BATCH_MIN = 3;  // smallest B on the batched MFMA path (measured B = 3: 117 vs 154 us, B = 2: 119 vs 114)
@@ -187,6 +191,9 @@ inline ArStepPlan ar_plan_step(const Opts& o_, int wdtype, int kvdtype, int B, b
   // Every block then has the select chain ahead of its tile loop, with the history's first tiles in flight under it.
   // (fp32 KV under bf16 weights keeps the two launches: the fused form has the per-key-slot kernels only)
   p.l0_fused = o.l0a && p.sel == SEL_Q0_ROWS && p.nsplit == 1 && !p.attn8 && B >= 9 && kvdtype != LVX_DTYPE_F32;
+  // The fused layers form on the same cells (each attention block of layers 1-3 is then its own c_attn: no
+  // hand-off between workgroups, the head's weight slice shared through the XCD's L2)
+  p.la_fused = o.laf && p.l0_fused;
   // fragment-packed operand rows on the v2 steps with the rows kernel at B <= 32
   p.xpk = (p.path == PATH_MFMA_ROWS && B <= 32) ? 1 : 0;
   p.attn_direct = p.nsplit > 1 || !(mf || p.path == PATH_F32B) ? ATTN_PARTIALS

@@ -872,6 +872,7 @@ int lvx_set_option(lvx_ctx* c, const char* name, int value) {
   else if (n == "ln_max") o.ln_max = std::min(std::max(value, 2), 8);
   else if (n == "l0q") o.l0q = value != 0;
   else if (n == "l0a") o.l0a = value != 0;
+  else if (n == "laf") o.laf = value != 0;
   else return fail(LVX_E_NAME, "unknown option " + n);
   ++c->opt_epoch;  // this context's captured kernels change (checked in cached_graph)
   return LVX_OK;

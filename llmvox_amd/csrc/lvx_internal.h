@@ -49,6 +49,9 @@ struct Opts {
   int l0a = 1;           // SEL_Q0_ROWS steps whose attention is one split in 4-wave blocks (bf16 KV 9 <= B <= 32, fp8 KV
                          // 17 <= B <= 32): ar_q0_rows_kernel's work inside attention layer 0 (ar_attn_l0_kernel);
                          // 0: the two launches (bit-identical: tests/test_gpu_l0_fused.py)
+  int laf = 1;           // the same steps (l0a on): LayerNorm and c_attn of layers 1-3 inside their attention blocks
+                         // (ar_attn_la_kernel); 0: ar_rows_kernel + c_attn + attention (bit-identical:
+                         // tests/test_gpu_la_fused.py)
 };
 const Opts& opts();  // the calling thread's bound options (the defaults when none is bound)
 struct OptScope {    // binds `o` to this thread until the scope ends
