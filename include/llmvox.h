@@ -759,6 +759,79 @@ int lvx_pcm_level(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int
                   const uint8_t* final_host, int volume_pct, float* out_dev, long long out_stride_bytes,
                   int32_t* n_out_host, float* g_out_dev, long long g_stride_bytes, void* stream);
 
+/* ---- PCM FLAC ------------------------------------------------------------------
+ * A lossless compressed output: a sixth stage BEHIND lvx_pcm_convert. Its input is the s16le samples of the
+ * format's rate, exactly what lvx_pcm_convert writes with LVX_PCM_S16LE (int16 rows on the device); a decoder
+ * gives those samples back. Integer arithmetic only, so THE DEVICE'S BYTES ARE THOSE OF A HOST EVALUATION
+ * (llmvox_amd/audio.py: flac_subframe; here: lvx_flac_subframe) and THE CONCATENATED OUTPUT OF ANY CHUNKING OF A
+ * SEGMENT IS BIT-IDENTICAL TO ITS ONE-SHOT OUTPUT. One segment is one sentence of one stream. The rule is
+ * self-consistent (a separately written decoder round-trips it); it has not been held to libFLAC.
+ *
+ * Frames. BS = sample_rate / 25 (40 ms): 320, 640, 960, 1920 samples. A sentence of T > 0 samples is
+ * k = max(0, floor((T - 16) / BS)) frames of BS samples, then one frame of the remaining T - k BS: every frame has
+ * 16 .. BS + 15 samples, but for a sentence shorter than 16 samples, which is one frame. The stream is of FLAC's
+ * variable-blocksize kind. STREAMINFO: min blocksize 16, max blocksize BS + 15, mono, 16 bits; the frame sizes, the
+ * total sample count and the MD5 are 0 (unknown).
+ *
+ * Streaming. After a non-final call that brings the segment's input to T the frames emitted so far are
+ * max(0, floor((T - 16) / BS)); a final call emits the rest. The library keeps, per KV slot, the <= BS + 15 samples
+ * no frame has taken yet (two buffers per slot: a launch reads one and writes the other) and, on the host, a
+ * mirror of the slot's count and rate. A segment has one rate: another before its final call is LVX_E_ARG.
+ *
+ * The subframe of a frame x[0 .. n), made on the device:
+ *   CONSTANT, if all samples are equal: the byte 0x00, then x[0] in 16 bits.
+ *   Predictor order: r_p = the p-th difference of x; E_p = sum of |r_p[i]| over i = 4 .. n - 1; p = the smallest
+ *     of 0 .. 4 with the least E_p (so p = 0 for n <= 4).
+ *   Folding: u = 2 r for r >= 0, else -2 r - 1 (u < 2^21 for int16 input).
+ *   Partition order: P = min(3, trailing zero bits of n), lowered while P > 0 and (n >> P) < 16; partition j has
+ *     n >> P samples, less p in partition 0.
+ *   Rice parameter of a partition: the k of 0 .. 14 with the least sum((u >> k) + 1 + k), the smallest at a tie;
+ *     the escape code is never used.
+ *   FIXED: the byte (8 | p) << 1; p warm-up samples of 16 bits; 00 (the coding method); P in 4 bits; per
+ *     partition k in 4 bits, then per sample u >> k zeros, a one, and the low k bits of u.
+ *   VERBATIM, if that bit count is not smaller than 8 + 16 n: the byte 0x02, then the samples in 16 bits.
+ *   Bits are packed MSB first and zero-padded to a byte: at most 1 + 2 n bytes.
+ * The rest of a frame depends on where the sentence sits in the request (a request's sentences alternate between
+ * two streams, so no device call knows a frame's sample number) and is made on the host, lvx_flac_finish:
+ *   sync 0xFFF9; block size code 0111; sample-rate code 0100 / 0101 / 0111 / 1010 (8 / 16 / 24 / 48 kHz); the byte
+ *   0x08 (mono, 16 bits); the first sample's number in FLAC's UTF-8-like coding (1 .. 7 bytes); n - 1 in 16 bits;
+ *   the CRC-8 of these bytes (polynomial 0x07, initial value 0); the subframe; the CRC-16 of everything before it
+ *   (polynomial 0x8005, initial value 0, not reflected), high byte first. At most 2 n + 17 bytes.
+ *   (Over "123456789" the two CRCs are 0xF4 and 0xFEE8.)
+ *
+ * Device output. Row b holds the frames a call emits in fixed slots of LVX_FLAC_SLOT(rate) bytes: an 8-byte record
+ * {uint16 n, uint16 body_bytes, uint32 0} (little endian), the subframe, zeros to the slot's end. How many frames
+ * a call emits is a closed form of the counts (lvx_pcm_flac_emitted): n_frames_host is filled on the host. */
+#define LVX_FLAC_SLOT(rate) ((8 + 1 + 2 * ((rate) / 25 + 15) + 15) / 16 * 16)
+/* host only: BS of a rate (negative: LVX_E_ARG for an unsupported rate) */
+int lvx_pcm_flac_block(int sample_rate);
+/* host only: frames a call emits for a slot that has consumed t0 inputs of its segment (negative: LVX_E_ARG for
+ * an unsupported rate, t0 < 0 or n_in < 0) */
+int lvx_pcm_flac_emitted(int sample_rate, long long t0, int n_in, int final);
+/* host only: "fLaC" and the STREAMINFO block, 42 bytes. LVX_E_ARG: an unsupported rate, a null pointer, cap < 42. */
+int lvx_flac_stream_header(int sample_rate, uint8_t* out, int cap);
+/* host only: the subframe of x[0 .. n) by the rule above. Returns its bytes (<= 1 + 2 n). LVX_E_ARG: n outside
+ * 1 .. 65535, a null pointer; LVX_E_CAPACITY: cap is smaller than the subframe (nothing is written). */
+int lvx_flac_subframe(const int16_t* x, int n, uint8_t* out, int cap);
+/* host only: the n_frames slots of one row of lvx_pcm_flac made frames (header, subframe, CRC-16), the first at
+ * sample number *sample_no, which advances by the frames' samples. Returns the bytes written. LVX_E_ARG: an
+ * unsupported rate, a null pointer, n_frames < 0, a record that is none of this stage's, a sample number past 2^36,
+ * frames of 2^31 bytes or more in one call;
+ * LVX_E_CAPACITY: cap is smaller than the frames (2 n + 17 bytes each always suffice). In both cases nothing is
+ * written and *sample_no stays. */
+int lvx_flac_finish(int sample_rate, const uint8_t* slots, int n_frames, unsigned long long* sample_no, uint8_t* out,
+                    int cap);
+/* lvx_pcm_convert's conventions: rows b of s16_dev (int16, row b at s16_dev + b * in_stride_bytes, n_in samples)
+ * continue the FLAC segments of slots_host[b]; final_host[b] != 0 emits the last frame and resets the slot; n_in
+ * may be 0 with final. out row b starts at out_dev + b * out_stride_bytes; n_frames_host[b] = slots written.
+ * LVX_E_ARG (and no slot's state changed): an unsupported rate or another than the slot's open segment has, B < 1,
+ * n_in < 0, a slot out of range or named twice, s16_dev or in_stride_bytes odd, in_stride_bytes smaller than a row,
+ * out_dev or out_stride_bytes not a multiple of 4, out_stride_bytes smaller than a row's slots. lvx_pcm_reset also
+ * forgets a slot's FLAC state. lvx_pcm_convert itself takes no such encoding. */
+int lvx_pcm_flac(lvx_ctx* ctx, const int16_t* s16_dev, long long in_stride_bytes, int B, int n_in,
+                 const int32_t* slots_host, const uint8_t* final_host, int sample_rate, void* out_dev,
+                 long long out_stride_bytes, int32_t* n_frames_host, void* stream);
+
 /* ---- WavTokenizer encoder, a context of its own (its weights are not needed for TTS).
  * Replaces WavTokenizer.encode_infer (WavTokenizer/decoder/pretrained.py:185-190 ->
  * decoder/feature_extractors.py:122-133): SEANet encoder (encoder/modules/seanet.py:94-143) + the

@@ -9,7 +9,9 @@ rate conversion): ``pitch_plan``, ``ratio_ref``. And the join of a sentence's du
 frame crossfaded with the next dump's rendering of it, in front of the other three): ``join_ref``. And the volume
 control ("PCM level": a gain and a feed-forward peak limiter, between the ratio and the rate conversion):
 ``level_ref``. And the G.711 encodings ("PCM G.711": the s16 quantisation companded to 8-bit mu-law or A-law, integer
-arithmetic only): ``g711_encode``, ``g711_decode``."""
+arithmetic only): ``g711_encode``, ``g711_decode``. And the FLAC output ("PCM FLAC": the s16 samples cut into frames of
+40 ms, each a CONSTANT, FIXED or VERBATIM subframe, integer arithmetic only): ``flac_subframe``, ``flac_frame``,
+``flac_encode_ref``, and ``FlacMux``, which finishes the device's subframes into frames on the delivery path."""
 from __future__ import annotations
 
 import struct
@@ -21,9 +23,11 @@ import numpy as np
 
 BASE_RATE = 24000  # the codec's output rate
 RATES = {24000: (1, 1, 0), 16000: (2, 3, 72), 8000: (1, 3, 72), 48000: (2, 1, 48)}  # rate: (L, M, N)
-ENCODINGS = ("f32le", "s16le", "ulaw", "alaw")
+ENCODINGS = ("f32le", "s16le", "ulaw", "alaw")  # the sample encodings: what lvx_pcm_convert writes, one dtype each
+FORMAT_ENCODINGS = ENCODINGS + ("flac",)  # what a format may name: those, and the FLAC stream made behind s16le
 G711_LAWS = ("ulaw", "alaw")  # the 8-bit companded encodings (LVX_PCM_ULAW, LVX_PCM_ALAW)
-_SAMPLE_DTYPE = {"f32le": np.dtype("<f4"), "s16le": np.dtype("<i2"), "ulaw": np.dtype("u1"), "alaw": np.dtype("u1")}
+_SAMPLE_DTYPE = {"f32le": np.dtype("<f4"), "s16le": np.dtype("<i2"), "ulaw": np.dtype("u1"), "alaw": np.dtype("u1"),
+                 "flac": np.dtype("u1")}  # (flac: the bytes of the device's slots, then of the stream)
 _G711_TAG = {"ulaw": 7, "alaw": 6}   # WAVE format tags, the values of LVX_PCM_ULAW / LVX_PCM_ALAW
 _G711_SILENCE = {"ulaw": 0xFF, "alaw": 0xD5}  # the codes of q = 0
 CONTAINERS = ("raw", "wav")
@@ -44,6 +48,7 @@ LEVEL_A = 120           # the limiter's attack half-window in samples (LVX_LEVEL
 LEVEL_R = 1200          # its hold (LVX_LEVEL_R): 50 ms
 LEVEL_CEIL = np.float32(0.8912509)  # its ceiling c (LVX_LEVEL_CEIL): -1 dBFS
 LEVEL_HISTORY = 1600    # inputs of history a slot keeps between level calls
+FLAC_MAX_K = 14         # the largest Rice parameter the FLAC stage chooses (the escape code is never used)
 
 
 def pitch_plan(speed_pct: int, pitch_pct: int) -> Tuple[int, int, int]:
@@ -77,10 +82,12 @@ class AudioFormat:
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
             raise ValueError(f"sample_rate must be one of {sorted(RATES)}, got {self.sample_rate!r}")
-        if self.encoding not in ENCODINGS:
-            raise ValueError(f"encoding must be one of {ENCODINGS}, got {self.encoding!r}")
+        if self.encoding not in FORMAT_ENCODINGS:
+            raise ValueError(f"encoding must be one of {FORMAT_ENCODINGS}, got {self.encoding!r}")
         if self.container not in CONTAINERS:
             raise ValueError(f"container must be one of {CONTAINERS}, got {self.container!r}")
+        if self.encoding == "flac" and self.container != "raw":
+            raise ValueError("encoding 'flac' is its own container: container must be 'raw', got 'wav'")
         if isinstance(self.speed_pct, bool) or not isinstance(self.speed_pct, int) \
                 or not SPEED_MIN <= self.speed_pct <= SPEED_MAX:
             raise ValueError(f"speed_pct must be an integer in [{SPEED_MIN}, {SPEED_MAX}], got {self.speed_pct!r}")
@@ -126,6 +133,8 @@ class AudioFormat:
 
     @property
     def media_type(self) -> str:
+        if self.encoding == "flac":
+            return "audio/flac"
         return "audio/wav" if self.container == "wav" else "application/octet-stream"
 
 
@@ -356,9 +365,245 @@ def frame_chunks(chunks, fmt: AudioFormat, frame_ms: int):
 
 
 def encode_ref(y, fmt: AudioFormat) -> np.ndarray:
+    if fmt.encoding == "flac":  # a whole sentence: every frame's slot, as the device writes them
+        q = quantize_s16(y)
+        return flac_slots_ref(q, fmt.sample_rate, 0, flac_frames_upto(fmt.sample_rate, q.size, True))
     if fmt.encoding in G711_LAWS:
         return g711_encode(quantize_s16(y), fmt.encoding)
     return quantize_s16(y) if fmt.encoding == "s16le" else np.asarray(y, dtype=np.float32)
+
+
+# ---- the FLAC rule (include/llmvox.h, "PCM FLAC"), in numpy: integers only -----------------------------
+
+_FLAC_RATE_CODE = {8000: 4, 16000: 5, 24000: 7, 48000: 10}
+
+
+def flac_block(sample_rate: int) -> int:
+    """BS = sample_rate / 25: the samples of a whole frame, 40 ms (``lvx_pcm_flac_block``)."""
+    if sample_rate not in RATES:
+        raise ValueError(f"unsupported sample rate {sample_rate}")
+    return sample_rate // 25
+
+
+def flac_slot_bytes(sample_rate: int) -> int:
+    """Bytes of one slot of the device's output (LVX_FLAC_SLOT): the 8-byte record and the longest subframe of the
+    rate, 1 + 2 (BS + 15) bytes, rounded up to 16."""
+    return (8 + 1 + 2 * (flac_block(sample_rate) + 15) + 15) // 16 * 16
+
+
+def flac_frames_upto(sample_rate: int, T: int, final: bool) -> int:
+    """Frames of a segment emitted once T inputs are consumed: after a non-final call the whole frames
+    max(0, floor((T - 16) / BS)); a final call adds the frame of the remaining samples."""
+    k = max(0, (T - 16) // flac_block(sample_rate))
+    return k + (1 if final and T > 0 else 0)
+
+
+def flac_emitted(sample_rate: int, t0: int, n_in: int, final: bool) -> int:
+    """Frames a FLAC call emits for a slot that has consumed t0 inputs of its segment (``lvx_pcm_flac_emitted``)."""
+    if t0 < 0 or n_in < 0:
+        raise ValueError("t0 and n_in must be >= 0")
+    return flac_frames_upto(sample_rate, t0 + n_in, final) - flac_frames_upto(sample_rate, t0, False)
+
+
+def flac_frames_of(T: int, sample_rate: int) -> List[int]:
+    """The block sizes of a sentence of T samples: k = max(0, floor((T - 16) / BS)) frames of BS, then one frame of
+    the remaining T - k BS (16 .. BS + 15 samples, fewer only for a sentence shorter than 16); none for T = 0."""
+    bs = flac_block(sample_rate)
+    if T <= 0:
+        return []
+    k = max(0, (T - 16) // bs)
+    return [bs] * k + [T - k * bs]
+
+
+def _flac_s16(x) -> np.ndarray:
+    x = np.asarray(x)
+    if x.dtype.kind not in "iu" or (x.size and (x.min() < -32768 or x.max() > 32767)):
+        raise ValueError("the samples must be integers in -32768 .. 32767")
+    return x.astype(np.int64).reshape(-1)
+
+
+def _flac_put(bits: np.ndarray, pos, length: int, val):
+    """The low ``length`` bits of val (arrays or scalars) at bit positions pos, MSB first."""
+    pos, val = np.asarray(pos, dtype=np.int64), np.asarray(val, dtype=np.int64)
+    for t in range(length):
+        bits[pos + t] = (val >> (length - 1 - t)) & 1
+
+
+def flac_subframe(x) -> bytes:
+    """The subframe of the frame x[0 .. n), n >= 1 int16 samples, by the header's rule (``lvx_flac_subframe``; the
+    device's ``pcm_flac_kernel``): CONSTANT, else FIXED of the order with the least error sum, its residuals Rice-coded
+    in partitions, else VERBATIM where that is not smaller."""
+    x = _flac_s16(x)
+    n = x.size
+    if n < 1:
+        raise ValueError("a frame has at least one sample")
+    if np.all(x == x[0]):
+        return bytes([0x00]) + struct.pack(">H", int(x[0]) & 0xFFFF)
+    diffs = [x]
+    for _ in range(4):  # r_p[i] for i >= p (the entries in front hold differences with x[-1 ..] = 0 and are not used)
+        diffs.append(np.diff(diffs[-1], prepend=0))
+    E = [int(np.abs(d[4:]).sum()) for d in diffs]
+    p = int(np.argmin(E))  # (the first of the least: the smallest p)
+    r = diffs[p][p:]
+    u = np.where(r >= 0, 2 * r, -2 * r - 1)
+    P = 0
+    while P < 3 and n % (2 << P) == 0:
+        P += 1
+    while P > 0 and (n >> P) < 16:
+        P -= 1
+    psize = n >> P
+    parts, start = [], 0
+    for j in range(1 << P):
+        cnt = psize - (p if j == 0 else 0)
+        uj = u[start:start + cnt]
+        cost = [int(((uj >> k) + 1 + k).sum()) for k in range(FLAC_MAX_K + 1)]
+        k = int(np.argmin(cost))  # (the smallest k at a tie)
+        parts.append((k, uj, cost[k]))
+        start += cnt
+    total = 8 + 16 * p + 2 + 4 + sum(4 + c for _, _, c in parts)
+    if total >= 8 + 16 * n:
+        return bytes([0x02]) + (x & 0xFFFF).astype(">u2").tobytes()
+    bits = np.zeros((total + 7) // 8 * 8, dtype=np.uint8)
+    _flac_put(bits, 0, 8, (8 | p) << 1)
+    _flac_put(bits, 8 + 16 * np.arange(p), 16, x[:p] & 0xFFFF)
+    pos = 8 + 16 * p
+    _flac_put(bits, pos, 6, P)  # the coding method 00, then P in 4 bits
+    pos += 6
+    for k, uj, c in parts:
+        _flac_put(bits, pos, 4, k)
+        pos += 4
+        q = uj >> k
+        ends = pos + np.cumsum(q + 1 + k)  # a sample's bits end here: q zeros, the one, k low bits
+        bits[ends - k - 1] = 1
+        _flac_put(bits, ends - k, k, uj & ((1 << k) - 1))
+        pos += c
+    assert pos == total
+    return np.packbits(bits).tobytes()
+
+
+def _crc_table(poly: int, width: int) -> List[int]:
+    top, mask, table = 1 << (width - 1), (1 << width) - 1, []
+    for i in range(256):
+        c = i << (width - 8)
+        for _ in range(8):
+            c = ((c << 1) ^ poly) & mask if c & top else (c << 1) & mask
+        table.append(c)
+    return table
+
+
+_CRC8, _CRC16 = _crc_table(0x07, 8), _crc_table(0x8005, 16)
+
+
+def flac_crc8(data: bytes) -> int:
+    """CRC-8 of a frame header: polynomial 0x07, initial value 0 (0xF4 over b"123456789")."""
+    c = 0
+    for b in data:
+        c = _CRC8[c ^ b]
+    return c
+
+
+def flac_crc16(data: bytes) -> int:
+    """CRC-16 of a frame: polynomial 0x8005, initial value 0, not reflected (0xFEE8 over b"123456789")."""
+    c = 0
+    for b in data:
+        c = ((c << 8) & 0xFFFF) ^ _CRC16[(c >> 8) ^ b]
+    return c
+
+
+def _flac_utf8(v: int) -> bytes:
+    """The sample number in FLAC's UTF-8-like coding: 1 .. 7 bytes for a number below 2^36."""
+    if not 0 <= v < 1 << 36:
+        raise ValueError(f"sample number {v} is outside [0, 2^36)")
+    if v < 0x80:
+        return bytes([v])
+    n = 2
+    while n < 7 and v >= 1 << (5 * n + 1):
+        n += 1
+    first = ((0xFF00 >> n) & 0xFF) | (v >> (6 * (n - 1)) if n < 7 else 0)
+    return bytes([first] + [0x80 | ((v >> (6 * (n - 1 - i))) & 0x3F) for i in range(1, n)])
+
+
+def flac_finish_ref(sample_rate: int, n: int, body: bytes, sample_no: int) -> bytes:
+    """A frame from its subframe: the header (sync 0xFFF9, block size code 0111, the rate's code, 0x08, the first
+    sample's number, n - 1 in 16 bits, the CRC-8), the subframe, the CRC-16 (``lvx_flac_finish`` for one slot)."""
+    flac_block(sample_rate)
+    if sample_no + n > 1 << 36:
+        raise ValueError("the sample number passes 2^36")
+    head = bytes([0xFF, 0xF9, 0x70 | _FLAC_RATE_CODE[sample_rate], 0x08]) + _flac_utf8(sample_no) + struct.pack(">H", n - 1)
+    frame = head + bytes([flac_crc8(head)]) + body
+    return frame + struct.pack(">H", flac_crc16(frame))
+
+
+def flac_frame(x, sample_rate: int, sample_no: int) -> bytes:
+    """The frame of the samples x at ``sample_rate`` whose first sample has the number ``sample_no``: at most
+    2 n + 17 bytes."""
+    x = _flac_s16(x)
+    return flac_finish_ref(sample_rate, x.size, flac_subframe(x), sample_no)
+
+
+def flac_stream_header(sample_rate: int) -> bytes:
+    """"fLaC" and the one STREAMINFO block, 42 bytes (``lvx_flac_stream_header``): min blocksize 16, max blocksize
+    BS + 15, mono, 16 bits; the frame sizes, the total sample count and the MD5 are 0 (unknown)."""
+    bs = flac_block(sample_rate)
+    info = struct.pack(">HH", 16, bs + 15) + bytes(6) + struct.pack(">Q", (sample_rate << 44) | (15 << 36)) + bytes(16)
+    return b"fLaC" + bytes([0x80, 0, 0, 34]) + info
+
+
+def flac_encode_ref(q, sample_rate: int, sample_no: int = 0, header: bool = True) -> bytes:
+    """One sentence q (int16 samples at ``sample_rate``) as FLAC: the stream header (``header``), then the frames of
+    ``flac_frames_of``, the first at ``sample_no``. What the device's slots give once ``lvx_flac_finish`` has run."""
+    q = _flac_s16(q)
+    out, at = [flac_stream_header(sample_rate)] if header else [], 0
+    for n in flac_frames_of(q.size, sample_rate):
+        out.append(flac_frame(q[at:at + n], sample_rate, sample_no + at))
+        at += n
+    return b"".join(out)
+
+
+def flac_slots_ref(q, sample_rate: int, j0: int, j1: int) -> np.ndarray:
+    """Frames j0 .. j1 - 1 of the sentence q as the device writes them (``lvx_pcm_flac``): slots of
+    ``flac_slot_bytes``, each the record {u16 n, u16 body_bytes, u32 0}, the subframe, zeros (uint8)."""
+    q = _flac_s16(q)
+    bs, size = flac_block(sample_rate), flac_slot_bytes(sample_rate)
+    sizes = flac_frames_of(q.size, sample_rate)
+    out = np.zeros((j1 - j0) * size, dtype=np.uint8)
+    for j in range(j0, j1):
+        body = flac_subframe(q[j * bs:j * bs + sizes[j]])
+        rec = struct.pack("<HHI", sizes[j], len(body), 0) + body
+        out[(j - j0) * size:(j - j0) * size + len(rec)] = np.frombuffer(rec, dtype=np.uint8)
+    return out
+
+
+class FlacMux:
+    """The host end of a FLAC stream: ``header()`` is the stream header; ``push(blob)`` turns the slots one call of
+    the device stage delivered (bytes or uint8, whole slots of ``flac_slot_bytes``) into frames with the running
+    sample number, through the library's ``lvx_flac_finish``. The one place that knows the speaking order."""
+
+    def __init__(self, sample_rate: int):
+        self.sample_rate, self.slot = sample_rate, flac_slot_bytes(sample_rate)
+        self.sample_no = 0
+
+    def header(self) -> bytes:
+        return flac_stream_header(self.sample_rate)
+
+    def push(self, blob) -> bytes:
+        import ctypes
+
+        from . import _lib
+        blob = blob.tobytes() if isinstance(blob, np.ndarray) else bytes(blob)
+        if len(blob) % self.slot:
+            raise ValueError(f"{len(blob)} bytes are no whole slots of {self.slot}")
+        frames = len(blob) // self.slot
+        if not frames:
+            return b""
+        cap = frames * self.slot + 16 * frames  # (a frame is at most its subframe and 16 bytes)
+        out = ctypes.create_string_buffer(cap)
+        no = ctypes.c_ulonglong(self.sample_no)
+        n = _lib.load().lvx_flac_finish(self.sample_rate, blob, frames, ctypes.byref(no), out, cap)
+        if n < 0:
+            raise _lib.error_for(int(n))
+        self.sample_no = int(no.value)
+        return out.raw[:n]
 
 
 # ---- the time stretch's rule (include/llmvox.h, "PCM time stretch"), in numpy -------------------------
@@ -623,7 +868,8 @@ class StreamRef:
     """The streaming form of the rule for one slot, on the host: ``push(x, final)`` returns the samples the
     call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_join`` when the format joins its dumps, then
     ``lvx_pcm_stretch`` when the plan has a stretch, then ``lvx_pcm_ratio`` when it has a ratio, then
-    ``lvx_pcm_level`` when it has a volume, then ``lvx_pcm_convert``). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the
+    ``lvx_pcm_level`` when it has a volume, then ``lvx_pcm_convert`` and, a FLAC format, ``lvx_pcm_flac`` behind it as s16le:
+    the slots of the frames the call emits). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the
     whole segment; for tests and stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
 
     def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, join_windows=None, level_win=None):
@@ -650,6 +896,8 @@ class StreamRef:
         self.join_tail: Optional[np.ndarray] = None  # the join's view: the held-back frame (None: closed)
         self.lvl: List[np.ndarray] = []  # the level stage's view: the resampled segment and its count
         self.lvl_t0 = 0
+        self.fq: List[np.ndarray] = []  # the FLAC stage's view: the segment's s16 samples and their count
+        self.fq_t0 = 0
 
     def _ratio(self, x, final: bool) -> np.ndarray:
         m0 = ratio_emitted_upto(self.L, self.M, self.mid_t0, False)
@@ -697,15 +945,28 @@ class StreamRef:
         self.seg.append(x)
         self.t0 += x.size
         whole = np.concatenate(self.seg) if self.seg else np.zeros(0, np.float32)
-        y = encode_ref(resample_ref(whole, rate, self.taps, m0, m1), self.fmt)
+        y = resample_ref(whole, rate, self.taps, m0, m1)
+        if self.fmt.encoding == "flac":  # the sixth stage: the s16le samples cut into frames, whole slots out
+            q = quantize_s16(y)
+            j0 = flac_frames_upto(rate, self.fq_t0, False)
+            j1 = flac_frames_upto(rate, self.fq_t0 + q.size, final)
+            self.fq.append(q)
+            self.fq_t0 += q.size
+            # (a frame that is whole now reads the same samples in the sentence as it stands as in the finished one)
+            y = flac_slots_ref(np.concatenate(self.fq), rate, j0, j1) if j1 > j0 else np.zeros(0, np.uint8)
+        else:
+            y = encode_ref(y, self.fmt)
         if final:
             self.reset()
         return y
 
 
 __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "resample_ref", "quantize_s16",
-           "convert_ref", "StreamRef", "RATES", "ENCODINGS", "G711_LAWS", "g711_encode", "g711_decode", "silence_byte",
-           "FRAME_MS", "frame_ms_of", "frame_bytes", "frame_chunks", "CONTAINERS", "BASE_RATE", "HISTORY",
+           "convert_ref", "StreamRef", "RATES", "ENCODINGS", "FORMAT_ENCODINGS", "G711_LAWS", "g711_encode", "g711_decode", "silence_byte",
+           "FRAME_MS", "frame_ms_of", "frame_bytes", "frame_chunks", "CONTAINERS",
+           "flac_block", "flac_slot_bytes", "flac_frames_upto", "flac_emitted", "flac_frames_of", "flac_subframe",
+           "flac_frame", "flac_finish_ref", "flac_stream_header", "flac_encode_ref", "flac_slots_ref", "flac_crc8",
+           "flac_crc16", "FlacMux", "FLAC_MAX_K", "BASE_RATE", "HISTORY",
            "stretch_window", "stretch_ref", "stretch_emitted", "stretch_emitted_upto", "SPEED_MIN", "SPEED_MAX",
            "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY", "pitch_plan", "ratio_design", "ratio_emitted",
            "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY",

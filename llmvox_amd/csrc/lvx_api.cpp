@@ -212,7 +212,7 @@ struct lvx_ctx {
   int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
   // The PCM stages (pcm_host.h: the skeleton of their calls). Each has its device tables, a pool of two buffers per
   // slot [2][max_streams][*_HIST] and, in seg (under mu), the host mirror of every slot's segment.
-  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_STAGES };
+  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_FLAC, SEG_STAGES };
   std::vector<PcmSeg> seg[SEG_STAGES];
   float* pcm_taps = nullptr;  // rate and encoding: the taps of the three resampling rates
   float* pcm_hist = nullptr;
@@ -230,6 +230,7 @@ struct lvx_ctx {
   float* join_tail = nullptr;  // an open segment's current buffer holds the 320 samples not emitted yet
   float* lvl_win = nullptr;  // level: the window table w[-A .. A]
   float* lvl_hist = nullptr;  // (raw inputs)
+  int16_t* flac_hist = nullptr;  // FLAC: the s16 samples no frame has taken yet
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -733,8 +734,11 @@ int lvx_finalize(lvx_ctx* c) {
     if ((r = c->dalloc(&c->lvl_win, LVL_TAPS)) || (r = c->dalloc(&c->lvl_hist, (size_t)2 * S * LVL_HIST))) return r;
     HIP_TRY(hipMemcpy(c->lvl_win, win, sizeof(win), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->lvl_hist, 0, (size_t)2 * S * LVL_HIST * 4));
-    for (auto& v : c->seg) v.assign(S, PcmSeg{});
   }
+  // ---- PCM FLAC (allocated last: every other buffer stays where it was) ----
+  if ((r = c->dalloc(&c->flac_hist, (size_t)2 * S * FLAC_HIST))) return r;
+  HIP_TRY(hipMemset(c->flac_hist, 0, (size_t)2 * S * FLAC_HIST * 2));
+  for (auto& v : c->seg) v.assign(S, PcmSeg{});
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
   c->finalized = true;
@@ -1513,6 +1517,62 @@ int lvx_pcm_level(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* 
   return pcm_launches<PcmRows>(c, rows, [&](const PcmRows& pk, int nr, int max_out) {
     pcm_launch_level(pk, nr, max_out, gain, pcm, n_in, c->lvl_win, c->lvl_hist, out, out_stride, g_out, g_stride,
                      (hipStream_t)stream);
+  });
+}
+
+// ---- PCM FLAC ----
+int lvx_pcm_flac_block(int sample_rate) {
+  const int bs = flac_block(sample_rate);
+  if (!bs) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate) + " (24000, 16000, 8000, 48000)");
+  return bs;
+}
+
+int lvx_pcm_flac_emitted(int sample_rate, long long t0, int n_in, int final) {
+  const int bs = flac_block(sample_rate);
+  if (!bs) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate));
+  if (t0 < 0 || n_in < 0) return fail(LVX_E_ARG, "t0 and n_in must be >= 0");
+  return (int)(flac_frames_upto(bs, t0 + n_in, final != 0) - flac_frames_upto(bs, t0, false));
+}
+
+int lvx_flac_stream_header(int sample_rate, uint8_t* out, int cap) {
+  if (cap < 42 || !flac_stream_header(sample_rate, out)) return fail(LVX_E_ARG, "an unsupported sample rate, a null pointer or cap < 42");
+  return LVX_OK;
+}
+
+int lvx_flac_subframe(const int16_t* x, int n, uint8_t* out, int cap) {
+  const int r = flac_subframe(x, n, out, cap);
+  if (r == LVX_E_CAPACITY) return fail(r, "cap is smaller than the subframe");
+  if (r < 0) return fail(r, "n must be in 1 .. 65535, x / out not null");
+  return r;
+}
+
+int lvx_flac_finish(int sample_rate, const uint8_t* slots, int n_frames, unsigned long long* sample_no, uint8_t* out, int cap) {
+  if (n_frames > 0x7FFFFFFF / (2 * (FLAC_MAX_BS + 15) + 17)) return fail(LVX_E_ARG, "too many frames for one call");
+  const long long r = flac_finish(sample_rate, slots, n_frames, sample_no, out, cap);
+  if (r == LVX_E_CAPACITY) return fail(LVX_E_CAPACITY, "cap is smaller than the frames");
+  if (r < 0) return fail(LVX_E_ARG, "an unsupported sample rate, a null pointer, n_frames < 0, a record of no FLAC slot or a sample number past 2^36");
+  return (int)r;
+}
+
+int lvx_pcm_flac(lvx_ctx* c, const int16_t* s16, long long in_stride, int B, int n_in, const int32_t* slots,
+                 const uint8_t* final_host, int sample_rate, void* out, long long out_stride, int32_t* n_frames_host, void* stream) {
+  NEED_FINAL(c);
+  const int bs = flac_block(sample_rate);
+  if (!bs) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate) + " (24000, 16000, 8000, 48000)");
+  if (int r = pcm_args(B, n_in, s16, slots && final_host && n_frames_host ? slots : nullptr, true, out, out_stride)) return r;
+  if ((reinterpret_cast<uintptr_t>(s16) & 1) || in_stride < 0 || (in_stride & 1))
+    return fail(LVX_E_ARG, "s16_dev and in_stride_bytes must be multiples of 2");
+  std::vector<FlacRow> rows;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_FLAC], FLAC_HIST, B, n_in, slots, final_host, n_frames_host, sample_rate, true,
+        [](long long k) { return std::to_string(k) + " Hz"; }, rows,
+        [&](const PcmCall& q, FlacRow& r) { return plan_flac(q, n_in, sample_rate, in_stride, out_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
+  }
+  return pcm_launches<FlacRows>(c, rows, [&](const FlacRows& pk, int nr, int max_out) {
+    pcm_launch_flac(pk, nr, max_out, bs, s16, n_in, in_stride, c->flac_hist, out, out_stride, (hipStream_t)stream);
   });
 }
 

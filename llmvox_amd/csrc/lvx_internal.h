@@ -287,5 +287,7 @@ void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float*
 void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, const float* pcm, int n_in,
                       const float* win, float* hist, float* out, long long out_stride, float* g_out, long long g_stride,
                       hipStream_t s);
+void pcm_launch_flac(const FlacRows& rows, int n_rows, int max_frames, int bs, const int16_t* s16, int n_in,
+                     long long in_stride, int16_t* hist, void* out, long long out_stride, hipStream_t s);
 
 }  // namespace lvx

@@ -1,13 +1,15 @@
 // Host side of the PCM stages (include/llmvox.h: "PCM output stage", "PCM time stretch", "PCM pitch shift", "PCM dump
-// join", "PCM level", "PCM G.711"): the stages' constants and kernel row packets, the tables and streaming counts of
-// llmvox.h's rules in double, the G.711 companding, and the one skeleton every stage's entry point runs (lvx_api.cpp).
-// No HIP header and no device: tests/host/pcm_stage_check.cpp and g711_check.cpp drive all of it with the system
-// compiler.
+// join", "PCM level", "PCM G.711", "PCM FLAC"): the stages' constants and kernel row packets, the tables and streaming
+// counts of llmvox.h's rules in double, the G.711 companding, the FLAC stage's selection arithmetic and the host side of
+// its frames, and the one skeleton every stage's entry point runs (lvx_api.cpp). No HIP header and no device:
+// tests/host/pcm_stage_check.cpp, g711_check.cpp and flac_check.cpp drive all of it with the system compiler.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -89,6 +91,23 @@ constexpr int LVL_A = LVX_LEVEL_A;   // attack half-window
 constexpr int LVL_R = LVX_LEVEL_R;   // hold
 constexpr int LVL_TAPS = 2 * LVL_A + 1;
 constexpr int LVL_HIST = 1600;       // raw inputs of history a slot keeps between calls (an output reaches back <= 3 A + R = 1560)
+
+// PCM FLAC: the s16 rows of lvx_pcm_convert cut into frames, one subframe a workgroup
+constexpr int FLAC_MAX_BS = 1920;            // the block size at 48 kHz, the largest
+constexpr int FLAC_HIST = FLAC_MAX_BS + 16;  // int16 a slot keeps between calls: the <= BS + 15 samples no frame has taken yet
+constexpr int FLAC_MAX_N = 65535;            // samples of a frame lvx_flac_subframe takes (the device's are <= BS + 15)
+struct FlacRow {
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long j0;  // frames of the segment emitted before this call = index of the call's first frame
+  int n_out;     // frames of this call
+  int last_n;    // samples of the call's last frame (every frame before it has BS)
+  int hist_in;   // int16 offset of the slot's history [FLAC_HIST] (inputs t0 - FLAC_HIST .. t0 - 1) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int row;       // row of s16 / out
+};
+struct FlacRows {
+  FlacRow r[PCM_ROWS];
+};
 
 // ---------------- the rules' tables and counts ----------------
 // ---- PCM dump join: the window tables and the counts (llmvox.h) ----
@@ -296,6 +315,222 @@ constexpr int pcm_sample_bytes(int encoding) {
   return encoding == LVX_PCM_F32LE ? 4 : encoding == LVX_PCM_S16LE ? 2 : is_g711(encoding) ? 1 : 0;
 }
 
+// ---- PCM FLAC: the frame cuts, the subframe's selection arithmetic and the host side of a frame (llmvox.h) ----
+// The constexpr functions are the one statement of the cuts, the folding, the partition order, a difference and the
+// cost of a Rice parameter that pcm_flac_kernel and the host entries below both call, as g711_ulaw is shared.
+constexpr int flac_block(int rate) {  // BS = rate / 25 (40 ms); 0: not a rate of the stage
+  return rate == 8000 || rate == 16000 || rate == 24000 || rate == 48000 ? rate / 25 : 0;
+}
+constexpr int flac_rate_code(int rate) { return rate == 8000 ? 4 : rate == 16000 ? 5 : rate == 24000 ? 7 : 10; }
+constexpr int flac_slot_bytes(int bs) { return (8 + 1 + 2 * (bs + 15) + 15) / 16 * 16; }
+static_assert(flac_slot_bytes(flac_block(8000)) == LVX_FLAC_SLOT(8000) && flac_slot_bytes(FLAC_MAX_BS) == LVX_FLAC_SLOT(48000), "");
+// whole frames of BS a segment of T samples has in front of its last frame
+constexpr long long flac_full_frames(int bs, long long T) { return T >= 16 ? (T - 16) / bs : 0; }
+// frames of a segment emitted once T inputs are consumed: after a non-final call the whole ones; a final call adds
+// the frame of the remaining T - k BS samples
+constexpr long long flac_frames_upto(int bs, long long T, bool final) {
+  return flac_full_frames(bs, T) + (final && T > 0 ? 1 : 0);
+}
+constexpr unsigned flac_fold(int r) { return r >= 0 ? 2u * (unsigned)r : 2u * (unsigned)(-r) - 1u; }
+constexpr int flac_partition_order(int n) {  // n >= 1
+  int P = __builtin_ctz((unsigned)n) < 3 ? __builtin_ctz((unsigned)n) : 3;
+  while (P > 0 && (n >> P) < 16) --P;
+  return P;
+}
+// the p-th difference at a sample: x[i], x[i - 1], .. x[i - 4] (those beyond p are not read)
+constexpr int flac_diff(int p, int a, int b, int c, int d, int e) {
+  return p == 0 ? a : p == 1 ? a - b : p == 2 ? a - 2 * b + c : p == 3 ? a - 3 * b + 3 * c - d : a - 4 * b + 6 * c - 4 * d + e;
+}
+constexpr unsigned flac_rice_bits(unsigned u, int k) { return (u >> k) + 1u + (unsigned)k; }  // of one folded residual
+constexpr int FLAC_MAX_K = 14;
+
+// CRC-8 (polynomial 0x07) and CRC-16 (0x8005), initial value 0, not reflected: the tables
+struct FlacCrc {
+  uint8_t t8[256];
+  uint16_t t16[256];
+  constexpr FlacCrc() : t8{}, t16{} {
+    for (int i = 0; i < 256; ++i) {
+      unsigned a = (unsigned)i, b = (unsigned)i << 8;
+      for (int k = 0; k < 8; ++k) {
+        a = (a & 0x80u) ? ((a << 1) ^ 0x07u) & 0xFFu : (a << 1) & 0xFFu;
+        b = (b & 0x8000u) ? ((b << 1) ^ 0x8005u) & 0xFFFFu : (b << 1) & 0xFFFFu;
+      }
+      t8[i] = (uint8_t)a;
+      t16[i] = (uint16_t)b;
+    }
+  }
+};
+inline constexpr FlacCrc kFlacCrc{};
+inline unsigned flac_crc8(const uint8_t* p, size_t n) {
+  unsigned c = 0;
+  for (size_t i = 0; i < n; ++i) c = kFlacCrc.t8[c ^ p[i]];
+  return c;
+}
+inline unsigned flac_crc16(const uint8_t* p, size_t n) {
+  unsigned c = 0;
+  for (size_t i = 0; i < n; ++i) c = ((c << 8) & 0xFFFFu) ^ kFlacCrc.t16[(c >> 8) ^ p[i]];
+  return c;
+}
+
+// bits MSB first into a byte vector, zero-padded to a byte
+struct FlacBits {
+  std::vector<uint8_t> bytes;
+  int free_bits = 0;  // unused low bits of the last byte
+  void put(unsigned v, int len) {  // the low len bits of v, len <= 32
+    for (int i = len - 1; i >= 0; --i) {
+      if (free_bits == 0) {
+        bytes.push_back(0);
+        free_bits = 8;
+      }
+      --free_bits;
+      bytes.back() |= (uint8_t)(((v >> i) & 1u) << free_bits);
+    }
+  }
+  void zeros(unsigned n) {
+    for (; n > 0; --n) put(0, 1);
+  }
+};
+
+// lvx_flac_subframe: the subframe of x[0 .. n) by llmvox.h's rule, serially. Its bytes, or LVX_E_ARG (n outside
+// 1 .. 65535, a null pointer) or LVX_E_CAPACITY (cap smaller than the subframe; nothing is written)
+inline int flac_subframe(const int16_t* x, int n, uint8_t* out, int cap) {
+  if (n < 1 || n > FLAC_MAX_N || !x || !out || cap < 0) return LVX_E_ARG;
+  FlacBits w;
+  bool same = true;
+  for (int i = 1; i < n; ++i) same = same && x[i] == x[0];
+  if (same) {
+    w.put(0x00, 8);
+    w.put((uint16_t)x[0], 16);
+  } else {
+    auto diff = [&](int p, int i) {
+      return flac_diff(p, x[i], i >= 1 ? x[i - 1] : 0, i >= 2 ? x[i - 2] : 0, i >= 3 ? x[i - 3] : 0, i >= 4 ? x[i - 4] : 0);
+    };
+    int p = 0;
+    unsigned long long best = ~0ull;
+    for (int q = 0; q <= 4; ++q) {
+      unsigned long long e = 0;
+      for (int i = 4; i < n; ++i) e += (unsigned long long)std::abs(diff(q, i));
+      if (e < best) {
+        best = e;
+        p = q;
+      }
+    }
+    const int P = flac_partition_order(n), psize = n >> P;
+    std::vector<unsigned> u(n, 0);
+    for (int i = p; i < n; ++i) u[i] = flac_fold(diff(p, i));
+    int ks[8];
+    unsigned long long bits = 8 + 16ull * p + 2 + 4;
+    for (int j = 0; j < (1 << P); ++j) {
+      const int lo = std::max(p, j * psize), hi = (j + 1) * psize;
+      unsigned long long least = ~0ull;
+      for (int k = 0; k <= FLAC_MAX_K; ++k) {
+        unsigned long long c = 0;
+        for (int i = lo; i < hi; ++i) c += flac_rice_bits(u[i], k);
+        if (c < least) {
+          least = c;
+          ks[j] = k;
+        }
+      }
+      bits += 4 + least;
+    }
+    if (bits >= 8 + 16ull * n) {
+      w.put(0x02, 8);
+      for (int i = 0; i < n; ++i) w.put((uint16_t)x[i], 16);
+    } else {
+      w.put((8u | (unsigned)p) << 1, 8);
+      for (int i = 0; i < p; ++i) w.put((uint16_t)x[i], 16);
+      w.put(0, 2);
+      w.put((unsigned)P, 4);
+      for (int j = 0; j < (1 << P); ++j) {
+        const int k = ks[j];
+        w.put((unsigned)k, 4);
+        for (int i = std::max(p, j * psize); i < (j + 1) * psize; ++i) {
+          w.zeros(u[i] >> k);
+          w.put(1, 1);
+          w.put(u[i] & ((1u << k) - 1u), k);
+        }
+      }
+    }
+  }
+  if ((size_t)cap < w.bytes.size()) return LVX_E_CAPACITY;
+  std::copy(w.bytes.begin(), w.bytes.end(), out);
+  return (int)w.bytes.size();
+}
+
+// lvx_flac_stream_header: "fLaC" and the one STREAMINFO block, 42 bytes; false: not a rate of the stage
+inline bool flac_stream_header(int rate, uint8_t* out) {
+  const int bs = flac_block(rate);
+  if (!bs || !out) return false;
+  const uint8_t head[8] = {'f', 'L', 'a', 'C', 0x80, 0, 0, 34};
+  std::fill(out, out + 42, (uint8_t)0);
+  std::copy(head, head + 8, out);
+  out[8] = 0;
+  out[9] = 16;  // min blocksize
+  out[10] = (uint8_t)((bs + 15) >> 8);
+  out[11] = (uint8_t)(bs + 15);  // max blocksize; the frame sizes stay 0 (unknown)
+  // sample rate (20 bits), channels - 1 (3), bits per sample - 1 (5), total samples (36, 0: unknown)
+  const unsigned long long v = ((unsigned long long)rate << 44) | (15ull << 36);
+  for (int i = 0; i < 8; ++i) out[18 + i] = (uint8_t)(v >> (56 - 8 * i));
+  return true;  // the MD5 stays 0 (unknown)
+}
+
+// the sample number in FLAC's UTF-8-like coding (1 .. 7 bytes for a number below 2^36); its length
+inline int flac_utf8(unsigned long long v, uint8_t* out) {
+  if (v < 0x80) {
+    out[0] = (uint8_t)v;
+    return 1;
+  }
+  int len = 2;  // bytes: the first carries 7 - len bits (none at len 7), the others 6 each
+  while (len < 7 && v >= (1ull << (5 * len + 1))) ++len;
+  out[0] = (uint8_t)((0xFF00u >> len) & 0xFFu) | (uint8_t)(len < 7 ? v >> (6 * (len - 1)) : 0);
+  for (int i = 1; i < len; ++i) out[i] = (uint8_t)(0x80u | ((v >> (6 * (len - 1 - i))) & 0x3Fu));
+  return len;
+}
+
+// lvx_flac_finish: the n_frames slots the device wrote (records and subframes) made frames, the first at sample
+// number *sample_no. Bytes written, or LVX_E_ARG (a bad rate, a null pointer, n_frames < 0, a sample number past 2^36,
+// a record that is none of the stage's) or LVX_E_CAPACITY (cap too small): then nothing is written and *sample_no stays.
+inline long long flac_finish(int rate, const uint8_t* slots, int n_frames, unsigned long long* sample_no, uint8_t* out,
+                             long long cap) {
+  const int bs = flac_block(rate);
+  if (!bs || n_frames < 0 || !sample_no || cap < 0 || (n_frames > 0 && (!slots || !out))) return LVX_E_ARG;
+  const int slot = flac_slot_bytes(bs);
+  unsigned long long no = *sample_no;
+  long long need = 0;
+  for (int f = 0; f < n_frames; ++f) {
+    const uint8_t* s = slots + (size_t)f * slot;
+    const int n = s[0] | (s[1] << 8), body = s[2] | (s[3] << 8);
+    if (n < 1 || n > bs + 15 || body < 3 || body > 1 + 2 * n || (s[4] | s[5] | s[6] | s[7]) || no + n > (1ull << 36)) return LVX_E_ARG;
+    uint8_t num[7];
+    need += 4 + flac_utf8(no, num) + 3 + body + 2;
+    no += n;
+  }
+  if (need > cap) return LVX_E_CAPACITY;
+  no = *sample_no;
+  uint8_t* o = out;
+  for (int f = 0; f < n_frames; ++f) {
+    const uint8_t* s = slots + (size_t)f * slot;
+    const int n = s[0] | (s[1] << 8), body = s[2] | (s[3] << 8);
+    uint8_t* h = o;
+    *o++ = 0xFF;
+    *o++ = 0xF9;
+    *o++ = (uint8_t)(0x70 | flac_rate_code(rate));
+    *o++ = 0x08;
+    o += flac_utf8(no, o);
+    *o++ = (uint8_t)((n - 1) >> 8);
+    *o++ = (uint8_t)(n - 1);
+    *o = (uint8_t)flac_crc8(h, (size_t)(o - h));
+    ++o;
+    o = std::copy(s + 8, s + 8 + body, o);
+    const unsigned c = flac_crc16(h, (size_t)(o - h));
+    *o++ = (uint8_t)(c >> 8);
+    *o++ = (uint8_t)c;
+    no += n;
+  }
+  *sample_no = no;
+  return need;
+}
+
 // ---------------- the skeleton of a stage's call ----------------
 // A stage keeps one record per slot, the host mirror of the slot's open segment, and two history buffers per slot in a
 // device pool [2][slots][hist]: a call reads the current one and writes the other, so no launch reads what it writes.
@@ -447,6 +682,17 @@ inline std::string plan_join(const PcmCall& c, int n_in, int ctx_frames, long lo
   if (n_out * 4ll > out_stride) return stride_msg("out_stride_bytes", out_stride, n_out * 4ll);
   r = JoinRow{JOIN_HOLD * ctx_frames, !open ? JOIN_HEAD_NONE : ctx_frames > 0 ? JOIN_HEAD_FADE : JOIN_HEAD_TAIL, n_out, c.cur,
               c.final ? -1 : c.other, c.row};
+  return {};
+}
+
+// the key is the rate; every call that brings samples keeps the ones no frame has taken (so it turns the buffers)
+inline std::string plan_flac(const PcmCall& c, int n_in, int rate, long long in_stride, long long out_stride, FlacRow& r) {
+  const int bs = flac_block(rate);
+  if (n_in * 2ll > in_stride) return stride_msg("in_stride_bytes", in_stride, n_in * 2ll);
+  const long long t0 = c.seg.t0, j0 = flac_frames_upto(bs, t0, false), j1 = flac_frames_upto(bs, t0 + n_in, c.final);
+  if ((j1 - j0) * flac_slot_bytes(bs) > out_stride) return stride_msg("out_stride_bytes", out_stride, (j1 - j0) * flac_slot_bytes(bs));
+  const long long last = c.final ? t0 + n_in - flac_full_frames(bs, t0 + n_in) * bs : bs;
+  r = FlacRow{t0, j0, (int)(j1 - j0), (int)last, c.cur, n_in > 0 && !c.final ? c.other : -1, c.row};
   return {};
 }
 

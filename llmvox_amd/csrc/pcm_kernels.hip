@@ -9,7 +9,8 @@
 // frame and crossfades it with the next dump's rendering of it, launched only for a stream that asked.
 // And the volume control between the pitch control and the rate conversion ("PCM level"): a gain and a
 // feed-forward peak limiter (a sliding minimum and one fixed-order sum), launched only for a stream at
-// another volume than 100.
+// another volume than 100. And, behind the rate conversion's s16le rows, the lossless compressed output
+// ("PCM FLAC"): one FLAC subframe a workgroup, launched only for a stream that asked for "flac".
 #include <algorithm>
 
 #include "lvx_internal.h"
@@ -556,7 +557,240 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_level_kernel(PcmRows rows, fl
   if (g_out) store4(reinterpret_cast<float*>(g_out + (size_t)r.row * (size_t)g_stride) + mb + ml, gg, ml, nb);
 }
 
+
+// ---- PCM FLAC (llmvox.h, "PCM FLAC"): one subframe a workgroup ----
+// Grid (the most frames of a row, rows of the launch). Block (f, y) makes frame j0 + f of row y's segment: its
+// samples from the slot's kept ones and the call's int16 row into LDS; the five error sums and the all-equal test by
+// a workgroup reduction; the partitions' Rice parameters from bit counts (sum(u >> k) = sum over b >= k of
+// 2^(b - k) count_b, count_b the samples of the partition whose u has bit b: one wave ballot a bit, exactly the sum
+// the rule states, in uint32); every sample's bit length; an exclusive scan of the lengths (a wave64 shuffle scan,
+// then one pass over the wave totals); then every thread ORs its samples' stop bit and low bits, at most 15 bits in
+// at most two words, into a zeroed LDS word buffer (the unary zeros are the buffer's), and the buffer goes out
+// byte-swapped in 32-bit stores. Block (0, y) also writes the slot's next history. The selection arithmetic is
+// pcm_host.h's (flac_diff, flac_fold, flac_partition_order, flac_rice_bits), the one lvx_flac_subframe runs.
+constexpr int FLAC_THREADS = 256;
+constexpr int FLAC_SPT = 8;                                  // consecutive samples of a thread
+constexpr int FLAC_CAP = FLAC_THREADS * FLAC_SPT;            // 2048 >= BS + 15
+constexpr int FLAC_WORDS = (flac_slot_bytes(FLAC_MAX_BS) - 8) / 4;  // words of the largest slot's subframe
+constexpr int FLAC_UBITS = 21;                               // u < 2^21
+static_assert(FLAC_MAX_BS + 15 <= FLAC_CAP && FLAC_MAX_BS + 15 <= FLAC_HIST, "a frame fits a block and the history");
+static_assert(8 + 16 * (FLAC_MAX_BS + 15) <= 32 * (FLAC_WORDS - 1), "a word past the longest subframe's last stays inside the buffer");
+
+// the low len bits of v (len 1 .. 16) at bit pos of the stream (MSB first) into the word buffer
+__device__ __forceinline__ void flac_put(unsigned* words, unsigned pos, int len, unsigned v) {
+  const unsigned long long t = (unsigned long long)v << (64 - (int)(pos & 31u) - len);
+  const unsigned hi = (unsigned)(t >> 32), lo = (unsigned)t;
+  atomicOr(&words[pos >> 5], hi);
+  if (lo) atomicOr(&words[(pos >> 5) + 1], lo);
+}
+
+__global__ __launch_bounds__(FLAC_THREADS) void pcm_flac_kernel(FlacRows rows, int bs, const int16_t* __restrict__ s16,
+                                                                 int n_in, long long in_stride, int16_t* hist,
+                                                                 unsigned char* __restrict__ out, long long out_stride) {
+  const FlacRow r = rows.r[blockIdx.y];
+  const int16_t* __restrict__ x =
+      reinterpret_cast<const int16_t*>(reinterpret_cast<const unsigned char*>(s16) + (size_t)r.row * (size_t)in_stride);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
+  auto input = [&](long long g) -> int {  // segment input g from the call's row or the slot's history; zero outside
+    if (g < 0 || g >= t1) return 0;
+    if (g >= r.t0) return x[g - r.t0];
+    const long long back = r.t0 - g;
+    return back <= FLAC_HIST ? hist[r.hist_in + FLAC_HIST - back] : 0;
+  };
+  if (blockIdx.x == 0 && r.hist_out >= 0)
+    for (int i = tid; i < FLAC_HIST; i += FLAC_THREADS) hist[r.hist_out + i] = (int16_t)input(t1 - FLAC_HIST + i);
+  const int f = blockIdx.x;
+  if (f >= r.n_out) return;
+  const int n = min(f == r.n_out - 1 ? r.last_n : bs, FLAC_CAP);  // (<= BS + 15 by the plan)
+  const long long s0 = (r.j0 + f) * bs;                            // the frame's first sample in the segment
+  const int slot_bytes = flac_slot_bytes(bs);
+
+  __shared__ __attribute__((aligned(16))) int s_x[4 + FLAC_CAP];  // x[-4 .. FLAC_CAP): zeros in front and behind
+  __shared__ unsigned s_u[FLAC_CAP];                              // the folded residuals (0: a warm-up, none)
+  __shared__ unsigned s_w[FLAC_WORDS];
+  __shared__ unsigned s_cnt[8][FLAC_UBITS];
+  __shared__ unsigned s_red[FLAC_THREADS / 64][6];
+  __shared__ unsigned s_tot[FLAC_THREADS / 64];
+  __shared__ int s_k[8];
+  if (tid < 4) s_x[tid] = 0;
+  for (int i = tid; i < FLAC_CAP; i += FLAC_THREADS) s_x[4 + i] = i < n ? input(s0 + i) : 0;
+  for (int i = tid; i < FLAC_WORDS; i += FLAC_THREADS) s_w[i] = 0;
+  if (tid < 8 * FLAC_UBITS) (&s_cnt[0][0])[tid] = 0;
+  __syncthreads();
+
+  // the thread's samples i0 .. i0 + 7 and the four in front of them
+  const int i0 = tid * FLAC_SPT;
+  int w[4 + FLAC_SPT];
+  {
+    const int4* __restrict__ p4 = reinterpret_cast<const int4*>(s_x + i0);
+#pragma unroll
+    for (int q = 0; q < (4 + FLAC_SPT) / 4; ++q) {
+      const int4 v = p4[q];
+      w[4 * q] = v.x;
+      w[4 * q + 1] = v.y;
+      w[4 * q + 2] = v.z;
+      w[4 * q + 3] = v.w;
+    }
+  }
+  // E_p over i = 4 .. n - 1 (|r_4| <= 2^19 and n < 2^11: uint32) and whether any sample differs from x[0]
+  unsigned acc[6] = {0, 0, 0, 0, 0, 0};
+  const int x0 = s_x[4];
+#pragma unroll
+  for (int e = 0; e < FLAC_SPT; ++e) {
+    const int i = i0 + e;
+    if (i < n) {
+      if (w[e + 4] != x0) acc[5] = 1;
+      if (i >= 4) {
+#pragma unroll
+        for (int p = 0; p <= 4; ++p) acc[p] += (unsigned)abs(flac_diff(p, w[e + 4], w[e + 3], w[e + 2], w[e + 1], w[e]));
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc[q] += __shfl_xor(acc[q], m);
+    if (lane == 0) s_red[wave][q] = acc[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    acc[q] = 0;
+#pragma unroll
+    for (int v = 0; v < FLAC_THREADS / 64; ++v) acc[q] += s_red[v][q];
+  }
+  unsigned char* slot = out + (size_t)r.row * (size_t)out_stride + (size_t)f * (size_t)slot_bytes;
+  uint32_t* slot_w = reinterpret_cast<uint32_t*>(slot);
+  unsigned total_bits;  // of the subframe
+  if (acc[5] == 0) {    // CONSTANT
+    total_bits = 24;
+    if (tid == 0) flac_put(s_w, 8, 16, (unsigned)x0 & 0xFFFFu);  // (the header byte is 0)
+  } else {
+    int p = 0;
+#pragma unroll
+    for (int q = 1; q <= 4; ++q)
+      if (acc[q] < acc[p]) p = q;
+    unsigned u[FLAC_SPT];
+#pragma unroll
+    for (int e = 0; e < FLAC_SPT; ++e) {
+      const int i = i0 + e;
+      u[e] = i >= p && i < n ? flac_fold(flac_diff(p, w[e + 4], w[e + 3], w[e + 2], w[e + 1], w[e])) : 0u;
+      s_u[i] = u[e];
+    }
+    __syncthreads();
+    // the bit counts of every partition: the waves walk the samples in runs of 64 consecutive ones
+    const int P = flac_partition_order(n), psize = n >> P;
+    for (int e = 0; e < FLAC_SPT; ++e) {
+      const int i = e * FLAC_THREADS + tid;
+      const bool valid = i >= p && i < n;
+      const int j = valid ? min(i / psize, 7) : -1;
+      const unsigned ui = s_u[i];
+      unsigned long long todo = __ballot(valid);
+      while (todo) {
+        const int jj = __shfl(j, __ffsll((long long)todo) - 1);
+        const bool mine = j == jj;
+        todo &= ~__ballot(mine);
+        unsigned c = 0;
+#pragma unroll
+        for (int b = 0; b < FLAC_UBITS; ++b) {
+          const unsigned long long has = __ballot(mine && ((ui >> b) & 1u));
+          if (lane == b) c = (unsigned)__popcll(has);
+        }
+        if (lane < FLAC_UBITS && c) atomicAdd(&s_cnt[jj][lane], c);
+      }
+    }
+    __syncthreads();
+    if (tid < (1 << P)) {  // the partition's k: the least sum((u >> k) + 1 + k), the smallest k at a tie
+      const unsigned cnt = (unsigned)(psize - (tid == 0 ? p : 0));
+      unsigned least = 0xFFFFFFFFu;
+      int best = 0;
+      for (int k = 0; k <= FLAC_MAX_K; ++k) {
+        unsigned c = cnt * (unsigned)(1 + k);
+        for (int b = k; b < FLAC_UBITS; ++b) c += s_cnt[tid][b] << (b - k);
+        if (c < least) {
+          least = c;
+          best = k;
+        }
+      }
+      s_k[tid] = best;
+    }
+    __syncthreads();
+    // the bits of the thread's samples: a warm-up's 16, a residual's (u >> k) + 1 + k; the method and P (6 bits) ride
+    // in front of residual p, a partition's k (4 bits) in front of its first residual
+    unsigned len = 0;
+#pragma unroll
+    for (int e = 0; e < FLAC_SPT; ++e) {
+      const int i = i0 + e;
+      if (i < p) {
+        len += 16;
+      } else if (i < n) {
+        const int j = min(i / psize, 7);
+        len += flac_rice_bits(u[e], s_k[j]) + (i == p ? 10u : i == j * psize ? 4u : 0u);
+      }
+    }
+    unsigned scan = len;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+      const unsigned o = __shfl_up(scan, m);
+      if (lane >= m) scan += o;
+    }
+    if (lane == 63) s_tot[wave] = scan;
+    __syncthreads();
+    unsigned pos = 8 + scan - len, all = 0;
+#pragma unroll
+    for (int v = 0; v < FLAC_THREADS / 64; ++v) {
+      if (v < wave) pos += s_tot[v];
+      all += s_tot[v];
+    }
+    total_bits = 8 + all;
+    if (total_bits >= 8u + 16u * (unsigned)n) {  // VERBATIM
+      total_bits = 8u + 16u * (unsigned)n;
+      if (tid == 0) flac_put(s_w, 0, 8, 0x02u);
+#pragma unroll
+      for (int e = 0; e < FLAC_SPT; ++e)
+        if (i0 + e < n) flac_put(s_w, 8u + 16u * (unsigned)(i0 + e), 16, (unsigned)w[e + 4] & 0xFFFFu);
+    } else {  // FIXED: every position below lies under total_bits < 8 + 16 n, inside the buffer
+      if (tid == 0) flac_put(s_w, 0, 8, (8u | (unsigned)p) << 1);
+#pragma unroll
+      for (int e = 0; e < FLAC_SPT; ++e) {
+        const int i = i0 + e;
+        if (i < p) {
+          flac_put(s_w, pos, 16, (unsigned)w[e + 4] & 0xFFFFu);
+          pos += 16;
+        } else if (i < n) {
+          const int j = min(i / psize, 7), k = s_k[j];
+          if (i == p) {
+            flac_put(s_w, pos, 6, (unsigned)P);
+            pos += 6;
+          }
+          if (i == p || i == j * psize) {
+            flac_put(s_w, pos, 4, (unsigned)k);
+            pos += 4;
+          }
+          const unsigned q = u[e] >> k;
+          flac_put(s_w, pos + q, k + 1, (1u << k) | (u[e] & ((1u << k) - 1u)));
+          pos += q + 1u + (unsigned)k;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // the record {u16 n, u16 body_bytes, u32 0}, then the subframe's words, big-endian bytes; zeros to the slot's end
+  if (tid == 0) {
+    slot_w[0] = (uint32_t)n | (((total_bits + 7u) >> 3) << 16);
+    slot_w[1] = 0;
+  }
+  for (int i = tid; i < (slot_bytes - 8) / 4; i += FLAC_THREADS) slot_w[2 + i] = __builtin_bswap32(s_w[i]);
+}
+
 }  // namespace
+
+void pcm_launch_flac(const FlacRows& rows, int n_rows, int max_frames, int bs, const int16_t* s16, int n_in,
+                     long long in_stride, int16_t* hist, void* out, long long out_stride, hipStream_t s) {
+  pcm_flac_kernel<<<dim3((unsigned)std::max(1, max_frames), (unsigned)n_rows), FLAC_THREADS, 0, s>>>(
+      rows, bs, s16, n_in, in_stride, hist, (unsigned char*)out, out_stride);
+}
 
 void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, const float* pcm, int n_in,
                       const float* win, float* hist, float* out, long long out_stride, float* g_out, long long g_stride,

@@ -480,7 +480,9 @@ class Engine:
         (lvx_pcm_join, a format with ``join``: row b with ``ctx_frames[b]`` frames of context in front, None: none
         anywhere), the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the plan's L / M
         (lvx_pcm_ratio), the gain and limiter at volume_pct (lvx_pcm_level), the rate and the encoding
-        (lvx_pcm_convert). Rows may leave a stage with different counts: they pass the next one grouped by count.
+        (lvx_pcm_convert). A "flac" format runs that last stage as s16le and a sixth behind it (lvx_pcm_flac): its rows are
+        uint8, whole slots of LVX_FLAC_SLOT bytes (a record and a subframe each; ``audio.FlacMux`` makes them frames), and
+        counts[b] is their bytes. Rows may leave a stage with different counts: they pass the next one grouped by count.
         Asynchronous on the current stream; a slot's calls must be issued in order on one stream."""
         stretch_pct, (L, M), vol = fmt.stretch_pct, fmt.ratio, fmt.volume_pct
         slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
@@ -501,6 +503,13 @@ class Engine:
         # segment still has to advance).
         if not stages or not (fmt.sample_rate == 24000 and fmt.encoding == "f32le"):
             stages.append(lambda sub, sl, fl: self._pcm_resample(sub, sl, fl, fmt))
+        if fmt.encoding == "flac":  # the sixth stage, behind the s16le rows of the rate: whole slots, counted in bytes
+            rate, slot = fmt.sample_rate, ((8 + 1 + 2 * (fmt.sample_rate // 25 + 15) + 15) // 16) * 16
+
+            def flac(sub, sl, fl):
+                out, frames = self.pcm_flac(sub, sl, fl, rate)
+                return out, [n * slot for n in frames]
+            stages.append(flac)
         dtype = _PCM_ENCODINGS[fmt.encoding][1]
 
         def run(i, sub, sl, fl):  # stage i and, grouped by what it hands on, the stages behind it
@@ -536,10 +545,37 @@ class Engine:
                 counts[b] = n
         return out, counts
 
+    def pcm_flac(self, s16: Optional[torch.Tensor], slots, finals, sample_rate: int):
+        """The FLAC stage alone (lvx_pcm_flac): rows of ``s16`` (device int16 [B, n_in] at ``sample_rate``, what
+        ``pcm_convert`` writes as s16le; rows may be strided; None or n_in 0: flush only) continue the FLAC segments of
+        ``slots``; a true ``finals[b]`` emits the sentence's last frame and ends the segment. Returns (out, frames): a
+        device uint8 tensor [B, width] whose row b holds frames[b] slots of LVX_FLAC_SLOT(sample_rate) bytes, each the
+        record {u16 n, u16 body_bytes, u32 0} and the frame's subframe. Asynchronous on the current stream; a slot's
+        calls must be issued in order on one stream."""
+        slots = [int(s) for s in slots]
+        B, n_in, stride = len(slots), 0, 0
+        if s16 is not None and s16.shape[1]:
+            if s16.shape[0] != B or s16.dtype != torch.int16 or s16.device != self.device:
+                raise ValueError(f"s16 must be an int16 [{B}, n_in] tensor on {self.device}")
+            if s16.stride(1) != 1 or (B > 1 and s16.stride(0) < s16.shape[1]):
+                s16 = s16.contiguous()
+            n_in, stride = int(s16.shape[1]), 2 * int(s16.stride(0) if B > 1 else s16.shape[1])
+        sl, fl = (ctypes.c_int32 * B)(*slots), (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
+        cnt = (ctypes.c_int32 * B)()
+        bs = int(sample_rate) // 25
+        slot = ((8 + 1 + 2 * (bs + 15) + 15) // 16) * 16
+        # (a call emits at most the frames of its own samples and the kept BS + 15, and the last one)
+        width = ((n_in + bs + 15) // max(bs, 1) + 1) * slot
+        out = torch.empty(B, width, device=self.device, dtype=torch.uint8)
+        _lib.check(self.lib.lvx_pcm_flac(self.h, _ptr(s16) if n_in else None, stride, B, n_in, sl, fl, int(sample_rate),
+                                         _ptr(out), width, cnt, self.stream_handle()))
+        return out, list(cnt)
+
     def _pcm_resample(self, pcm: Optional[torch.Tensor], slots, finals, fmt):
-        """pcm_convert without the speed and the pitch: the rate and the encoding (lvx_pcm_convert)."""
+        """pcm_convert without the speed and the pitch: the rate and the encoding (lvx_pcm_convert; a "flac" format: as
+        s16le, the FLAC stage's input)."""
         pcm, n_in, B, sl, fl, cnt, same = self._pcm_args(pcm, slots, finals)
-        enc, dtype = _PCM_ENCODINGS[fmt.encoding]
+        enc, dtype = _PCM_ENCODINGS["s16le" if fmt.encoding == "flac" else fmt.encoding]
         if fmt.sample_rate == 24000 and fmt.encoding == "f32le":  # the rows are the output (nothing is launched)
             out, width = same, n_in
         else:
@@ -586,7 +622,8 @@ class Engine:
 
 # an audio.AudioFormat's encoding: (the LVX_PCM_* value, the dtype of the rows lvx_pcm_convert writes)
 _PCM_ENCODINGS = {"f32le": (_lib.LVX_PCM_F32LE, torch.float32), "s16le": (_lib.LVX_PCM_S16LE, torch.int16),
-                  "ulaw": (_lib.LVX_PCM_ULAW, torch.uint8), "alaw": (_lib.LVX_PCM_ALAW, torch.uint8)}
+                  "ulaw": (_lib.LVX_PCM_ULAW, torch.uint8), "alaw": (_lib.LVX_PCM_ALAW, torch.uint8),
+                  "flac": (None, torch.uint8)}  # (no encoding of lvx_pcm_convert: lvx_pcm_flac behind its s16le rows)
 
 
 def build_engine(device_index=0, weight_dtype="fp32", kv_dtype="fp32", seed=1234, max_streams=8,

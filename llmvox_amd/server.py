@@ -320,13 +320,24 @@ class TTSService:
     def chunks(self, session: _Session, timeout: float = 0.05, frame_ms: Optional[int] = None):
         """``frame_ms`` (one of ``audio.FRAME_MS``): the body behind the WAV header is re-cut on the host into whole
         frames of that duration, the last one filled with the encoding's silence (``audio.frame_chunks``); None:
-        the scheduler's chunks as they come."""
+        the scheduler's chunks as they come. A "flac" session: the stream header first, then every chunk (the device's
+        slots of subframes) made frames here, where the speaking order and so each frame's sample number is known
+        (``audio.FlacMux``); FLAC frames have no fixed size, so ``frame_ms`` with it is a ValueError."""
         w = session.worker
+        flac = session.audio is not None and session.audio.encoding == "flac"
+        if flac and frame_ms is not None:
+            self.close(session)
+            raise ValueError("frame_ms with encoding 'flac': FLAC frames have no fixed byte size")
         try:
             if session.audio is not None and session.audio.container == "wav":
                 from .audio import wav_header
                 yield wav_header(session.audio)
             body = audio_chunks(session.queues[0], session.queues[1], timeout=timeout, stop=lambda: w.error is not None)
+            if flac:
+                from .audio import FlacMux
+                mux = FlacMux(session.audio.sample_rate)
+                yield mux.header()
+                body = (frames for frames in map(mux.push, body) if frames)
             if frame_ms is not None:
                 from .audio import AudioFormat, frame_chunks
                 body = frame_chunks(body, session.audio if session.audio is not None else AudioFormat(), frame_ms)
@@ -423,7 +434,9 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     (a float in 0.0 .. 4.0; 1.0: as spoken; a bool, a non-number, a non-finite or an out-of-range value: 422) is the
     loudness: the PCM is multiplied by round(volume * 100) percent and peak-limited at -1 dBFS on the device
     (``audio.level_ref``), which holds back 10 ms of every sentence until its end; the response carries it in
-    ``X-Audio-Volume``. ``encoding`` also takes "ulaw" and "alaw": 8-bit G.711, the s16le samples companded on the
+    ``X-Audio-Volume``. ``encoding`` also takes "flac" at any of the four rates: a native FLAC stream (``fLaC``, one
+    STREAMINFO block, then frames of 40 ms) of the s16le samples, lossless, media type audio/flac; it is its own container
+    ("wav" with it: 422) and its frames have no fixed size (``frame_ms`` with it: 422). ``encoding`` also takes "ulaw" and "alaw": 8-bit G.711, the s16le samples companded on the
     device (``audio.g711_encode``), at any of the four rates; their WAV header is the 58-byte form of a non-PCM tag.
     ``frame_ms`` (10, 20, 30, 40 or 60; null or absent: the chunks as they come; anything else, a bool or a float
     included: 422) cuts the body behind the WAV header, on the host, into chunks of whole frames of that duration, the
@@ -445,6 +458,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join,
                                 volume_pct_of(volume))
     default_frame_ms = frame_ms_of(frame_ms)
+    if default_frame_ms is not None and default_audio.encoding == "flac":
+        raise ValueError("frame_ms with encoding 'flac': FLAC frames have no fixed byte size")
 
     class TTSRequest(BaseModel):
         text: str
@@ -517,6 +532,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         sp = sampling_of(request)
         fmt = audio_of(request)
         ms = frames_of(request)
+        if ms is not None and fmt.encoding == "flac":
+            raise HTTPException(status_code=422, detail="frame_ms with encoding 'flac': FLAC frames have no fixed byte size")
         kw = {} if sp is None else {"sampling": sp}
         if not fmt.is_default:  # (a default request reaches submit exactly as it always did)
             kw["audio"] = fmt
@@ -572,8 +589,8 @@ def arg_parser():
     ap.add_argument("--repetition-window", type=int, default=64, help="how many recent tokens it covers (1 .. 256)")
     ap.add_argument("--sample-rate", type=int, default=24000, choices=[24000, 16000, 8000, 48000],
                     help="output sample rate of requests that name none")
-    ap.add_argument("--encoding", default="f32le", choices=["f32le", "s16le", "ulaw", "alaw"],
-                    help="their sample encoding (ulaw / alaw: 8-bit G.711)")
+    ap.add_argument("--encoding", default="f32le", choices=["f32le", "s16le", "ulaw", "alaw", "flac"],
+                    help="their sample encoding (ulaw / alaw: 8-bit G.711; flac: a lossless FLAC stream of the s16le samples)")
     ap.add_argument("--frame-ms", type=int, default=None, choices=[10, 20, 30, 40, 60],
                     help="cut the body of requests that name no frame_ms into whole frames of this duration (default: no framing)")
     ap.add_argument("--container", default="raw", choices=["raw", "wav"], help="their container (wav: a header first)")
