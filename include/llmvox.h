@@ -404,7 +404,10 @@ int lvx_stream_position(lvx_ctx* ctx, int slot, int* pos_out, void* stream);
  *                     pending mlp copies into x (three launches and their gaps less per layer);
  *                     0: the three launches (bit-identical: tests/test_gpu_la_fused.py). The per-op entry
  *                     points (lvx_probe_kernel, lvx_attn_probe, lvx_ar_ops) plan without the tables, so
- *                     they go on running and timing the separate kernels whatever this option says. */
+ *                     they go on running and timing the separate kernels whatever this option says;
+ *   "fmt_group"    0: lvx_pcm_formant chooses, per launch, how many output hop blocks a workgroup writes (few
+ *                     in a small launch, up to 32 in a large one); 1 .. 32: that many (bit-identical at every
+ *                     value: tests/test_gpu_pcm_formant.py). */
 int lvx_set_option(lvx_ctx* ctx, const char* name, int value);
 /* The stream the decode graphs are captured on (then replayed on the caller's stream). NULL (default):
  * the caller's stream. Name another one when something may query, from another thread, an event
@@ -758,6 +761,80 @@ int lvx_pcm_level_emitted(int volume_pct, long long t0, int n_in, int final);
 int lvx_pcm_level(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
                   const uint8_t* final_host, int volume_pct, float* out_dev, long long out_stride_bytes,
                   int32_t* n_out_host, float* g_out_dev, long long g_stride_bytes, void* stream);
+
+/* ---- PCM formant --------------------------------------------------------------
+ * The formant control: a correction of the spectral envelope, because the pitch control is a resampling and moves
+ * the vocal-tract resonances with f0. It runs AFTER the ratio resampler and BEFORE the level stage, always at the
+ * nominal 24 kHz: a seventh stage. A stream that names no formant never comes here.
+ *
+ * The plan (integers, lvx_pcm_formant_plan). After the ratio stage the envelope sits at r = M / L times the model's,
+ * (L, M) lvx_pcm_pitch_plan's. To leave it at formant_pct / 100 the stage corrects by
+ *   rho = (100 M) / (formant_pct L), in lowest terms Fn / Fd, valid iff Fd <= 2 Fn and Fn <= 2 Fd.
+ * Fn == Fd is the identity: nothing is launched. The envelope of the output at bin k is that of the input at k rho.
+ *
+ * The rule is a short-time Fourier transform with a fixed fp32 order, so the device output is bit-identical to a host
+ * evaluation of the same order (llmvox_amd/audio.py: formant_ref) and INDEPENDENT OF CHUNKING.
+ * Constants: N = 1024 the frame, H = 256 the hop, K = 12 the smoothing half-width in bins, e = the fp32 nearest to
+ * 1e-10, the clamp [1/256, 256] on the squared gain (+-24 dB), s = the fp32 nearest to 2/3.
+ * Tables, built on the host in double, each entry rounded once to fp32 (lvx_pcm_formant_tables):
+ *   w[n] = 0.5 - 0.5 cos(2 pi (n + 0.5) / N),  n = 0 .. N - 1;
+ *   c[d] = (0.5 + 0.5 cos(pi d / (K + 1))) / (K + 1),  d = -K .. K  (25 taps; their sum is 1);
+ *   the twiddles exp(-2 pi i k / N): tr[k] = cos(2 pi k / N), ti[k] = -sin(2 pi k / N),  k = 0 .. N / 2 - 1.
+ *
+ * One segment is one sentence of one stream: x[0 .. T), x = 0 outside. Frame j (j >= 0) covers the inputs
+ * [(j - 3) H, (j + 1) H). Only + - * / and the square root occur, each correctly rounded to fp32, no fused multiply-add.
+ * A complex product (a + b i)(wr + wi i) is (fl(fl(a wr) - fl(b wi)), fl(fl(a wi) + fl(b wr))).
+ *   DFT_N: radix 2, decimation in time. The input goes to bit-reversed places: a[rev10(n)] = in[n]. Then ten stages,
+ *     h = 1, 2, .. 512: for every i whose bit h is clear, with p = i mod h: t = a[i + h] (tr + ti i)[p N / (2 h)] (the
+ *     product above), then a[i] = u + t and a[i + h] = u - t componentwise, u the old a[i]. EVERY stage runs the full
+ *     product, the first (whose twiddle is 1 - 0 i) included. The inverse transform is the same with ti negated,
+ *     followed by the product with 2^-10.
+ *   1. X = DFT_N(fl(w[n] frame[n]) + 0 i).
+ *   2. P[k] = fl(fl(re re) + fl(im im)),  k = 0 .. N / 2.
+ *   3. P[-k] = P[k] and P[N / 2 + k] = P[N / 2 - k].
+ *   4. E[k]: acc = 0, then for d = -K .. K ascending acc = fl(acc + fl(c[d] P[k + d])).
+ *   5. i = (k Fn) div Fd;  f = fl(float((k Fn) mod Fd) / float(Fd));  Es = E[N / 2] where i >= N / 2, otherwise
+ *      Es = fl(E[i] + fl(f fl(E[i + 1] - E[i]))).
+ *   6. G2 = min(max(fl(fl(Es + e) / fl(E[k] + e)), 1/256), 256);  G = sqrt(G2). (Silence: e / e = 1, no 0 / 0.)
+ *   7. Y[k] = (fl(G re), fl(G im)),  k = 0 .. N / 2;  Y[N - k] = conj(Y[k]),  k = 1 .. N / 2 - 1.
+ *   8. y_j[n] = fl(w[n] fl(2^-10 re(a[n]))), a the inverse transform of Y (its imaginary part is not used).
+ * Output sample n, in hop block b = n div H: fl(s (((y_b + y_{b+1}) + y_{b+2}) + y_{b+3})[n]), each frame read at
+ * its own index of n, the frames added in ascending j, every sum rounded. (The four shifted w^2 sum to 1.5.)
+ * Dependence: output n depends on x[(b - 3) H .. (b + 4) H) only. THE CONCATENATED OUTPUTS OF ANY CHUNKING OF A
+ * SEGMENT ARE BIT-IDENTICAL TO ITS ONE-SHOT OUTPUT, and, for finite input, bit-identical to audio.formant_ref. (A NaN
+ * or an infinity reaches every bin of the frames that cover it, and a power that overflows gives inf / inf: in those
+ * frames the device and numpy may differ, because which NaN an operation returns, and what min and max make of one
+ * (the device's drop it, numpy's keep it), is each processor's own. Codec PCM is finite.)
+ *
+ * Streaming. After a non-final call that brings the consumed input to T the emitted outputs are the
+ * n < max(0, (T div H - 3) H); a final call emits up to T: a stream holds back 768 .. 1023 samples (32 .. 43 ms)
+ * until more arrives or its sentence's final call. The first output of a call reaches back at most 7 H - 1 = 1791
+ * inputs before the call's first input, so the library keeps, per KV slot, the last 1792 inputs of the previous call
+ * (two buffers per slot: a launch reads one and writes the other) and, on the host, a mirror of the slot's consumed
+ * count and ratio: a slot's calls are issued in order on one stream. A segment has one ratio: another before its
+ * final call is LVX_E_ARG. */
+#define LVX_FORMANT_N 1024
+#define LVX_FORMANT_H 256
+#define LVX_FORMANT_K 12
+/* host only: Fn / Fd of a speed, a pitch and a formant, each in percent (the outputs may be NULL). LVX_E_ARG: one of
+ * them outside [50, 200], a pair of speed and pitch lvx_pcm_pitch_plan rejects, or a ratio outside 1/2 .. 2. */
+int lvx_pcm_formant_plan(int speed_pct, int pitch_pct, int formant_pct, int* Fn, int* Fd);
+/* host only: the fp32 tables: w [1024], c [25] (c[-12 .. 12]), tw [1024] (tr[0 .. 512) then ti[0 .. 512)). A NULL
+ * table is left out; cap_w, cap_c, cap_tw are the floats each holds. LVX_E_ARG: a table given with a smaller cap. */
+int lvx_pcm_formant_tables(float* w_host, int cap_w, float* c_host, int cap_c, float* tw_host, int cap_tw);
+/* host only: samples a formant call emits for a slot that has consumed t0 inputs of its segment (negative:
+ * LVX_E_ARG for t0 < 0 or n_in < 0) */
+int lvx_pcm_formant_emitted(long long t0, int n_in, int final);
+/* lvx_pcm_level's conventions: rows b of pcm_dev [B][n_in] f32 continue the formant segments of slots_host[b];
+ * final_host[b] != 0 emits the rest and resets the slot; n_in may be 0 with final (flush only). out row b (f32)
+ * starts at out_dev + b * out_stride_bytes; n_out_host[b] = samples written. Fn == Fd (1 / 1): nothing is launched
+ * and nothing written, the rows of pcm_dev are the output (n_out_host[b] = n_in; out_dev may be NULL). LVX_E_ARG (and
+ * no slot's state changed): Fn / Fd not coprime, outside 1 .. 40000 or 1/2 .. 2, or another than the slot's open
+ * segment has, B < 1, n_in < 0, a slot out of range or named twice, out_dev / out_stride_bytes not a multiple of 4
+ * or a stride smaller than a row's output. lvx_pcm_reset also forgets a slot's formant state. */
+int lvx_pcm_formant(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
+                    const uint8_t* final_host, int Fn, int Fd, float* out_dev, long long out_stride_bytes,
+                    int32_t* n_out_host, void* stream);
 
 /* ---- PCM FLAC ------------------------------------------------------------------
  * A lossless compressed output: a sixth stage BEHIND lvx_pcm_convert. Its input is the s16le samples of the

@@ -133,6 +133,10 @@ _SIGS = {
     "lvx_pcm_level_window": (_I, [_P, _I]),
     "lvx_pcm_level_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
     "lvx_pcm_level": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P]),
+    "lvx_pcm_formant_plan": (_I, [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "lvx_pcm_formant_tables": (_I, [_P, _I, _P, _I, _P, _I]),
+    "lvx_pcm_formant_emitted": (_I, [ctypes.c_longlong, _I, _I]),
+    "lvx_pcm_formant": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, ctypes.c_longlong, _P, _P]),
     "lvx_pcm_flac_block": (_I, [_I]),
     "lvx_pcm_flac_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
     "lvx_flac_stream_header": (_I, [_I, _P, _I]),

@@ -8,7 +8,9 @@ pitch into a stretch and a resampling ratio L / M, and the resampler of that rat
 rate conversion): ``pitch_plan``, ``ratio_ref``. And the join of a sentence's dumps ("PCM dump join": a held-back
 frame crossfaded with the next dump's rendering of it, in front of the other three): ``join_ref``. And the volume
 control ("PCM level": a gain and a feed-forward peak limiter, between the ratio and the rate conversion):
-``level_ref``. And the G.711 encodings ("PCM G.711": the s16 quantisation companded to 8-bit mu-law or A-law, integer
+``level_ref``. And the formant control ("PCM formant": the integer plan of the envelope correction Fn / Fd and a
+short-time Fourier correction of the spectral envelope, between the ratio and the level): ``formant_plan``,
+``formant_ref``. And the G.711 encodings ("PCM G.711": the s16 quantisation companded to 8-bit mu-law or A-law, integer
 arithmetic only): ``g711_encode``, ``g711_decode``. And the FLAC output ("PCM FLAC": the s16 samples cut into frames of
 40 ms, each a CONSTANT, FIXED or VERBATIM subframe, integer arithmetic only): ``flac_subframe``, ``flac_frame``,
 ``flac_encode_ref``, and ``FlacMux``, which finishes the device's subframes into frames on the delivery path."""
@@ -48,6 +50,14 @@ LEVEL_A = 120           # the limiter's attack half-window in samples (LVX_LEVEL
 LEVEL_R = 1200          # its hold (LVX_LEVEL_R): 50 ms
 LEVEL_CEIL = np.float32(0.8912509)  # its ceiling c (LVX_LEVEL_CEIL): -1 dBFS
 LEVEL_HISTORY = 1600    # inputs of history a slot keeps between level calls
+FORMANT_MIN, FORMANT_MAX = 50, 200  # formant_pct of a stream (None: the formants follow the pitch, no stage)
+FORMANT_N = 1024        # the formant stage's frame length (LVX_FORMANT_N)
+FORMANT_H = 256         # its hop (LVX_FORMANT_H)
+FORMANT_K = 12          # its smoothing half-width in bins (LVX_FORMANT_K)
+FORMANT_EPS = np.float32(1e-10)  # the floor added to both envelope values
+FORMANT_G2_MIN, FORMANT_G2_MAX = np.float32(1.0 / 256.0), np.float32(256.0)  # the clamp on the squared gain: +-24 dB
+FORMANT_MAX_TERM = 40000  # Fn and Fd of a correction ratio the stage takes: 1 .. 40000, coprime, within 1/2 .. 2
+FORMANT_HISTORY = 1792  # inputs of history a slot keeps between formant calls (7 H)
 FLAC_MAX_K = 14         # the largest Rice parameter the FLAC stage chooses (the escape code is never used)
 
 
@@ -68,6 +78,30 @@ def pitch_plan(speed_pct: int, pitch_pct: int) -> Tuple[int, int, int]:
     return stretch, stretch // g, speed_pct // g
 
 
+def _check_formant_pct(formant_pct) -> int:
+    if isinstance(formant_pct, bool) or not isinstance(formant_pct, (int, np.integer)) \
+            or not FORMANT_MIN <= formant_pct <= FORMANT_MAX:
+        raise ValueError(f"formant_pct must be an integer in [{FORMANT_MIN}, {FORMANT_MAX}], got {formant_pct!r}")
+    return int(formant_pct)
+
+
+def formant_plan(speed_pct: int, pitch_pct: int, formant_pct: int) -> Tuple[int, int]:
+    """(Fn, Fd) of a stream's speed, pitch and formant, all integers (``lvx_pcm_formant_plan``): behind the
+    resampling by L / M of ``pitch_plan`` the spectral envelope sits at M / L times the model's; to leave it at
+    formant_pct / 100 the formant stage corrects by rho = (100 M) / (formant_pct L), in lowest terms Fn / Fd.
+    1 / 1: no stage. ValueError: a percentage outside [50, 200], a pair ``pitch_plan`` rejects, or a rho outside
+    1/2 .. 2."""
+    _, L, M = pitch_plan(speed_pct, pitch_pct)
+    formant_pct = _check_formant_pct(formant_pct)
+    n, d = 100 * M, formant_pct * L
+    g = gcd(n, d)
+    Fn, Fd = n // g, d // g
+    if Fd > 2 * Fn or Fn > 2 * Fd:
+        raise ValueError(f"speed_pct {speed_pct}, pitch_pct {pitch_pct} and formant_pct {formant_pct} need an envelope "
+                         f"correction of {Fn} / {Fd}, outside 1/2 .. 2")
+    return Fn, Fd
+
+
 @dataclass(frozen=True)
 class AudioFormat:
     """What a stream's audio is delivered as. The default is the reference's: headerless float32 at 24 kHz."""
@@ -78,6 +112,9 @@ class AudioFormat:
     pitch_pct: int = 100  # pitch in percent (a stretch and a resampling of the PCM, ``pitch_plan``; 100: none)
     join: bool = False    # click-free dump joins: context frames and a crossfade at every dump boundary (``join_ref``)
     volume_pct: int = 100  # volume in percent (a gain and a peak limiter on the PCM, ``level_ref``; 100: none)
+    # where the formants sit, in percent of the model's own (``formant_ref`` behind the resampling; None: they follow
+    # the pitch, no stage)
+    formant_pct: Optional[int] = None
 
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
@@ -100,18 +137,21 @@ class AudioFormat:
         if isinstance(self.volume_pct, bool) or not isinstance(self.volume_pct, int) \
                 or not VOLUME_MIN <= self.volume_pct <= VOLUME_MAX:
             raise ValueError(f"volume_pct must be an integer in [{VOLUME_MIN}, {VOLUME_MAX}], got {self.volume_pct!r}")
+        if self.formant_pct is not None:
+            formant_plan(self.speed_pct, self.pitch_pct, self.formant_pct)  # (the three together: the ratio must exist)
 
     @property
     def is_default(self) -> bool:
         return (self.sample_rate == BASE_RATE and self.encoding == "f32le" and self.container == "raw"
-                and self.speed_pct == 100 and self.pitch_pct == 100 and not self.join and self.volume_pct == 100)
+                and self.speed_pct == 100 and self.pitch_pct == 100 and not self.join and self.volume_pct == 100
+                and self.formant_pct is None)
 
     @property
     def converts(self) -> bool:
-        """The samples differ from the codec's (another rate, encoding, speed, pitch or volume, or joined dumps):
-        the stream needs the device stage."""
+        """The samples differ from the codec's (another rate, encoding, speed, pitch, volume or formant, or joined
+        dumps): the stream needs the device stage."""
         return (self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
-                or self.pitch_pct != 100 or self.join or self.volume_pct != 100)
+                or self.pitch_pct != 100 or self.join or self.volume_pct != 100 or self.formant != (1, 1))
 
     @property
     def stretch_pct(self) -> int:
@@ -122,6 +162,23 @@ class AudioFormat:
     def ratio(self) -> Tuple[int, int]:
         """(L, M) of the resampling behind the stretch (``pitch_plan``): (1, 1) without a pitch."""
         return pitch_plan(self.speed_pct, self.pitch_pct)[1:]
+
+    @property
+    def formant(self) -> Tuple[int, int]:
+        """(Fn, Fd) of the envelope correction behind the resampling (``formant_plan``): (1, 1) without a formant, and
+        where the named formant is where the pitch has put the envelope anyway."""
+        if self.formant_pct is None:
+            return 1, 1
+        return formant_plan(self.speed_pct, self.pitch_pct, self.formant_pct)
+
+    @property
+    def formant_moved(self) -> float:
+        """The factor by which the spectral envelope moves against the model's own voice: formant_pct / 100 where the
+        format names one, the realised pitch ratio M / L where it does not."""
+        if self.formant_pct is not None:
+            return self.formant_pct / 100.0
+        L, M = self.ratio
+        return M / L
 
     @property
     def sample_bytes(self) -> int:
@@ -849,16 +906,159 @@ def level_ref(x, volume_pct: int, window=None, n0: int = 0, n1: Optional[int] = 
     return y, g
 
 
-def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, level_win=None) -> np.ndarray:
+# ---- the formant control's rule (include/llmvox.h, "PCM formant"), in numpy -----------------------------
+
+def _check_formant(Fn: int, Fd: int):
+    if not (1 <= Fn <= FORMANT_MAX_TERM and 1 <= Fd <= FORMANT_MAX_TERM and Fd <= 2 * Fn and Fn <= 2 * Fd
+            and gcd(Fn, Fd) == 1):
+        raise ValueError(f"Fn / Fd must be coprime, each in 1 .. {FORMANT_MAX_TERM}, with Fd <= 2 Fn and Fn <= 2 Fd, "
+                         f"got {Fn} / {Fd}")
+
+
+def formant_tables() -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(w float32 [1024], c float32 [25], tw float32 [1024]): the formant stage's window w[n] = 0.5 - 0.5 cos(2 pi
+    (n + 0.5) / N), its smoothing taps c[d] = (0.5 + 0.5 cos(pi d / (K + 1))) / (K + 1), d = -K .. K, and the
+    twiddles exp(-2 pi i k / N), k < N / 2 (tw[:512] the real parts cos(2 pi k / N), tw[512:] the imaginary parts
+    -sin(2 pi k / N)), built in double, each entry rounded once (the library's own: ``lvx_pcm_formant_tables``)."""
+    N, K = FORMANT_N, FORMANT_K
+    n = np.arange(N, dtype=np.float64)
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * (n + 0.5) / N)
+    d = np.arange(-K, K + 1, dtype=np.float64)
+    c = (0.5 + 0.5 * np.cos(np.pi * d / (K + 1))) / (K + 1)
+    k = np.arange(N // 2, dtype=np.float64)
+    tw = np.concatenate([np.cos(2.0 * np.pi * k / N), -np.sin(2.0 * np.pi * k / N)])
+    return w.astype(np.float32), c.astype(np.float32), tw.astype(np.float32)
+
+
+def formant_emitted_upto(T: int, final: bool) -> int:
+    """Samples of a segment the formant stage has emitted once T inputs are consumed (after a non-final / a final
+    call): a hop block waits for the four frames that cover it, so the last 768 .. 1023 wait for more input."""
+    if final:
+        return T
+    return max(0, (T // FORMANT_H - 3) * FORMANT_H)
+
+
+def formant_emitted(t0: int, n_in: int, final: bool) -> int:
+    """Samples a formant call emits for a slot that has consumed t0 inputs of its segment
+    (``lvx_pcm_formant_emitted``)."""
+    if t0 < 0 or n_in < 0:
+        raise ValueError("t0 and n_in must be >= 0")
+    return formant_emitted_upto(t0 + n_in, final) - formant_emitted_upto(t0, False)
+
+
+_FORMANT_REV = np.array([int(format(n, "010b")[::-1], 2) for n in range(FORMANT_N)], dtype=np.int64)
+
+
+def _formant_dft(re: np.ndarray, im: np.ndarray, tr: np.ndarray, ti: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The rule's DFT_N of float32 [..., N] (natural order in and out) with the twiddles tr + ti i: radix 2, decimation
+    in time, ten stages of whole-array float32 operations, each product and each sum rounded on its own."""
+    N = FORMANT_N
+    lead = re.shape[:-1]
+    re, im = re[..., _FORMANT_REV], im[..., _FORMANT_REV]
+    h = 1
+    while h < N:
+        wr, wi = tr[::N // (2 * h)], ti[::N // (2 * h)]  # the h twiddles of the stage
+        a, b = re.reshape(lead + (N // (2 * h), 2, h)), im.reshape(lead + (N // (2 * h), 2, h))
+        ur, ui, vr, vi = a[..., 0, :], b[..., 0, :], a[..., 1, :], b[..., 1, :]
+        pr = vr * wr - vi * wi
+        pi = vr * wi + vi * wr
+        re = np.stack([ur + pr, ur - pr], axis=-2).reshape(lead + (N,))
+        im = np.stack([ui + pi, ui - pi], axis=-2).reshape(lead + (N,))
+        h *= 2
+    return re, im
+
+
+def _formant_frames(x: np.ndarray, Fn: int, Fd: int, j0: int, j1: int, tables) -> Tuple[np.ndarray, np.ndarray]:
+    """Frames j0 .. j1 - 1 of the segment x[..., T) by the rule's eight steps: (y float32 [..., j1 - j0, N], the
+    gains G float32 [..., j1 - j0, N / 2 + 1])."""
+    N, H, K = FORMANT_N, FORMANT_H, FORMANT_K
+    w, c, tw = tables
+    tr, ti = tw[:N // 2], tw[N // 2:]
+    T = x.shape[-1]
+    lo, hi = (j0 - 3) * H, (j1 + 3) * H  # frame j covers [(j - 3) H, (j + 1) H); the rest is slack
+    xs = np.zeros(x.shape[:-1] + (hi - lo,), dtype=np.float32)
+    a, b = max(lo, 0), min(hi, T)
+    if b > a:
+        xs[..., a - lo:b - lo] = x[..., a:b]
+    fr = np.lib.stride_tricks.sliding_window_view(xs, N, axis=-1)[..., ::H, :][..., :j1 - j0, :]
+    with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
+        re, im = _formant_dft(w * fr, np.zeros(fr.shape, dtype=np.float32), tr, ti)  # 1.
+        re, im = re[..., :N // 2 + 1], im[..., :N // 2 + 1]
+        P = re * re + im * im  # 2.
+        at = np.abs(np.arange(-K, N // 2 + 1 + K))
+        Pe = P[..., np.where(at > N // 2, N - at, at)]  # 3.
+        E = np.zeros(P.shape, dtype=np.float32)
+        for d in range(2 * K + 1):  # 4. d ascending: acc = fl(acc + fl(c[d] P[k + d]))
+            E = E + c[d] * Pe[..., d:d + N // 2 + 1]
+        kn = np.arange(N // 2 + 1, dtype=np.int64) * Fn  # 5.
+        i = kn // Fd
+        f = (kn % Fd).astype(np.float32) / np.float32(Fd)
+        i0 = np.minimum(i, N // 2 - 1)
+        e0 = E[..., i0]
+        Es = np.where(i >= N // 2, E[..., N // 2:], e0 + f * (E[..., i0 + 1] - e0))
+        G2 = np.minimum(np.maximum((Es + FORMANT_EPS) / (E + FORMANT_EPS), FORMANT_G2_MIN), FORMANT_G2_MAX)  # 6.
+        G = np.sqrt(G2).astype(np.float32)
+        yr, yi = G * re, G * im  # 7.
+        yr = np.concatenate([yr, yr[..., N // 2 - 1:0:-1]], axis=-1)
+        yi = np.concatenate([yi, -yi[..., N // 2 - 1:0:-1]], axis=-1)
+        back = _formant_dft(yr, yi, tr, -ti)[0]
+        y = w * (np.float32(2.0 ** -10) * back)  # 8.
+    return y.astype(np.float32), G
+
+
+def formant_gains(x, Fn: int, Fd: int, tables=None) -> np.ndarray:
+    """The gains G[j, k] float32 [..., ceil(T / H) + 3, 513] every frame of the segment x applies to its bins."""
+    _check_formant(Fn, Fd)
+    x = np.asarray(x, dtype=np.float32)
+    tables = formant_tables() if tables is None else tuple(np.asarray(t, dtype=np.float32) for t in tables)
+    return _formant_frames(x, Fn, Fd, 0, -(-x.shape[-1] // FORMANT_H) + 3, tables)[1]
+
+
+def formant_ref(x, Fn: int, Fd: int, tables=None, n0: int = 0, n1: Optional[int] = None) -> np.ndarray:
+    """Outputs n0 .. n1 - 1 (default: all T; n0 a multiple of H) of the segment x[0 .. T) (float32 at 24 kHz, zero
+    outside) with its spectral envelope moved by Fd / Fn (the envelope of the output at bin k is that of the input at
+    k Fn / Fd): frames of 1024 at a hop of 256, in each the smoothed power spectrum looked up at k Fn / Fd over
+    itself, the square root of that as a gain on the bins, and the overlap-add of the four frames that cover a hop,
+    every operation fp32 in the rule's order (the transform's factorisation included): the bits the device computes
+    (``lvx_pcm_formant``) with the same fp32 tables. ``tables``: (w, c, tw) (default: built here; the device tests pass
+    the library's). 1 / 1 is evaluated like any other (the service never sends such a stream here). The bit identity
+    is for finite input: a NaN or an infinity spreads through its frames' transforms, and there the device may differ
+    (which NaN an operation returns is the processor's; the device's min and max drop a NaN, numpy's keep it)."""
+    _check_formant(Fn, Fd)
+    H = FORMANT_H
+    x = np.asarray(x, dtype=np.float32)
+    T = x.shape[-1]
+    if n1 is None:
+        n1 = T
+    if n0 % H:
+        raise ValueError("n0 must be a multiple of the hop")
+    if n1 <= n0:
+        return np.zeros(x.shape[:-1] + (0,), dtype=np.float32)
+    tables = formant_tables() if tables is None else tuple(np.asarray(t, dtype=np.float32) for t in tables)
+    b0, b1 = n0 // H, -(-n1 // H)  # the hop blocks of the outputs; block b is covered by the frames b .. b + 3
+    y = _formant_frames(x, Fn, Fd, b0, b1 + 3, tables)[0]
+    nb = b1 - b0
+    acc = y[..., 0:nb, 3 * H:]  # the frames in ascending j: ((y_b + y_b+1) + y_b+2) + y_b+3
+    for q in (1, 2, 3):
+        acc = acc + y[..., q:q + nb, (3 - q) * H:(4 - q) * H]
+    out = np.float32(2.0 / 3.0) * acc
+    return out.reshape(x.shape[:-1] + (nb * H,))[..., :n1 - n0].astype(np.float32)
+
+
+def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, level_win=None,
+                formant_tabs=None) -> np.ndarray:
     """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, volume, rate and encoding (a float32,
-    int16 or uint8 array): stretched at the plan's stretch_pct, resampled by its L / M, levelled at its volume_pct, then
-    resampled to the rate and encoded. ``ratio_taps``: the fp32 table of the format's ratio (default: designed
-    here); ``level_win``: the level stage's fp32 window (default: built here)."""
-    stretch, (L, M) = fmt.stretch_pct, fmt.ratio
+    int16 or uint8 array): stretched at the plan's stretch_pct, resampled by its L / M, its envelope corrected by
+    the plan's Fn / Fd, levelled at its volume_pct, then resampled to the rate and encoded. ``ratio_taps``: the fp32
+    table of the format's ratio (default: designed here); ``level_win``: the level stage's fp32 window (default:
+    built here); ``formant_tabs``: the formant stage's fp32 tables (default: built here)."""
+    stretch, (L, M), (Fn, Fd) = fmt.stretch_pct, fmt.ratio, fmt.formant
     if stretch != 100:
         x = stretch_ref(x, stretch, windows)[0]
     if L != M:
         x = ratio_ref(x, L, M, ratio_taps)
+    if Fn != Fd:
+        x = formant_ref(x, Fn, Fd, formant_tabs)
     if fmt.volume_pct != 100:
         x = level_ref(x, fmt.volume_pct, level_win)[0]
     return encode_ref(resample_ref(x, fmt.sample_rate, taps), fmt)
@@ -868,12 +1068,18 @@ class StreamRef:
     """The streaming form of the rule for one slot, on the host: ``push(x, final)`` returns the samples the
     call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_join`` when the format joins its dumps, then
     ``lvx_pcm_stretch`` when the plan has a stretch, then ``lvx_pcm_ratio`` when it has a ratio, then
-    ``lvx_pcm_level`` when it has a volume, then ``lvx_pcm_convert`` and, a FLAC format, ``lvx_pcm_flac`` behind it as s16le:
-    the slots of the frames the call emits). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the
-    whole segment; for tests and stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
+    ``lvx_pcm_formant`` when it has an envelope correction, then ``lvx_pcm_level`` when it has a volume, then
+    ``lvx_pcm_convert`` and, a FLAC format, ``lvx_pcm_flac`` behind it as s16le: the slots of the frames the call
+    emits). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the whole segment; for
+    tests and stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
 
-    def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, join_windows=None, level_win=None):
+    def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, join_windows=None, level_win=None,
+                 formant_tabs=None):
         self.fmt, self.taps, self.ratio_taps = fmt, taps, ratio_taps
+        self.Fn, self.Fd = fmt.formant
+        if self.Fn != self.Fd:
+            tabs = formant_tables() if formant_tabs is None else formant_tabs
+            self.formant_tabs = tuple(np.asarray(t, dtype=np.float32) for t in tabs)
         if fmt.volume_pct != 100:
             self.level_win = level_window() if level_win is None else np.asarray(level_win, dtype=np.float32)
         if fmt.join:
@@ -894,6 +1100,8 @@ class StreamRef:
         self.mid: List[np.ndarray] = []  # the ratio resampler's view: the stretched segment and its count
         self.mid_t0 = 0
         self.join_tail: Optional[np.ndarray] = None  # the join's view: the held-back frame (None: closed)
+        self.fmn: List[np.ndarray] = []  # the formant stage's view: the resampled segment and its count
+        self.fmn_t0 = 0
         self.lvl: List[np.ndarray] = []  # the level stage's view: the resampled segment and its count
         self.lvl_t0 = 0
         self.fq: List[np.ndarray] = []  # the FLAC stage's view: the segment's s16 samples and their count
@@ -905,6 +1113,13 @@ class StreamRef:
         self.mid.append(x)
         self.mid_t0 += x.size
         return ratio_ref(np.concatenate(self.mid), self.L, self.M, self.ratio_taps, m0, m1)
+
+    def _formant(self, x, final: bool) -> np.ndarray:
+        n0 = formant_emitted_upto(self.fmn_t0, False)
+        n1 = formant_emitted_upto(self.fmn_t0 + x.size, final)
+        self.fmn.append(x)
+        self.fmn_t0 += x.size
+        return formant_ref(np.concatenate(self.fmn), self.Fn, self.Fd, self.formant_tabs, n0, n1)
 
     def _level(self, x, final: bool) -> np.ndarray:
         pct = self.fmt.volume_pct
@@ -937,6 +1152,8 @@ class StreamRef:
             x = self._stretch(x, final)
         if self.L != self.M:
             x = self._ratio(x, final)
+        if self.Fn != self.Fd:
+            x = self._formant(x, final)
         if self.fmt.volume_pct != 100:
             x = self._level(x, final)
         rate = self.fmt.sample_rate
@@ -972,4 +1189,7 @@ __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "re
            "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY",
            "join_window", "join_emitted", "join_ref", "JOIN_HOLD", "JOIN_CONTEXT",
            "level_window", "level_emitted", "level_emitted_upto", "level_ref", "VOLUME_MIN", "VOLUME_MAX",
-           "LEVEL_A", "LEVEL_R", "LEVEL_CEIL", "LEVEL_HISTORY"]
+           "LEVEL_A", "LEVEL_R", "LEVEL_CEIL", "LEVEL_HISTORY",
+           "formant_plan", "formant_tables", "formant_emitted", "formant_emitted_upto", "formant_ref", "formant_gains",
+           "FORMANT_MIN", "FORMANT_MAX", "FORMANT_N", "FORMANT_H", "FORMANT_K", "FORMANT_EPS", "FORMANT_MAX_TERM",
+           "FORMANT_HISTORY"]

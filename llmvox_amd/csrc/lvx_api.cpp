@@ -212,7 +212,7 @@ struct lvx_ctx {
   int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
   // The PCM stages (pcm_host.h: the skeleton of their calls). Each has its device tables, a pool of two buffers per
   // slot [2][max_streams][*_HIST] and, in seg (under mu), the host mirror of every slot's segment.
-  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_FLAC, SEG_STAGES };
+  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_FLAC, SEG_FORMANT, SEG_STAGES };
   std::vector<PcmSeg> seg[SEG_STAGES];
   float* pcm_taps = nullptr;  // rate and encoding: the taps of the three resampling rates
   float* pcm_hist = nullptr;
@@ -231,6 +231,8 @@ struct lvx_ctx {
   float* lvl_win = nullptr;  // level: the window table w[-A .. A]
   float* lvl_hist = nullptr;  // (raw inputs)
   int16_t* flac_hist = nullptr;  // FLAC: the s16 samples no frame has taken yet
+  float* fmt_tab = nullptr;   // formant: the tables [FMT_TABLES]: w, c, the twiddles
+  float* fmt_hist = nullptr;
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -738,6 +740,14 @@ int lvx_finalize(lvx_ctx* c) {
   // ---- PCM FLAC (allocated last: every other buffer stays where it was) ----
   if ((r = c->dalloc(&c->flac_hist, (size_t)2 * S * FLAC_HIST))) return r;
   HIP_TRY(hipMemset(c->flac_hist, 0, (size_t)2 * S * FLAC_HIST * 2));
+  // ---- PCM formant (allocated last: every other buffer stays where it was) ----
+  {
+    std::vector<float> tab(FMT_TABLES);
+    formant_design(tab.data(), tab.data() + FMT_N, tab.data() + FMT_N + FMT_TAPS);
+    if ((r = c->dalloc(&c->fmt_tab, FMT_TABLES)) || (r = c->dalloc(&c->fmt_hist, (size_t)2 * S * FMT_HIST))) return r;
+    HIP_TRY(hipMemcpy(c->fmt_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(c->fmt_hist, 0, (size_t)2 * S * FMT_HIST * 4));
+  }
   for (auto& v : c->seg) v.assign(S, PcmSeg{});
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
@@ -877,6 +887,7 @@ int lvx_set_option(lvx_ctx* c, const char* name, int value) {
   else if (n == "l0q") o.l0q = value != 0;
   else if (n == "l0a") o.l0a = value != 0;
   else if (n == "laf") o.laf = value != 0;
+  else if (n == "fmt_group") o.fmt_group = std::min(std::max(value, 0), 32);
   else return fail(LVX_E_NAME, "unknown option " + n);
   ++c->opt_epoch;  // this context's captured kernels change (checked in cached_graph)
   return LVX_OK;
@@ -1517,6 +1528,54 @@ int lvx_pcm_level(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* 
   return pcm_launches<PcmRows>(c, rows, [&](const PcmRows& pk, int nr, int max_out) {
     pcm_launch_level(pk, nr, max_out, gain, pcm, n_in, c->lvl_win, c->lvl_hist, out, out_stride, g_out, g_stride,
                      (hipStream_t)stream);
+  });
+}
+
+// ---- PCM formant ----
+int lvx_pcm_formant_plan(int speed_pct, int pitch_pct, int formant_pct, int* Fn, int* Fd) {
+  if (formant_pct < 50 || formant_pct > 200) return fail(LVX_E_ARG, "formant_pct must be in [50, 200], got " + std::to_string(formant_pct));
+  if (int r = lvx_pcm_pitch_plan(speed_pct, pitch_pct, nullptr, nullptr, nullptr)) return r;
+  int n = 0, d = 0;
+  if (!formant_plan(speed_pct, pitch_pct, formant_pct, &n, &d))
+    return fail(LVX_E_ARG, "speed_pct " + std::to_string(speed_pct) + ", pitch_pct " + std::to_string(pitch_pct) + " and formant_pct " +
+                               std::to_string(formant_pct) + " need an envelope correction outside 1/2 .. 2");
+  if (Fn) *Fn = n;
+  if (Fd) *Fd = d;
+  return LVX_OK;
+}
+
+int lvx_pcm_formant_tables(float* w_host, int cap_w, float* c_host, int cap_c, float* tw_host, int cap_tw) {
+  if ((w_host && cap_w < FMT_N) || (c_host && cap_c < FMT_TAPS) || (tw_host && cap_tw < FMT_N))
+    return fail(LVX_E_ARG, "w_host holds fewer than 1024 floats, c_host fewer than 25 or tw_host fewer than 1024");
+  formant_design(w_host, c_host, tw_host);
+  return LVX_OK;
+}
+
+int lvx_pcm_formant_emitted(long long t0, int n_in, int final) {
+  if (t0 < 0 || n_in < 0) return fail(LVX_E_ARG, "t0 and n_in must be >= 0");
+  return (int)(formant_emitted_upto(t0 + n_in, final != 0) - formant_emitted_upto(t0, false));
+}
+
+int lvx_pcm_formant(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const uint8_t* final_host,
+                    int Fn, int Fd, float* out, long long out_stride, int32_t* n_out_host, void* stream) {
+  NEED_FINAL(c);
+  if (!formant_ok(Fn, Fd)) return fail(LVX_E_ARG, formant_msg(Fn, Fd));
+  const bool launch = Fn != Fd;  // 1 / 1: the rows of pcm_dev are the output
+  if (int r = pcm_args(B, n_in, pcm, slots && final_host && n_out_host ? slots : nullptr, launch, out, out_stride)) return r;
+  std::vector<PcmRow> rows;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_FORMANT], FMT_HIST, B, n_in, slots, final_host, n_out_host, ratio_key(Fn, Fd), launch,
+        [](long long k) { return "the ratio " + std::to_string(k >> 16) + " / " + std::to_string(k & 0xffff); }, rows,
+        [&](const PcmCall& q, PcmRow& r) { return plan_formant(q, n_in, Fn, Fd, out_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
+  }
+  if (!launch) return LVX_OK;
+  const Opts o = c->opts_snapshot();
+  OptScope os(&o);
+  return pcm_launches<PcmRows>(c, rows, [&](const PcmRows& pk, int nr, int max_out) {
+    pcm_launch_formant(pk, nr, max_out, Fn, Fd, pcm, n_in, c->fmt_tab, c->fmt_hist, out, out_stride, (hipStream_t)stream);
   });
 }
 

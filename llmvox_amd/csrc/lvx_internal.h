@@ -52,6 +52,8 @@ struct Opts {
   int laf = 1;           // the same steps (l0a on): LayerNorm and c_attn of layers 1-3 inside their attention blocks
                          // (ar_attn_la_kernel); 0: ar_rows_kernel + c_attn + attention (bit-identical:
                          // tests/test_gpu_la_fused.py)
+  int fmt_group = 0;     // formant stage: hop blocks a workgroup writes, 1 .. 32; 0: chosen per launch from its rows and
+                         // their lengths (pcm_launch_formant). Bit-identical at every value: tests/test_gpu_pcm_formant.py
 };
 const Opts& opts();  // the calling thread's bound options (the defaults when none is bound)
 struct OptScope {    // binds `o` to this thread until the scope ends
@@ -287,6 +289,9 @@ void pcm_launch_join(const JoinRows& rows, int n_rows, int max_out, const float*
 void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, const float* pcm, int n_in,
                       const float* win, float* hist, float* out, long long out_stride, float* g_out, long long g_stride,
                       hipStream_t s);
+// Fn / Fd: the correction ratio, coprime, each <= FMT_MAX; tab: w [FMT_N], c [FMT_TAPS], the twiddles [FMT_N]
+void pcm_launch_formant(const PcmRows& rows, int n_rows, int max_out, int Fn, int Fd, const float* pcm, int n_in,
+                        const float* tab, float* hist, float* out, long long out_stride, hipStream_t s);
 void pcm_launch_flac(const FlacRows& rows, int n_rows, int max_frames, int bs, const int16_t* s16, int n_in,
                      long long in_stride, int16_t* hist, void* out, long long out_stride, hipStream_t s);
 

@@ -1,8 +1,8 @@
 // Host side of the PCM stages (include/llmvox.h: "PCM output stage", "PCM time stretch", "PCM pitch shift", "PCM dump
-// join", "PCM level", "PCM G.711", "PCM FLAC"): the stages' constants and kernel row packets, the tables and streaming
+// join", "PCM level", "PCM formant", "PCM G.711", "PCM FLAC"): the stages' constants and kernel row packets, the tables and streaming
 // counts of llmvox.h's rules in double, the G.711 companding, the FLAC stage's selection arithmetic and the host side of
 // its frames, and the one skeleton every stage's entry point runs (lvx_api.cpp). No HIP header and no device:
-// tests/host/pcm_stage_check.cpp, g711_check.cpp and flac_check.cpp drive all of it with the system compiler.
+// tests/host/pcm_stage_check.cpp, g711_check.cpp, flac_check.cpp and formant_check.cpp drive all of it with the system compiler.
 #pragma once
 #include <stdint.h>
 
@@ -108,6 +108,17 @@ struct FlacRow {
 struct FlacRows {
   FlacRow r[PCM_ROWS];
 };
+
+// PCM formant: the spectral-envelope correction. The rows travel as PcmRows: t0 the inputs consumed before the call,
+// m0 the outputs emitted before it (a multiple of FMT_H), hist_in / hist_out float offsets of [FMT_HIST] buffers.
+constexpr int FMT_N = LVX_FORMANT_N;      // frame length
+constexpr int FMT_H = LVX_FORMANT_H;      // hop
+constexpr int FMT_K = LVX_FORMANT_K;      // smoothing half-width in bins
+constexpr int FMT_TAPS = 2 * FMT_K + 1;
+constexpr int FMT_BINS = FMT_N / 2 + 1;   // bins 0 .. N / 2 of a real signal's spectrum
+constexpr int FMT_HIST = 7 * FMT_H;       // inputs of history a slot keeps between calls (a call's first output reaches back <= 7 H - 1)
+constexpr int FMT_MAX = 40000;            // Fn and Fd of a correction ratio: 1 .. 40000 (the plan's are <= 100 * 200 and 200 * 200)
+constexpr int FMT_TABLES = FMT_N + FMT_TAPS + FMT_N;  // floats of the device tables: w, c, then the twiddles (re then im)
 
 // ---------------- the rules' tables and counts ----------------
 // ---- PCM dump join: the window tables and the counts (llmvox.h) ----
@@ -252,6 +263,47 @@ inline void level_design(float* w) {
 inline long long level_emitted_upto(int pct, long long T, bool final) {
   if (pct == 100 || final) return T;
   return std::max(0ll, T - 2 * LVL_A);
+}
+
+// ---- PCM formant: the plan, the tables and the streaming counts (llmvox.h) ----
+// coprime 1 <= Fn, Fd <= 40000 with Fd <= 2 Fn and Fn <= 2 Fd
+inline bool formant_ok(int Fn, int Fd) {
+  return Fn >= 1 && Fd >= 1 && Fn <= FMT_MAX && Fd <= FMT_MAX && Fd <= 2 * Fn && Fn <= 2 * Fd && gcd_of(Fn, Fd) == 1;
+}
+inline std::string formant_msg(int Fn, int Fd) {
+  return "Fn / Fd must be coprime, each in 1 .. 40000, with Fd <= 2 Fn and Fn <= 2 Fd, got " + std::to_string(Fn) + " / " + std::to_string(Fd);
+}
+// rho = (100 M) / (formant_pct L) in lowest terms, (L, M) the resampling of speed_pct and pitch_pct (lvx_pcm_pitch_plan's:
+// L / M = stretch_pct / speed_pct). false: a percentage outside [50, 200], a stretch outside, or rho outside 1/2 .. 2
+inline bool formant_plan(int speed_pct, int pitch_pct, int formant_pct, int* Fn, int* Fd) {
+  if (speed_pct < 50 || speed_pct > 200 || pitch_pct < 50 || pitch_pct > 200 || formant_pct < 50 || formant_pct > 200) return false;
+  const int st = (200 * speed_pct + pitch_pct) / (2 * pitch_pct);  // speed 100 / pitch, rounded half up
+  if (st < 50 || st > 200) return false;
+  const int g = gcd_of(st, speed_pct), L = st / g, M = speed_pct / g;
+  const int n = 100 * M, d = formant_pct * L, h = gcd_of(n, d);
+  if (!formant_ok(n / h, d / h)) return false;
+  *Fn = n / h;
+  *Fd = d / h;
+  return true;
+}
+
+// w[n] = 0.5 - 0.5 cos(2 pi (n + 0.5) / N) [N]; c[d] = (0.5 + 0.5 cos(pi d / (K + 1))) / (K + 1), d = -K .. K [2 K + 1];
+// the twiddles exp(-2 pi i k / N), k < N / 2: tw[k] = cos(2 pi k / N), tw[N / 2 + k] = -sin(2 pi k / N) [N]. In double,
+// each entry rounded to fp32 once; a null table is left out
+inline void formant_design(float* w, float* c, float* tw) {
+  const double pi = 3.14159265358979323846;
+  for (int n = 0; w && n < FMT_N; ++n) w[n] = (float)(0.5 - 0.5 * std::cos(2.0 * pi * (n + 0.5) / FMT_N));
+  for (int d = -FMT_K; c && d <= FMT_K; ++d) c[d + FMT_K] = (float)((0.5 + 0.5 * std::cos(pi * d / (FMT_K + 1))) / (FMT_K + 1));
+  for (int k = 0; tw && k < FMT_N / 2; ++k) {
+    tw[k] = (float)std::cos(2.0 * pi * k / FMT_N);
+    tw[FMT_N / 2 + k] = (float)(-std::sin(2.0 * pi * k / FMT_N));
+  }
+}
+
+// samples of a segment emitted once T inputs are consumed: a hop block waits for the four frames that cover it
+inline long long formant_emitted_upto(long long T, bool final) {
+  if (final) return T;
+  return std::max(0ll, (T / FMT_H - 3) * FMT_H);
 }
 
 // ---- PCM G.711: the companding of an s16 sample and its inverse (llmvox.h), integers only ----
@@ -658,6 +710,12 @@ inline std::string plan_level(const PcmCall& c, int n_in, int pct, long long out
   std::string e = plan_counted(c, n_in, [&](long long T, bool f) { return level_emitted_upto(pct, T, f); }, true, true, 4, out_stride, r);
   if (e.empty() && want_g && r.n_out * 4ll > g_stride) e = stride_msg("g_stride_bytes", g_stride, r.n_out * 4ll);
   return e;
+}
+
+inline std::string plan_formant(const PcmCall& c, int n_in, int Fn, int Fd, long long out_stride, PcmRow& r) {
+  r = PcmRow{0, 0, n_in, 0, -1, c.row};
+  if (Fn == Fd) return {};  // 1 / 1: the rows of pcm_dev are the output
+  return plan_counted(c, n_in, [&](long long T, bool f) { return formant_emitted_upto(T, f); }, true, true, 4, out_stride, r);
 }
 
 inline std::string plan_stretch(const PcmCall& c, int n_in, int pct, long long out_stride, bool want_d, int d_stride, StretchRow& r) {

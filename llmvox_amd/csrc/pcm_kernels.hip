@@ -10,7 +10,9 @@
 // And the volume control between the pitch control and the rate conversion ("PCM level"): a gain and a
 // feed-forward peak limiter (a sliding minimum and one fixed-order sum), launched only for a stream at
 // another volume than 100. And, behind the rate conversion's s16le rows, the lossless compressed output
-// ("PCM FLAC"): one FLAC subframe a workgroup, launched only for a stream that asked for "flac".
+// ("PCM FLAC"): one FLAC subframe a workgroup, launched only for a stream that asked for "flac". And the
+// formant control between the pitch control and the volume control ("PCM formant"): a short-time Fourier
+// correction of the spectral envelope in LDS, launched only for a stream that named a formant.
 #include <algorithm>
 
 #include "lvx_internal.h"
@@ -784,7 +786,177 @@ __global__ __launch_bounds__(FLAC_THREADS) void pcm_flac_kernel(FlacRows rows, i
   for (int i = tid; i < (slot_bytes - 8) / 4; i += FLAC_THREADS) slot_w[2 + i] = __builtin_bswap32(s_w[i]);
 }
 
+// ---- PCM formant (llmvox.h, "PCM formant"): the envelope correction, a short-time Fourier transform in LDS ----
+// Grid (groups of `group` output hop blocks, rows of the launch). Workgroup (x, y) writes the hop blocks
+// [x group, (x + 1) group) of row y's call: it runs the group + 3 frames that cover them one after the
+// other in ascending j, each through the rule's eight steps (the window into bit-reversed places, ten radix-2 stages of
+// 512 butterflies, two a thread, the power, the 25-tap smoothing, the gain, the Hermitian spectrum through registers
+// into bit-reversed places again, ten stages back), and adds the frame's four quarters to the four hop blocks they
+// cover. A thread owns sample tid of every hop block, so the sums are its own words of a four-block ring: the block's
+// first frame sets, the next three add, in ascending j as the rule states, and the block goes out after its fourth.
+// No float atomics and no scratch: the frames a neighbouring group also needs (3 of group + 3) are computed twice.
+// group 1 is "one workgroup per output hop block computes its four frames": the shortest chain of frames, which a
+// launch too small to fill the device wants; a large launch wants the redundancy small. pcm_launch_formant chooses;
+// the bits do not depend on the choice (a block's four frames are added in the same order in any group).
+// Block (0, y) also writes the slot's next history.
+constexpr int FMT_GROUP_MAX = 32;
+constexpr int FMT_WGS = 1024;  // workgroups a launch aims at: four a CU
+constexpr int FMT_PER = FMT_N / PCM_THREADS;  // samples of a frame a thread moves: tid + 256 q, one of each quarter
+constexpr int FMT_HALF = FMT_N / 2;
+static_assert(FMT_N == 1024 && FMT_H == PCM_THREADS && FMT_PER == 4, "a thread owns one sample of each of a frame's four hop blocks");
+static_assert(FMT_HIST >= 7 * FMT_H - 1, "the history covers what a call's first output reaches back");
+
+__device__ __forceinline__ int fmt_rev(int n) { return (int)(__builtin_bitreverse32((unsigned)n) >> 22); }  // of 10 bits
+
+// The ten stages of the rule's DFT_N in place, the input already in bit-reversed places; inverse: ti negated. Each
+// product and each sum rounded (no fused multiply-add), the full product in every stage. Ends behind a barrier.
+__device__ __forceinline__ void fmt_stages(float* s_re, float* s_im, const float* s_tr, const float* s_ti, bool inverse, int tid) {
+#pragma clang fp contract(off)
+  for (int s = 0; s < 10; ++s) {
+    const int h = 1 << s;
+#pragma unroll
+    for (int t = tid; t < FMT_HALF; t += PCM_THREADS) {
+      const int p = t & (h - 1), i = ((t >> s) << (s + 1)) + p, j = i + h;
+      const float wr = s_tr[p << (9 - s)], wi0 = s_ti[p << (9 - s)], wi = inverse ? -wi0 : wi0;
+      const float ur = s_re[i], ui = s_im[i], vr = s_re[j], vi = s_im[j];
+      const float a = vr * wr, b = vi * wi, c = vr * wi, d = vi * wr;
+      const float pr = a - b, pi = c + d;
+      s_re[i] = ur + pr;
+      s_im[i] = ui + pi;
+      s_re[j] = ur - pr;
+      s_im[j] = ui - pi;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(PCM_THREADS) void pcm_formant_kernel(PcmRows rows, int Fn, int Fd, const float* __restrict__ pcm,
+                                                                  int n_in, const float* __restrict__ tab, float* hist,
+                                                                  unsigned char* __restrict__ out, long long out_stride,
+                                                                  int group) {
+#pragma clang fp contract(off)
+  const PcmRow r = rows.r[blockIdx.y];
+  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
+  const int tid = threadIdx.x;
+  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
+  const SegInput<FMT_HIST> input{x, hist, r.t0, t1, r.hist_in};
+  if (blockIdx.x == 0 && r.hist_out >= 0)
+    for (int i = tid; i < FMT_HIST; i += PCM_THREADS) hist[r.hist_out + i] = input(t1 - FMT_HIST + i);
+
+  const int n_blocks = (r.n_out + FMT_H - 1) / FMT_H;  // hop blocks of this call (the last may be cut by a final call)
+  const int lb0 = blockIdx.x * group;                  // the group's first, counted from the call's first
+  if (lb0 >= n_blocks) return;
+  const int lb1 = min(lb0 + group, n_blocks);
+  const long long b_first = r.m0 / FMT_H;  // (m0 is a multiple of H: only a final call emits part of a block)
+
+  __shared__ float s_re[FMT_N], s_im[FMT_N], s_acc[FMT_N], s_w[FMT_N];
+  __shared__ float s_tr[FMT_HALF], s_ti[FMT_HALF], s_c[FMT_TAPS];
+  __shared__ float s_P[FMT_BINS], s_E[FMT_BINS], s_G[FMT_BINS];
+  for (int i = tid; i < FMT_N; i += PCM_THREADS) s_w[i] = tab[i];
+  if (tid < FMT_TAPS) s_c[tid] = tab[FMT_N + tid];
+  for (int i = tid; i < FMT_HALF; i += PCM_THREADS) {
+    s_tr[i] = tab[FMT_N + FMT_TAPS + i];
+    s_ti[i] = tab[FMT_N + FMT_TAPS + FMT_HALF + i];
+  }
+  __syncthreads();
+
+  const float eps = 1e-10f, g2_lo = 1.f / 256.f, g2_hi = 256.f, two_thirds = (float)(2.0 / 3.0);
+  float* __restrict__ o = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride);
+  for (int lj = lb0; lj < lb1 + 3; ++lj) {  // frame j = b_first + lj covers the call's hop blocks lj - 3 .. lj
+    const long long g0 = (b_first + lj - 3) * FMT_H;  // its first input
+    // 1. the windowed frame, to bit-reversed places
+#pragma unroll
+    for (int q = 0; q < FMT_PER; ++q) {
+      const int n = tid + q * PCM_THREADS, v = fmt_rev(n);
+      s_re[v] = s_w[n] * input(g0 + n);
+      s_im[v] = 0.f;
+    }
+    __syncthreads();
+    fmt_stages(s_re, s_im, s_tr, s_ti, false, tid);
+    // 2. the power of bins 0 .. N / 2
+    for (int k = tid; k < FMT_BINS; k += PCM_THREADS) {
+      const float a = s_re[k] * s_re[k], b = s_im[k] * s_im[k];
+      s_P[k] = a + b;
+    }
+    __syncthreads();
+    // 3, 4. the envelope: 25 taps over the symmetric extension, d ascending
+    for (int k = tid; k < FMT_BINS; k += PCM_THREADS) {
+      float acc = 0.f;
+#pragma unroll
+      for (int d = -FMT_K; d <= FMT_K; ++d) {
+        const int at = k + d, idx = at < 0 ? -at : at > FMT_HALF ? FMT_N - at : at;
+        const float prod = s_c[d + FMT_K] * s_P[idx];
+        acc = acc + prod;
+      }
+      s_E[k] = acc;
+    }
+    __syncthreads();
+    // 5, 6. the envelope at k Fn / Fd over the envelope at k: the gain
+    for (int k = tid; k < FMT_BINS; k += PCM_THREADS) {
+      const int kn = k * Fn, i = kn / Fd;
+      float es = s_E[FMT_HALF];
+      if (i < FMT_HALF) {
+        const float f = __fdiv_rn((float)(kn - i * Fd), (float)Fd);
+        const float e0 = s_E[i], de = s_E[i + 1] - e0, fd = f * de;
+        es = e0 + fd;
+      }
+      const float num = es + eps, den = s_E[k] + eps;
+      const float g2 = fminf(fmaxf(__fdiv_rn(num, den), g2_lo), g2_hi);
+      s_G[k] = sqrtf(g2);  // (the correctly rounded one: the Makefile compiles this file with IEEE fp32 / and sqrt)
+    }
+    __syncthreads();
+    // 7. Y = G X on 0 .. N / 2 and its Hermitian extension, through registers to bit-reversed places
+    float yr[FMT_PER], yi[FMT_PER];
+#pragma unroll
+    for (int q = 0; q < FMT_PER; ++q) {
+      const int k = tid + q * PCM_THREADS, kk = k <= FMT_HALF ? k : FMT_N - k;
+      const float g = s_G[kk];
+      yr[q] = g * s_re[kk];
+      const float im = g * s_im[kk];
+      yi[q] = k <= FMT_HALF ? im : -im;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < FMT_PER; ++q) {
+      const int v = fmt_rev(tid + q * PCM_THREADS);
+      s_re[v] = yr[q];
+      s_im[v] = yi[q];
+    }
+    __syncthreads();
+    fmt_stages(s_re, s_im, s_tr, s_ti, true, tid);
+    // 8. the windowed frame, quarter q onto hop block lj - 3 + q: the block's first frame (q = 3) sets, the others add
+#pragma unroll
+    for (int q = 0; q < FMT_PER; ++q) {
+      const int n = tid + q * PCM_THREADS, lb = lj - 3 + q;
+      if (lb < lb0 || lb >= lb1) continue;  // a block of another group
+      const float sc = 0.0009765625f * s_re[n];
+      const float v = s_w[n] * sc;
+      float* a = s_acc + ((lb & 3) * FMT_H + tid);
+      *a = q == 3 ? v : *a + v;
+    }
+    if (lj - 3 >= lb0) {  // block lj - 3 has its four frames
+      const int nl = (lj - 3) * FMT_H + tid;
+      if (nl < r.n_out) o[nl] = two_thirds * s_acc[((lj - 3) & 3) * FMT_H + tid];
+    }
+    __syncthreads();  // (the next frame overwrites s_re)
+  }
+}
+
 }  // namespace
+
+void pcm_launch_formant(const PcmRows& rows, int n_rows, int max_out, int Fn, int Fd, const float* pcm, int n_in,
+                        const float* tab, float* hist, float* out, long long out_stride, hipStream_t s) {
+  const int blocks = (max_out + FMT_H - 1) / FMT_H;
+  // the smallest group at which the launch has at most FMT_WGS workgroups (measured: DESIGN 4, "The formant: a
+  // short-time Fourier correction of the spectral envelope", "Which group")
+  int group = opts().fmt_group;
+  if (group == 0) {
+    const int per_row = std::max(1, FMT_WGS / n_rows);
+    group = std::min(std::max(1, (blocks + per_row - 1) / per_row), FMT_GROUP_MAX);
+  }
+  pcm_formant_kernel<<<dim3((unsigned)std::max(1, (blocks + group - 1) / group), (unsigned)n_rows), PCM_THREADS, 0, s>>>(
+      rows, Fn, Fd, pcm, n_in, tab, hist, (unsigned char*)out, out_stride, group);
+}
 
 void pcm_launch_flac(const FlacRows& rows, int n_rows, int max_frames, int bs, const int16_t* s16, int n_in,
                      long long in_stride, int16_t* hist, void* out, long long out_stride, hipStream_t s) {

@@ -471,20 +471,55 @@ class Engine:
                                           width * 4, cnt, _ptr(g), width * 4, self.stream_handle()))
         return out, list(cnt), g
 
+    def pcm_formant_plan(self, speed_pct: int, pitch_pct: int, formant_pct: int):
+        """(Fn, Fd) of a speed, a pitch and a formant as the library plans them (lvx_pcm_formant_plan)."""
+        Fn, Fd = ctypes.c_int(), ctypes.c_int()
+        _lib.check(self.lib.lvx_pcm_formant_plan(int(speed_pct), int(pitch_pct), int(formant_pct), ctypes.byref(Fn),
+                                                 ctypes.byref(Fd)))
+        return Fn.value, Fd.value
+
+    def pcm_formant_tables(self):
+        """(w float32 [1024], c float32 [25], tw float32 [1024]): the formant stage's window, smoothing taps and
+        twiddles as the library builds them (lvx_pcm_formant_tables)."""
+        w, c, tw = np.zeros(1024, dtype=np.float32), np.zeros(25, dtype=np.float32), np.zeros(1024, dtype=np.float32)
+        ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        _lib.check(self.lib.lvx_pcm_formant_tables(ptr(w), w.size, ptr(c), c.size, ptr(tw), tw.size))
+        return w, c, tw
+
+    def pcm_formant(self, pcm: Optional[torch.Tensor], slots, finals, Fn: int, Fd: int):
+        """The formant control's envelope correction alone (lvx_pcm_formant): rows of ``pcm`` (device float32 [B, n_in]
+        at 24 kHz; None or n_in 0: flush only) continue the formant segments of ``slots`` at the ratio Fn / Fd (the
+        envelope of the output at a frequency is that of the input at Fn / Fd times it); a true ``finals[b]`` emits the
+        held-back 768 .. 1023 samples too and ends row b's segment. Returns (out, counts): a device float32 tensor
+        [B, width] whose row b holds counts[b] samples. 1 / 1: the rows themselves. Asynchronous on the current stream;
+        a slot's calls must be issued in order on one stream."""
+        pcm, n_in, B, sl, fl, cnt, same = self._pcm_args(pcm, slots, finals)
+        Fn, Fd = int(Fn), int(Fd)
+        out, width = None, 0
+        if Fn == Fd == 1:
+            out = same
+        elif 1 <= Fn <= 40000 and 1 <= Fd <= 40000:
+            # (the call's inputs and the held-back <= 1023; rows on 16-byte boundaries)
+            width = (n_in + 1023 + 7) // 8 * 8
+            out = torch.empty(B, width, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.lvx_pcm_formant(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, Fn, Fd, _ptr(out),
+                                            width * 4, cnt, self.stream_handle()))
+        return out, list(cnt)
+
     def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt, ctx_frames=None):
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
-        ``audio.AudioFormat`` (its speed, pitch, volume, rate and encoding). Returns (out, counts): a device tensor
-        [B, width] of float32, int16 or (G.711) uint8 whose row b holds counts[b] samples. Five stages in this order, each only
-        where the format needs it, so that a format makes exactly the calls of the stages it uses: the dump join
-        (lvx_pcm_join, a format with ``join``: row b with ``ctx_frames[b]`` frames of context in front, None: none
-        anywhere), the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the plan's L / M
-        (lvx_pcm_ratio), the gain and limiter at volume_pct (lvx_pcm_level), the rate and the encoding
-        (lvx_pcm_convert). A "flac" format runs that last stage as s16le and a sixth behind it (lvx_pcm_flac): its rows are
-        uint8, whole slots of LVX_FLAC_SLOT bytes (a record and a subframe each; ``audio.FlacMux`` makes them frames), and
-        counts[b] is their bytes. Rows may leave a stage with different counts: they pass the next one grouped by count.
+        ``audio.AudioFormat`` (its speed, pitch, formant, volume, rate and encoding). Returns (out, counts): a device
+        tensor [B, width] of float32, int16 or (G.711) uint8 whose row b holds counts[b] samples. Six stages in this
+        order, each only where the format needs it, so that a format makes exactly the calls of the stages it uses: the
+        dump join (lvx_pcm_join, a format with ``join``: row b with ``ctx_frames[b]`` frames of context in front, None:
+        none anywhere), the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the plan's
+        L / M (lvx_pcm_ratio), the envelope correction by the plan's Fn / Fd (lvx_pcm_formant), the gain and limiter at
+        volume_pct (lvx_pcm_level), the rate and the encoding (lvx_pcm_convert). A "flac" format runs that last stage as
+        s16le and one more behind it (lvx_pcm_flac): its rows are uint8, whole slots of LVX_FLAC_SLOT bytes (a record
+        and a subframe each; ``audio.FlacMux`` makes them frames), and counts[b] is their bytes. Rows may leave a stage with different counts: they pass the next one grouped by count.
         Asynchronous on the current stream; a slot's calls must be issued in order on one stream."""
-        stretch_pct, (L, M), vol = fmt.stretch_pct, fmt.ratio, fmt.volume_pct
+        stretch_pct, (L, M), vol, (Fn, Fd) = fmt.stretch_pct, fmt.ratio, fmt.volume_pct, fmt.formant
         slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
         if not fmt.join and ctx_frames is not None and any(ctx_frames):
             raise ValueError("ctx_frames without a joined format")
@@ -496,6 +531,8 @@ class Engine:
             stages.append(lambda sub, sl, fl: self.pcm_stretch(sub, sl, fl, stretch_pct)[:2])
         if L != M:
             stages.append(lambda sub, sl, fl: self.pcm_ratio(sub, sl, fl, L, M))
+        if Fn != Fd:
+            stages.append(lambda sub, sl, fl: self.pcm_formant(sub, sl, fl, Fn, Fd))
         if vol != 100:
             stages.append(lambda sub, sl, fl: self.pcm_level(sub, sl, fl, vol)[:2])
         # The rate and the encoding come last. At 24 kHz f32le they have nothing to do and the output of the stage

@@ -403,10 +403,24 @@ def volume_pct_of(volume) -> int:
     return pct
 
 
+def formant_pct_of(formant) -> Optional[int]:
+    """A formant factor (a float in 0.5 .. 2.0, or None: the formants follow the pitch) as the integer percentage the
+    formant stage's plan takes (``audio.AudioFormat.formant_pct``); ValueError for anything else."""
+    if formant is None:
+        return None
+    if isinstance(formant, bool) or not isinstance(formant, (int, float)) or not math.isfinite(formant):
+        raise ValueError(f"formant must be a number in 0.5 .. 2.0, got {formant!r}")
+    pct = int(round(formant * 100))
+    if not 50 <= pct <= 200:
+        raise ValueError(f"formant must be in 0.5 .. 2.0, got {formant!r}")
+    return pct
+
+
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
                encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
                min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0,
-               join: bool = False, volume: float = 1.0, frame_ms: Optional[int] = None):
+               join: bool = False, volume: float = 1.0, frame_ms: Optional[int] = None,
+               formant: Optional[float] = None):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -434,7 +448,15 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     (a float in 0.0 .. 4.0; 1.0: as spoken; a bool, a non-number, a non-finite or an out-of-range value: 422) is the
     loudness: the PCM is multiplied by round(volume * 100) percent and peak-limited at -1 dBFS on the device
     (``audio.level_ref``), which holds back 10 ms of every sentence until its end; the response carries it in
-    ``X-Audio-Volume``. ``encoding`` also takes "flac" at any of the four rates: a native FLAC stream (``fLaC``, one
+    ``X-Audio-Volume``. ``formant`` (a float in 0.5 .. 2.0; null or absent: the formants follow the pitch, as a
+    resampling moves them, and no stage runs; a bool, a non-number, a non-finite or an out-of-range value: 422) is
+    where the voice's spectral envelope sits against the model's own: 1.0 with a pitch changes f0 and leaves the
+    timbre, 0.9 alone darkens the voice. The PCM's envelope is corrected on the device behind the resampling
+    (``audio.formant_ref``) by the ratio ``audio.formant_plan`` gives for round(formant * 100) percent, which holds
+    back 32 .. 43 ms of every sentence until more arrives or it ends; a speed / pitch / formant combination whose
+    correction falls outside 1/2 .. 2: 422 with the plan's message; the response carries the factor by which the
+    envelope moved in ``X-Audio-Formant``, four decimals: the named one, or the realised pitch ratio.
+    ``encoding`` also takes "flac" at any of the four rates: a native FLAC stream (``fLaC``, one
     STREAMINFO block, then frames of 40 ms) of the s16le samples, lossless, media type audio/flac; it is its own container
     ("wav" with it: 422) and its frames have no fixed size (``frame_ms`` with it: 422). ``encoding`` also takes "ulaw" and "alaw": 8-bit G.711, the s16le samples companded on the
     device (``audio.g711_encode``), at any of the four rates; their WAV header is the 58-byte form of a non-PCM tag.
@@ -456,7 +478,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     extra_defaults = {"top_p": top_p, "min_p": min_p, "repetition_penalty": repetition_penalty,
                       "repetition_window": repetition_window}
     default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join,
-                                volume_pct_of(volume))
+                                volume_pct_of(volume), formant_pct_of(formant))
     default_frame_ms = frame_ms_of(frame_ms)
     if default_frame_ms is not None and default_audio.encoding == "flac":
         raise ValueError("frame_ms with encoding 'flac': FLAC frames have no fixed byte size")
@@ -477,6 +499,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         pitch: Optional[float] = None
         join: Optional[StrictBool] = None
         volume: Optional[Union[StrictInt, StrictFloat]] = None  # (strict: true / false are not numbers here)
+        formant: Optional[Union[StrictInt, StrictFloat]] = None  # (null: the server's default)
         frame_ms: Any = None  # (checked by frame_ms_of: an integer of audio.FRAME_MS, no bool, no float)
 
     def audio_of(request):
@@ -488,7 +511,9 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                default_audio.speed_pct if request.speed is None else speed_pct_of(request.speed),
                                default_audio.pitch_pct if request.pitch is None else pitch_pct_of(request.pitch),
                                default_audio.join if request.join is None else request.join,
-                               default_audio.volume_pct if request.volume is None else volume_pct_of(request.volume))
+                               default_audio.volume_pct if request.volume is None else volume_pct_of(request.volume),
+                               default_audio.formant_pct if request.formant is None
+                               else formant_pct_of(request.formant))
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -549,6 +574,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                           "X-Audio-Pitch": f"{fmt.speed_pct / fmt.stretch_pct:.4f}",
                                           "X-Audio-Join": "1" if fmt.join else "0",
                                           "X-Audio-Volume": f"{fmt.volume_pct / 100:.2f}",
+                                          "X-Audio-Formant": f"{fmt.formant_moved:.4f}",
                                           "X-Audio-Frame-Ms": str(ms or 0)})
 
     @app.get("/health")
@@ -600,6 +626,9 @@ def arg_parser():
                     help="pitch factor of requests that name none (0.5 .. 2.0; 1.0: as spoken)")
     ap.add_argument("--volume", type=float, default=1.0,
                     help="volume factor of requests that name none (0.0 .. 4.0; 1.0: as spoken; peak-limited at -1 dBFS)")
+    ap.add_argument("--formant", type=float, default=None,
+                    help="formant factor of requests that name none (0.5 .. 2.0; 1.0: the model's own timbre at any "
+                         "pitch; default: none, the formants follow the pitch)")
     ap.add_argument("--join", action="store_true",
                     help="click-free dump joins for requests that do not name `join` (context frames and a crossfade)")
     return ap
@@ -610,7 +639,7 @@ def app_options(a) -> dict:
     return dict(temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate, encoding=a.encoding,
                 container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
                 repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch,
-                join=a.join, volume=a.volume, frame_ms=a.frame_ms)
+                join=a.join, volume=a.volume, frame_ms=a.frame_ms, formant=a.formant)
 
 
 def main(argv=None):

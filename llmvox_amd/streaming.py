@@ -527,8 +527,8 @@ class _PcmPass:
     """The PCM output-stage calls of one chunk's dumps (streams opened with ``audio``). A slot's calls
     must reach the engine in dump order, whatever order the codec groups are decoded in, and no call may
     name a slot twice: ``run()`` converts, in rounds, every dump that is the next one of its stream and
-    whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch, join, volume), and
-    leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
+    whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch, join, volume,
+    formant), and leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
 
     def __init__(self, sched, dumps, finals):
         self.sched, self.dumps, self.finals = sched, dumps, finals
@@ -561,7 +561,8 @@ class _PcmPass:
                     eng.pcm_reset(st.slot)
                     continue
                 buckets.setdefault((id(self.where[i][0]), st.audio.sample_rate, st.audio.encoding,
-                                    st.audio.speed_pct, st.audio.pitch_pct, st.audio.join, st.audio.volume_pct),
+                                    st.audio.speed_pct, st.audio.pitch_pct, st.audio.join, st.audio.volume_pct,
+                                    st.audio.formant_pct),
                                    []).append(i)
             if not buckets:
                 return calls
@@ -670,7 +671,7 @@ class FusedScheduler:
         """sampling: a ``sampling.Sampling`` (temperature > 0) makes the stream draw its tokens, every
         sentence from ``segment_seed(seed, index, sentence)``; None (or temperature 0): greedy, and the
         engine's ``set_sampling`` is never called.
-        audio: an ``audio.AudioFormat`` with another speed, pitch, volume, rate or encoding than f32le at 24 kHz as
+        audio: an ``audio.AudioFormat`` with another speed, pitch, formant, volume, rate or encoding than f32le at 24 kHz as
         spoken: every dump of the stream is converted on the device (``Engine.pcm_convert``), behind its codec call on the same
         stream, each sentence as a signal of its own, and the stream's items are those samples (float32,
         int16 or, G.711, uint8 arrays with ``to_bytes=False``). None (or 24 kHz f32le): today's items, and the engine's
