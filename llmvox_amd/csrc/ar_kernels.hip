@@ -119,8 +119,6 @@ __device__ __forceinline__ Best best_merge(Best a, Best c) {
   return r;
 }
 
-__device__ __forceinline__ int4 make_rowinfo(const ArState& st, int b, int s, int p, int j, int prev);
-
 // best_merge over the whole wave (exact: best_merge is commutative and associative), DPP within
 // rows then the four row results through SGPRs; wave-uniform result
 template <int CTRL>
@@ -174,6 +172,19 @@ __device__ __forceinline__ int plan_tok(const ArState& st, int b, int j) {
   return (j < st.plan_stride) ? min(max(st.text_plan[(size_t)b * st.plan_stride + j], 0), TEXT_VOCAB - 1) : -1;
 }
 
+// Per-row control record of the step in flight: {slot, pos, text id, prev token}. Built once per
+// lvx_ar_steps call (then advanced by the argmax kernel of every step), so the kernels of a step read
+// one 16-byte record instead of chasing slots -> pos / prev / rowstep -> text_plan.
+// text id -1 marks "past the end of the plan": reported by the step that would consume it.
+__device__ __forceinline__ int4 make_rowinfo(const ArState& st, int b, int s, int p, int j, int prev) {
+  if (s < 0) return make_int4(-1, 0, 0, 0);
+  if (p >= st.max_pos) {
+    atomicOr(st.err, 1);
+    p = st.max_pos - 1;
+  }
+  return make_int4(s, p, plan_tok(st, b, j), min(max(prev, 0), VOCAB - 1));
+}
+
 __device__ __forceinline__ void argmax_commit(const ArState& st, int b, int4 ri, Best r) {
   if (!st.rowstep) return;  // measurement probe: no plan bound, state is not advanced
   const int s = ri.x;
@@ -186,6 +197,60 @@ __device__ __forceinline__ void argmax_commit(const ArState& st, int b, int4 ri,
   st.pos[s] = ri.y + 1;
   st.rowstep[b] = j + 1;
   st.rowinfo[b] = make_rowinfo(st, b, s, ri.y + 1, j + 1, r.i);
+}
+
+// A row's 4,096 logits -> Best by a block of four waves. row_best_wave: thread tid's four float4 (lv(k): elements
+// (k * 256 + tid) * 4 .. of the row, already loaded or loaded by lv) reduced over its wave, lane 0 leaves the
+// wave's partial in sv / sv2 / si (4 LDS words each); after the caller's barrier, row_best_merge merges the
+// four partials (every lane of the calling wave: the same bits) and applies softmax_ties.
+template <typename LV>
+__device__ __forceinline__ void row_best_wave(LV&& lv, float* sv, float* sv2, int* si) {
+  const int tid = threadIdx.x;
+  Best bt{-INFINITY, -INFINITY, 0x7fffffff};
+#pragma unroll
+  for (int k = 0; k < VOCAB / 1024; ++k) {
+    const float4 v = lv(k);
+    const int i0 = (k * 256 + tid) * 4;
+    bt = best_merge(bt, Best{v.x, -INFINITY, i0});
+    bt = best_merge(bt, Best{v.y, -INFINITY, i0 + 1});
+    bt = best_merge(bt, Best{v.z, -INFINITY, i0 + 2});
+    bt = best_merge(bt, Best{v.w, -INFINITY, i0 + 3});
+  }
+  bt = best_wave(bt);
+  if ((tid & 63) == 0) { sv[tid >> 6] = bt.v; sv2[tid >> 6] = bt.v2; si[tid >> 6] = bt.i; }
+}
+__device__ __forceinline__ Best row_best_merge(const float* sv, const float* sv2, const int* si,
+                                               const float* row, int lane) {
+  Best r{sv[0], sv2[0], si[0]};
+#pragma unroll
+  for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
+  return softmax_ties(row, r, lane);
+}
+
+// The deferred selects (SEL_GRAN, SEL_EMBED, SEL_LN_GRAN, SEL_Q0_ROWS and the fused layer-0 attention) commit the
+// previous step's token at the head of the next step, from the old record ri = {slot, pos, text id, prev} and
+// rx = {plan step j, text id of step j + 1}. deferred_record: the row's new record (position clamped; the
+// commit raises the capacity error). deferred_commit: argmax_commit's state advance for token r of plan step j
+// at the new position p, by one thread per row. Where the record goes (rowinfo or the shadow arrays) stays
+// with the caller.
+// advance_rowstep: true where a call's last step is committed by ar_argmax_kernel (END_ARGMAX), whose
+// argmax_commit takes the step from rowstep: every deferred commit before it has to advance it. False for the
+// granule forms (SEL_GRAN: the GEMV's GIN_EMBED_SELECT prologue; ar_q0_gran_kernel, written out, likewise): their call ends with
+// ar_select_final_kernel (END_SELECT_FINAL), which sets rowstep from rowx before its argmax_commit, so the
+// steps carry the plan step in rowx alone.
+__device__ __forceinline__ int4 deferred_record(const ArState& st, int4 ri, int2 rx, Best r) {
+  return make_int4(ri.x, min(ri.y + 1, st.max_pos - 1), rx.y, min(max(r.i, 0), VOCAB - 1));
+}
+__device__ __forceinline__ void deferred_commit(const ArState& st, int b, int slot, int p, int j, Best r,
+                                                bool advance_rowstep) {
+  if (p >= st.max_pos) atomicOr(st.err, 1);
+  if (j < st.plan_stride) {
+    st.tok_plan[(size_t)b * st.plan_stride + j] = r.i;
+    if (st.margin_plan) st.margin_plan[(size_t)b * st.plan_stride + j] = r.v - r.v2;
+  }
+  st.prev[slot] = r.i;
+  st.pos[slot] = p;
+  if (advance_rowstep) st.rowstep[b] = j + 1;
 }
 
 typedef __attribute__((address_space(1))) unsigned long long gu64;
@@ -597,25 +662,17 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
       wr[r][it] = WReg<TW>::load(W + (size_t)min(n, a.N - 1) * K + kp * KC + it * 256 + lane * 4);
   }
   if constexpr (IN == GIN_EMBED_SELECT) {
-    // commit the previous step's greedy select (argmax_commit's state advance; block 0 writes
+    // commit the previous step's greedy select (deferred_commit; block 0 writes
     // the shadow records, attention layer 0 copies them back) and build this step's record. The
     // reduction and the record select run unconditionally so that the granule loads stay in the
     // prologue (used only under a branch, the compiler sinks them into it: one more round trip).
     const Best r = softmax_ties(a.st.logits + (size_t)min(wave, a.B - 1) * VOCAB, lmg_reduce(lmg), lane);
     const int s = ripre.x, j = rxp.x, p = ripre.y + 1;
     const bool take = selpend && s >= 0;
-    const int4 rn = take ? make_int4(s, min(p, a.st.max_pos - 1), rxp.y, min(max(r.i, 0), VOCAB - 1)) : ripre;
+    const int4 rn = take ? deferred_record(a.st, ripre, rxp, r) : ripre;
     if (prefetched && blockIdx.x == 0 && lane == 0) {
       const int b = wave;
-      if (take) {
-        if (p >= a.st.max_pos) atomicOr(a.st.err, 1);
-        if (j < a.st.plan_stride) {
-          a.st.tok_plan[(size_t)b * a.st.plan_stride + j] = r.i;
-          if (a.st.margin_plan) a.st.margin_plan[(size_t)b * a.st.plan_stride + j] = r.v - r.v2;
-        }
-        a.st.prev[s] = r.i;
-        a.st.pos[s] = p;
-      }
+      if (take) deferred_commit(a.st, b, s, p, j, r, false);
       // the next text id is looked up by attention layer 0's copier (a dependent load here would
       // hold this block until its weight loads landed: vmcnt retires in order)
       a.st.rowx_n[b] = make_int2(take ? j + 1 : j, 0);
@@ -772,7 +829,8 @@ __device__ __forceinline__ void gemv_store(const GemvArgs& a, int n, int b, floa
   }
 }
 
-__device__ __forceinline__ void wave_ln_regs(float4 (&v)[3], const float4 (&g)[3]) {
+// {mean, rstd} of one 768-row held as 3 float4 per lane (one wave): the LayerNorm's statistics, eps 1e-5
+__device__ __forceinline__ float2 wave_ln_stats(const float4 (&v)[3]) {
   float s = 0.f;
 #pragma unroll
   for (int j = 0; j < 3; ++j) s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
@@ -780,13 +838,80 @@ __device__ __forceinline__ void wave_ln_regs(float4 (&v)[3], const float4 (&g)[3
   float q = 0.f;
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
-    v[j].x -= mean; v[j].y -= mean; v[j].z -= mean; v[j].w -= mean;
-    q += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
+    const float4 d = make_float4(v[j].x - mean, v[j].y - mean, v[j].z - mean, v[j].w - mean);
+    q += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
   }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-5f);
+  return make_float2(mean, 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-5f));
+}
+__device__ __forceinline__ void wave_ln_regs(float4 (&v)[3], const float4 (&g)[3]) {
+  const float2 ms = wave_ln_stats(v);
 #pragma unroll
   for (int j = 0; j < 3; ++j)
-    v[j] = make_float4(v[j].x * rstd * g[j].x, v[j].y * rstd * g[j].y, v[j].z * rstd * g[j].z, v[j].w * rstd * g[j].w);
+    v[j] = make_float4((v[j].x - ms.x) * ms.y * g[j].x, (v[j].y - ms.x) * ms.y * g[j].y, (v[j].z - ms.x) * ms.y * g[j].z,
+                       (v[j].w - ms.x) * ms.y * g[j].w);
+}
+// four elements of a bf16 operand row
+__device__ __forceinline__ uint2 pack4_bf16(float4 v) {
+  return make_uint2((uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16),
+                    (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16));
+}
+
+// x row of the embedding (a2-a4) for control record ri, lane layout k = j * 256 + lane * 4:
+// normalize(cat(text_table[id], codebook[prev] | 0 at position 0), eps 1e-8) + wpe[pos]
+__device__ __forceinline__ void embed_row(const GemvArgs& a, int4 ri, int lane, float4 (&v)[3], float* rden = nullptr) {
+  if (ri.x < 0) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return;
+  }
+  const int p = ri.y, prev = ri.w;
+  const int tok = ri.z < 0 ? 384 : ri.z;
+  // every load issued before any branch or use (the error flag's atomic and the position-0 zeros
+  // came between them: one load went out a round trip late); prev is a valid codebook row
+  float4 pe[3];
+  const float* wr_ = a.wpe + (size_t)p * D;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) pe[j] = *reinterpret_cast<const float4*>(wr_ + j * 256 + lane * 4);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int k = j * 256 + lane * 4;
+    v[j] = j == 0 ? *reinterpret_cast<const float4*>(a.text_table + (size_t)tok * TEXT_DIM + k)
+                  : *reinterpret_cast<const float4*>(a.codebook + (size_t)prev * SPEECH_DIM + (k - TEXT_DIM));
+  }
+  if (ri.z < 0 && lane == 0) atomicOr(a.st.err, 2);
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    if (j > 0 && p == 0) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    ss += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
+  }
+  const float den = fmaxf(sqrtf(wave_sum(ss)), 1e-8f);
+  if (rden) *rden = 1.0f / den;
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    v[j] = make_float4(v[j].x / den + pe[j].x, v[j].y / den + pe[j].y, v[j].z / den + pe[j].z, v[j].w / den + pe[j].w);
+}
+
+// One wave: {1 / den, mean, rstd} of row b's embedding row for record rn, the statistics that layer 0's
+// c_attn from the q0 tables needs (wave_ln_stats: the LayerNorm's own); store_x: the row goes to st.x (one
+// block per row). Shared by ar_q0_rows_kernel and the fused layer-0 attention (ar_q0_gran_kernel mirrors it).
+__device__ __forceinline__ float4 q0_row_stats(const GemvArgs& a, int4 rn, int b, int lane, bool store_x) {
+  float4 v[3];
+  float rden = 0.f;
+  embed_row(a, rn, lane, v, &rden);
+  if (store_x) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = v[j];
+  }
+  const float2 ms = wave_ln_stats(v);
+  return make_float4(rden, ms.x, ms.y, 0.f);
+}
+// Element n of layer 0's c_attn output from the q0 tables: LayerNorm(x) W^T with x = (text | cz code) / den + pos
+// folded into table rows (tt = Tt[text id][n], tc = Tc[prev][n], tp = Tp[pos][n], g = G[n]); ss = q0_row_stats.
+// Position 0: the codebook half of the input is zero.
+__device__ __forceinline__ float q0_out(float4 ss, int pos, float tt, float tc, float tp, float g) {
+  const float cz = pos == 0 ? 0.f : 1.f;
+  return ss.z * (((tt + cz * tc) * ss.x + tp) - ss.y * g);
 }
 
 // ---------------------------------------------------------------------------------
@@ -966,19 +1091,6 @@ __global__ __launch_bounds__(256) void ar_mlp_fused_kernel(GemvArgs a, const bf1
       atomicAdd(y + (size_t)bb * YCOPIES * D + tid + 256 * jj, yfx_of(t, a.st.err));  // no-return int64 add
     }
   }
-}
-
-// Per-row control record of the step in flight: {slot, pos, text id, prev token}. Built once per
-// lvx_ar_steps call (then advanced by the argmax kernel of every step), so the kernels of a step read
-// one 16-byte record instead of chasing slots -> pos / prev / rowstep -> text_plan.
-// text id -1 marks "past the end of the plan": reported by the step that would consume it.
-__device__ __forceinline__ int4 make_rowinfo(const ArState& st, int b, int s, int p, int j, int prev) {
-  if (s < 0) return make_int4(-1, 0, 0, 0);
-  if (p >= st.max_pos) {
-    atomicOr(st.err, 1);
-    p = st.max_pos - 1;
-  }
-  return make_int4(s, p, plan_tok(st, b, j), min(max(prev, 0), VOCAB - 1));
 }
 
 __global__ void ar_rowinfo_init_kernel(ArState st, int B) {
@@ -1163,20 +1275,18 @@ __device__ __forceinline__ float slot_fold_wave(float m, float& l, float (&o)[24
 // attention that also runs ar_q0_rows_kernel's work for its own (row, head), so the step has no launch of
 // that kernel. The block issues the old control record, the row's logits and its head's 288 columns of
 // G / Tt[t] / Tp[p] at entry, the first KV tiles of the history (keys below the new one: they do not
-// depend on the select) as soon as the record gives (slot, position), then runs the select (the same
-// four-wave reduce, softmax_ties and clamp), loads Tc[c], wave 0 builds the embedding row's statistics
-// (q0_row_stats) and threads 0-287 form q / k / v with ar_q0_rows_kernel's expression. q goes through LDS,
-// k / v are rounded as store_kv rounds them, appended to the cache and kept in LDS: after the history's
+// depend on the select) as soon as the record gives (slot, position), then runs the select (row_best_wave /
+// row_best_merge, deferred_record), loads Tc[c], wave 0 builds the embedding row's statistics
+// (q0_row_stats) and threads 0-287 form q / k / v (q0_out). q goes through LDS,
+// k / v are rounded as store_kv rounds them, appended to the cache and kept in LDS (newkey_put): after the history's
 // tile loop the lane quad that owns key t - 1 takes them from there (the last key its slot sees, as in the
 // two-launch form, so the slot states have the same bits; the block's own store is not read back). The
-// head-0 block of a row commits the select (ar_q0_rows_kernel's cx == 0 stores, records into the shadow
+// head-0 block of a row commits the select (deferred_commit, as ar_q0_rows_kernel's cx == 0 block; records into the shadow
 // arrays since the row's other blocks read the old ones in this launch); layer 1's ar_rows_kernel copies
 // the records back (RMODE_LN_Y_COPY; in a la_fused step, which has no such launch, layer 1's fused attention does:
 // selcopy). Ordering inside the block is by LDS barriers alone.
 // LA (ArStepPlan::la_fused, layers >= 1 of such a step): the block runs its row's LayerNorm and its head's c_attn
 // rows instead of the tables; described at ar_attn_la_kernel.
-__device__ __forceinline__ float4 q0_row_stats(const GemvArgs& a, int4 rn, int b, int lane, bool store_x);
-__device__ __forceinline__ uint2 pack4_bf16(float4 v);
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // plan_tok(st, b, jn + 1) from the plan element loaded at min(jn + 1, plan_stride - 1) (384 when no plan is bound)
@@ -1191,7 +1301,7 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-template <typename TKV, int DEPTH, int NW, bool QKV, bool L0, bool LA = false, int RT = 1>
+template <typename TKV, int NW, bool QKV, bool L0, bool LA = false, int RT = 1>
 __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns_max, int direct, int selcopy,
                                              const GemvArgs* a0) {
   // NW waves: a tile is NW x 16 keys (4 lanes per key); NW = 8 doubles the bytes in flight per
@@ -1243,7 +1353,8 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
       zn[h] = (e / HD) * D + head * HD + e % HD;
       zg[h] = a0->q0_g[zn[h]];
     }
-    // this step's (text id, position) as the commit sets them (from the records, not the select)
+    // this step's (text id, position) as the commit sets them (from the records, not the select; as in
+    // ar_q0_rows_kernel and ar_q0_gran_kernel: one shared definition moved the registers of each)
     tk = pend && rold.x >= 0;
     const int p1 = min(max(tk ? rold.y + 1 : rold.y, 0), st.max_pos - 1);
     const int t1 = tk ? rx.y : rold.z;
@@ -1364,13 +1475,14 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   float m = -INFINITY, l = 0.f, o[24];
 #pragma unroll
   for (int i = 0; i < 24; ++i) o[i] = 0.f;
-  // DEPTH tiles in flight: the register set of tile kb is refilled with tile kb + DEPTH * 64 right
-  // after it is consumed, while the other sets are landing (DEPTH * 24 KB per block in flight: a
-  // block streams at bytes-in-flight / latency, so the depth sets the per-CU rate). Loads are
+  // Two tiles in flight: the register set of tile kb is refilled with tile kb + 2 TK right
+  // after it is consumed, while the other set is landing (2 x 24 KB per block in flight: a
+  // block streams at bytes-in-flight / latency, so the depth sets the per-CU rate; deeper pipelines
+  // lost: notes at launch_attn). Loads are
   // unconditional (key clamped to the last valid one, invalid lanes masked after) so that no load
   // sits under a branch: the compiler's vmcnt for "this set has landed" then leaves the other sets
   // in flight instead of draining every outstanding load.
-  KvPiece<TKV> kpr[DEPTH][3], vpr[DEPTH][3];
+  KvPiece<TKV> kpr[2][3], vpr[2][3];
   const int klast = ((k1 - 1) / ATK) * ATK;  // SLOT: start of the last tile (a tile past it is clamped to it)
   auto issue = [&](int kb, KvPiece<TKV>(&kp)[3], KvPiece<TKV>(&vp)[3]) {
     if constexpr (SLOT) {  // keys past k1 in the last chunk: allocated rows, masked by `valid`
@@ -1398,6 +1510,24 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
     for (int j = 0; j < 12; ++j) o2[j] = f32x2_t{0.f, 0.f};
   }
   QSplit qsp;
+  auto newkey_put = [&](int e, float v, bool append) {
+    if (e < HD) {
+      qs_s[e] = v;
+    } else if (e < 3 * HD && append) {
+      const int which = e / HD - 1, d = e % HD;
+      TKV hv;
+      if constexpr (sizeof(TKV) == 4) hv = v;
+      else if constexpr (sizeof(TKV) == 2) hv = f32_to_bf16(v);
+      else hv = f32_to_fp8(v);
+      kvh_s[which][d] = hv;
+      reinterpret_cast<TKV*>(which ? st.vc : st.kc)[base + krow(ri.y) + d] = hv;
+    }
+  };
+  auto q_from_lds = [&]() {
+    lds_barrier();
+#pragma unroll
+    for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
+  };
   auto tile = [&](int kb, const KvPiece<TKV>(&kp)[3], const KvPiece<TKV>(&vp)[3]) {
     const bool valid = kb + kq < k1;
     if constexpr (BF) {
@@ -1435,7 +1565,7 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
     sc = quad_sum(sc);
     if (!valid) sc = -INFINITY;
     const float mn = fmaxf(m, wave_max(sc));  // -inf while this wave has seen no key: alpha = p = 0
-    if (DEPTH == 2 && mn == -INFINITY) return;  // (wave-uniform) skip the no-op update
+    if (mn == -INFINITY) return;                // (wave-uniform) skip the no-op update
     const float alpha = (m == -INFINITY) ? 0.f : expf(m - mn);
     const float p = valid ? expf(sc - mn) : 0.f;
     l = l * alpha + wave_sum(part == 0 ? p : 0.f);
@@ -1444,7 +1574,7 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
     m = mn;
   };
 #pragma unroll
-  for (int d = 0; d < DEPTH; ++d) issue(k0 + d * TK, kpr[d], vpr[d]);
+  for (int d = 0; d < 2; ++d) issue(k0 + d * TK, kpr[d], vpr[d]);
   if constexpr (QKV) {
     // the partials were issued before the tiles (vmcnt retires in issue order: this waits for them
     // alone); raw barrier after the LDS writes, the tiles stay in flight
@@ -1454,27 +1584,13 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
       float v = 0.f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) v += pq[h][k];
-      if (e < HD) {
-        qs_s[e] = v;
-      } else if (e < 3 * HD && k1 == t) {  // K / V of the new key (the last split): appended, kept in LDS
-        const int which = e / HD - 1, d = e % HD;
-        TKV hv;  // the value the one-launch c_attn stores (store_kv)
-        if constexpr (sizeof(TKV) == 4) hv = v;
-        else if constexpr (sizeof(TKV) == 2) hv = f32_to_bf16(v);
-        else hv = f32_to_fp8(v);
-        kvh_s[which][d] = hv;
-        reinterpret_cast<TKV*>(which ? st.vc : st.kc)[base + krow(ri.y) + d] = hv;
-      }
+      newkey_put(e, v, k1 == t);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
+    q_from_lds();
   }
   if constexpr (LA) {
     // the history's first tiles are in flight behind the row and the first weight tiles. ar_rows_kernel<RMODE_LN_Y>'s
-    // LayerNorm of x + the pending copies (same fold, reduction and rounding; every wave, its own LDS copy of
+    // LayerNorm of x + the pending copies by the same functions (xrow_sum, wave_ln_regs, pack4_bf16; every wave, its own LDS copy of
     // the bf16 row), then this head's 18 column tiles of c_attn as ar_mfma2_kernel<768, 2, M2OUT_QKV> computes
     // them: wave w owns k in [192 w, 192 w + 192), six k-steps in order, the batch operand the one row
     // replicated over the MFMA's 16 columns (an output element depends on its weight row and its batch column
@@ -1527,47 +1643,23 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) v += red_s[w][e];
-        if (e < HD) {
-          qs_s[e] = v;
-        } else {  // K / V of the new key: appended at (slot, position), kept in LDS
-          const int which = e / HD - 1, d = e % HD;
-          TKV hv;  // the value store_kv stores
-          if constexpr (sizeof(TKV) == 2) hv = f32_to_bf16(v);
-          else hv = f32_to_fp8(v);
-          kvh_s[which][d] = hv;
-          reinterpret_cast<TKV*>(which ? st.vc : st.kc)[base + krow(ri.y) + d] = hv;
-        }
+        newkey_put(e, v, true);
       }
     }
-    lds_barrier();
-#pragma unroll
-    for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
+    q_from_lds();
     TS_MARK(1);
   }
   if constexpr (L0) {
-    // the history's first tiles are in flight; the select chain of ar_q0_rows_kernel, same code and order
+    // the history's first tiles are in flight; ar_q0_rows_kernel's select chain from the shared select pieces
     const GemvArgs& a = *a0;
-    Best bt{-INFINITY, -INFINITY, 0x7fffffff};
-#pragma unroll
-    for (int k = 0; k < VOCAB / 1024; ++k) {
-      const int i0 = (k * 256 + tid) * 4;
-      bt = best_merge(bt, Best{lgv[k].x, -INFINITY, i0});
-      bt = best_merge(bt, Best{lgv[k].y, -INFINITY, i0 + 1});
-      bt = best_merge(bt, Best{lgv[k].z, -INFINITY, i0 + 2});
-      bt = best_merge(bt, Best{lgv[k].w, -INFINITY, i0 + 3});
-    }
-    bt = best_wave(bt);
-    if (lane == 0) { sv_s[wave] = bt.v; sv2_s[wave] = bt.v2; si_s[wave] = bt.i; }
+    row_best_wave([&](int k) { return lgv[k]; }, sv_s, sv2_s, si_s);
     lds_barrier();
     int4 rn = rold;
     if (tk) {  // (block-uniform) every wave merges the four partials; the row's head-0 block commits
-      Best r{sv_s[0], sv2_s[0], si_s[0]};
-#pragma unroll
-      for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv_s[w], sv2_s[w], si_s[w]});
-      r = softmax_ties(st.logits + (size_t)b * VOCAB, r, lane);
+      const Best r = row_best_merge(sv_s, sv2_s, si_s, st.logits + (size_t)b * VOCAB, lane);
       const int sl = rold.x, p = rold.y + 1, j = rx.x;
       rn = make_int4(sl, min(p, st.max_pos - 1), rx.y, min(max(r.i, 0), VOCAB - 1));
-      if (head == 0 && tid == 0) {  // argmax_commit, with the records into the shadow arrays
+      if (head == 0 && tid == 0) {  // written out, mirrors deferred_record / deferred_commit (advance_rowstep true)
         if (p >= st.max_pos) atomicOr(st.err, 1);
         if (j < st.plan_stride) {
           st.tok_plan[(size_t)b * st.plan_stride + j] = r.i;
@@ -1591,39 +1683,22 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
     }
     lds_barrier();
     const float4 ss = sst_s;
-    const float cz = rn.y == 0 ? 0.f : 1.f;  // position 0: the codebook half of the input is zero
 #pragma unroll
     for (int h = 0; h < QH; ++h) {
       const int e = tid + NW * 64 * h;
-      const float v = ss.z * (((zt[h] + cz * zc[h]) * ss.x + zp[h]) - ss.y * zg[h]);
-      if (e < HD) {
-        qs_s[e] = v;
-      } else if (e < 3 * HD) {  // K / V of the new key: appended at (slot, position), kept in LDS
-        const int which = e / HD - 1, d = e % HD;
-        TKV hv;  // the value store_kv stores
-        if constexpr (sizeof(TKV) == 2) hv = f32_to_bf16(v);
-        else hv = f32_to_fp8(v);
-        kvh_s[which][d] = hv;
-        reinterpret_cast<TKV*>(which ? st.vc : st.kc)[base + krow(ri.y) + d] = hv;
-      }
+      const float v = q0_out(ss, rn.y, zt[h], zc[h], zp[h], zg[h]);
+      newkey_put(e, v, true);
     }
-    lds_barrier();
-#pragma unroll
-    for (int i = 0; i < 24; ++i) q[i] = qs_s[part * 24 + i] * 0.10206207261596575f;
+    q_from_lds();
     TS_MARK(1);
   }
   if constexpr (BF) qsplit_make(q, qsp);
-  // DEPTH 2 (few tiles per block, the B <= 2 step): leave after the last valid tile. DEPTH >= 4
-  // (long splits, batched steps): whole groups of DEPTH tiles with no exit inside a group (a tile
-  // past k1 is all-invalid: alpha = 1, p = 0), which keeps the compiler from draining every
-  // outstanding load at the group boundary
-  for (int kb = k0; kb < k1; kb += DEPTH * TK) {
+  for (int kb = k0; kb < k1; kb += 2 * TK) {
 #pragma unroll
-    for (int d = 0; d < DEPTH; ++d) {
-      if (DEPTH == 2 && d > 0 && kb + d * TK >= k1) break;
+    for (int d = 0; d < 2; ++d) {
+      if (d > 0 && kb + d * TK >= k1) break;  // leave after the last valid tile
       tile(kb + d * TK, kpr[d], vpr[d]);
-      issue(kb + (d + DEPTH) * TK, kpr[d], vpr[d]);
-      if (DEPTH > 2) __builtin_amdgcn_sched_barrier(0);  // keep the refill right behind its tile
+      issue(kb + (d + 2) * TK, kpr[d], vpr[d]);
     }
   }
   if constexpr (HIST) {
@@ -1703,16 +1778,16 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   }
 }
 
-template <typename TKV, int DEPTH, int NW, bool QKV = false>
+template <typename TKV, int NW, bool QKV = false>
 __global__ __launch_bounds__(NW * 64) void ar_attn_v2_kernel(ArState st, int layer, int ns_max, int direct,
                                                          int selcopy) {
-  attn_v2_body<TKV, DEPTH, NW, QKV, false>(st, layer, ns_max, direct, selcopy, nullptr);
+  attn_v2_body<TKV, NW, QKV, false>(st, layer, ns_max, direct, selcopy, nullptr);
 }
 
 // the fused layer-0 form (L0 above): grid (1, 8 heads, B), the launch in ar_q0_rows_kernel's place
 template <typename TKV>
 __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArgs a, int direct) {
-  attn_v2_body<TKV, 2, 4, false, true>(a.st, 0, 1, direct, 0, &a);
+  attn_v2_body<TKV, 4, false, true>(a.st, 0, 1, direct, 0, &a);
 }
 
 // the fused layers form (LA above; ArStepPlan::la_fused): layers >= 1 of a step whose layer 0 is the fused
@@ -1730,7 +1805,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArg
 template <typename TKV>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void ar_attn_la_kernel(GemvArgs a, int direct,
                                                                                                     int selcopy) {
-  attn_v2_body<TKV, 2, 4, false, false, true, LVX_LA_RT>(a.st, a.layer, 1, direct, selcopy, &a);
+  attn_v2_body<TKV, 4, false, false, true, LVX_LA_RT>(a.st, a.layer, 1, direct, selcopy, &a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1748,23 +1823,10 @@ template <bool HIST = false>
 __device__ __forceinline__ void argmax_row(const ArState& st, int b, int4 ri, float* sv, float* sv2, int* si) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float4* lg = reinterpret_cast<const float4*>(st.logits + (size_t)b * VOCAB);
-  Best bt{-INFINITY, -INFINITY, 0x7fffffff};
-#pragma unroll
-  for (int j = 0; j < VOCAB / 1024; ++j) {
-    const float4 v = lg[j * 256 + tid];
-    const int i0 = (j * 256 + tid) * 4;
-    bt = best_merge(bt, Best{v.x, -INFINITY, i0});
-    bt = best_merge(bt, Best{v.y, -INFINITY, i0 + 1});
-    bt = best_merge(bt, Best{v.z, -INFINITY, i0 + 2});
-    bt = best_merge(bt, Best{v.w, -INFINITY, i0 + 3});
-  }
-  bt = best_wave(bt);
-  if (lane == 0) { sv[wave] = bt.v; sv2[wave] = bt.v2; si[wave] = bt.i; }
+  row_best_wave([&](int k) { return lg[k * 256 + tid]; }, sv, sv2, si);
   __syncthreads();
   if (wave == 0) {
-    Best r{sv[0], sv2[0], si[0]};
-    for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
-    r = softmax_ties(st.logits + (size_t)b * VOCAB, r, lane);
+    const Best r = row_best_merge(sv, sv2, si, st.logits + (size_t)b * VOCAB, lane);
     if (lane == 0) {
       argmax_commit(st, b, ri, r);
       if constexpr (HIST) hist_store(st, ri.x, ri.y, r.i);
@@ -2095,11 +2157,6 @@ static void launch_gemv(const GemvArgs& a, hipStream_t s) {
   }
 }
 
-__device__ __forceinline__ uint2 pack4_bf16(float4 v) {
-  return make_uint2((uint32_t)f32_to_bf16(v.x) | ((uint32_t)f32_to_bf16(v.y) << 16),
-                    (uint32_t)f32_to_bf16(v.z) | ((uint32_t)f32_to_bf16(v.w) << 16));
-}
-
 #ifndef LVX_YCS
 #define LVX_YCS 2
 #endif
@@ -2117,68 +2174,6 @@ constexpr int YCS = LVX_YCS;
 // over its waves (K/192 waves: 4 for K=768, 16 for K=3072); every lane issues all of its
 // 16-byte fragment loads up front (one memory latency), partial tiles combine through LDS.
 // ---------------------------------------------------------------------------------
-// x row of the embedding (a2-a4) for control record ri, lane layout k = j * 256 + lane * 4:
-// normalize(cat(text_table[id], codebook[prev] | 0 at position 0), eps 1e-8) + wpe[pos]
-__device__ __forceinline__ void embed_row(const GemvArgs& a, int4 ri, int lane, float4 (&v)[3], float* rden = nullptr) {
-  if (ri.x < 0) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    return;
-  }
-  const int p = ri.y, prev = ri.w;
-  const int tok = ri.z < 0 ? 384 : ri.z;
-  // every load issued before any branch or use (the error flag's atomic and the position-0 zeros
-  // came between them: one load went out a round trip late); prev is a valid codebook row
-  float4 pe[3];
-  const float* wr_ = a.wpe + (size_t)p * D;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) pe[j] = *reinterpret_cast<const float4*>(wr_ + j * 256 + lane * 4);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int k = j * 256 + lane * 4;
-    v[j] = j == 0 ? *reinterpret_cast<const float4*>(a.text_table + (size_t)tok * TEXT_DIM + k)
-                  : *reinterpret_cast<const float4*>(a.codebook + (size_t)prev * SPEECH_DIM + (k - TEXT_DIM));
-  }
-  if (ri.z < 0 && lane == 0) atomicOr(a.st.err, 2);
-  float ss = 0.f;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    if (j > 0 && p == 0) v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-    ss += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);
-  }
-  const float den = fmaxf(sqrtf(wave_sum(ss)), 1e-8f);
-  if (rden) *rden = 1.0f / den;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    v[j] = make_float4(v[j].x / den + pe[j].x, v[j].y / den + pe[j].y, v[j].z / den + pe[j].z, v[j].w / den + pe[j].w);
-}
-
-// One wave: {1 / den, mean, rstd} of row b's embedding row for record rn, the statistics that layer 0's
-// c_attn from the q0 tables needs (mean, rstd as wave_ln_regs computes them); store_x: the row goes to
-// st.x (one block per row). Shared by ar_q0_rows_kernel and the fused layer-0 attention: one reduction order.
-__device__ __forceinline__ float4 q0_row_stats(const GemvArgs& a, int4 rn, int b, int lane, bool store_x) {
-  float4 v[3];
-  float rden = 0.f;
-  embed_row(a, rn, lane, v, &rden);
-  if (store_x) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = v[j];
-  }
-  float sm = 0.f;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) sm += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-  const float mean = wave_sum(sm) * (1.0f / D);
-  float qs = 0.f;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const float4 d = make_float4(v[j].x - mean, v[j].y - mean, v[j].z - mean, v[j].w - mean);
-    qs += (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(qs) * (1.0f / D) + 1e-5f);
-  return make_float4(rden, mean, rstd, 0.f);
-}
-
-
 // MODE: RMODE_* (ar_plan.h). The fp32 output rows of the _F32 modes go to st.h ([B][768]; the batched
 // fp32 parity mode's c_attn / lm_head operand, ar_qkv_ksplit_f32_kernel / ar_f32b_kernel FIN_LN_ROWS:
 // h is free between mlp c_proj and the next c_fc)
@@ -2271,37 +2266,16 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_embed_select_kernel(Ge
   float4 lv[VOCAB / 1024];
 #pragma unroll
   for (int k = 0; k < VOCAB / 1024; ++k) lv[k] = lg[k * 256 + tid];
-  Best bt{-INFINITY, -INFINITY, 0x7fffffff};
-#pragma unroll
-  for (int k = 0; k < VOCAB / 1024; ++k) {
-    const int i0 = (k * 256 + tid) * 4;
-    bt = best_merge(bt, Best{lv[k].x, -INFINITY, i0});
-    bt = best_merge(bt, Best{lv[k].y, -INFINITY, i0 + 1});
-    bt = best_merge(bt, Best{lv[k].z, -INFINITY, i0 + 2});
-    bt = best_merge(bt, Best{lv[k].w, -INFINITY, i0 + 3});
-  }
-  bt = best_wave(bt);
+  row_best_wave([&](int k) { return lv[k]; }, sv, sv2, si);
   TS_MARK(1);
-  if (lane == 0) { sv[wave] = bt.v; sv2[wave] = bt.v2; si[wave] = bt.i; }
   __syncthreads();
   if (wave != 0) return;
   const bool take = pend && ri.x >= 0;
   if (take) {
-    Best r{sv[0], sv2[0], si[0]};
-#pragma unroll
-    for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
-    r = softmax_ties(a.st.logits + (size_t)b * VOCAB, r, lane);
-    const int s = ri.x, p = ri.y + 1, j = rx.x;
-    const int4 rn = make_int4(s, min(p, a.st.max_pos - 1), rx.y, min(max(r.i, 0), VOCAB - 1));
-    if (lane == 0) {  // argmax_commit
-      if (p >= a.st.max_pos) atomicOr(a.st.err, 1);
-      if (j < a.st.plan_stride) {
-        a.st.tok_plan[(size_t)b * a.st.plan_stride + j] = r.i;
-        if (a.st.margin_plan) a.st.margin_plan[(size_t)b * a.st.plan_stride + j] = r.v - r.v2;
-      }
-      a.st.prev[s] = r.i;
-      a.st.pos[s] = p;
-      a.st.rowstep[b] = j + 1;
+    const Best r = row_best_merge(sv, sv2, si, a.st.logits + (size_t)b * VOCAB, lane);
+    const int4 rn = deferred_record(a.st, ri, rx, r);
+    if (lane == 0) {  // (one block per row: the record goes straight to rowinfo)
+      deferred_commit(a.st, b, ri.x, ri.y + 1, rx.x, r, true);
       a.st.rowinfo[b] = rn;
     }
     ri = rn;
@@ -2329,13 +2303,16 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_embed_select_kernel(Ge
 }
 
 // B <= 2 GEMV steps with the deferred granule select (SEL_GRAN) and option l0q (bf16): layer 0's
-// c_attn from the q0 tables, as ar_embed_select_kernel<false, true> computes it, over 9 blocks of 256
+// c_attn from the q0 tables (q0_out), over 9 blocks of 256
 // outputs instead of one block per row: every block reduces the rows' lm_head granules (as the GEMV's
 // GIN_EMBED_SELECT prologue does; block 0 commits the select and leaves the new records in the shadow arrays that
 // attention layer 0 copies back), loads its 256-column slices of Tt[t], Tp[p], G and Tc[c], and one
 // wave per row builds the embedding row for (den, mean, rstd) (block 0 also stores x). Round 6: the
 // single-block form cost the B = 1 step 6.6 us per launch (kernel trace) against 4.6-4.8 for its
 // other kernels.
+// Written out: built from the shared pieces this kernel measured ~0.5 us slower per B = 1 step (the compiler
+// ordered its loads differently). It mirrors deferred_record / deferred_commit (advance_rowstep false),
+// q0_row_stats and q0_out.
 __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_gran_kernel(GemvArgs a) {
   constexpr int BM = 2;  // rows (the GEMV steps' B <= 2)
   __shared__ int4 rn_s[BM];
@@ -2406,7 +2383,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_gran_kernel(GemvArg
 #pragma unroll
       for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)wave * D + j * 256 + lane * 4) = v[j];
     }
-    float sm = 0.f;  // (mean, rstd) as wave_ln_regs computes them
+    float sm = 0.f;  // (mean, rstd): mirrors wave_ln_stats
 #pragma unroll
     for (int j = 0; j < 3; ++j) sm += (v[j].x + v[j].y) + (v[j].z + v[j].w);
     const float mean = wave_sum(sm) * (1.0f / D);
@@ -2439,7 +2416,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_gran_kernel(GemvArg
 }
 
 // Batched steps (4 <= B <= 32, bf16, option l0q; SEL_Q0_ROWS): the previous step's greedy select and
-// layer 0's c_attn from the q0 tables (as ar_embed_select_kernel<false, true> computes them) over a grid
+// layer 0's c_attn from the q0 tables (q0_out) over a grid
 // of 9 column slices x B rows: every block reduces its row's 4,096 logits (four waves, as
 // ar_embed_select_kernel), loads 256-column slices of Tt[t], Tp[p], G and Tc[c] and builds the
 // embedding row for (den, mean, rstd) with wave 0. The select is committed by the row's first block
@@ -2473,38 +2450,15 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_rows_kernel(GemvArg
   const int t1 = tk ? rx.y : ri.z;
   const float tq = a.q0_text[(size_t)(t1 < 0 ? 384 : t1) * (3 * D) + n];
   const float tpo = a.q0_pos[(size_t)p1 * (3 * D) + n];
-  Best bt{-INFINITY, -INFINITY, 0x7fffffff};
-#pragma unroll
-  for (int k = 0; k < VOCAB / 1024; ++k) {
-    const int i0 = (k * 256 + tid) * 4;
-    bt = best_merge(bt, Best{lv[k].x, -INFINITY, i0});
-    bt = best_merge(bt, Best{lv[k].y, -INFINITY, i0 + 1});
-    bt = best_merge(bt, Best{lv[k].z, -INFINITY, i0 + 2});
-    bt = best_merge(bt, Best{lv[k].w, -INFINITY, i0 + 3});
-  }
-  bt = best_wave(bt);
-  if (lane == 0) { sv[wave] = bt.v; sv2[wave] = bt.v2; si[wave] = bt.i; }
+  row_best_wave([&](int k) { return lv[k]; }, sv, sv2, si);
   __syncthreads();
   int4 rn = ri;
   if (tk) {  // (block-uniform) every wave merges the four partials; the row's first block commits
-    Best r{sv[0], sv2[0], si[0]};
-#pragma unroll
-    for (int w = 1; w < 4; ++w) r = best_merge(r, Best{sv[w], sv2[w], si[w]});
-    r = softmax_ties(a.st.logits + (size_t)b * VOCAB, r, lane);
-    const int sl = ri.x, p = ri.y + 1, j = rx.x;
-    rn = make_int4(sl, min(p, a.st.max_pos - 1), rx.y, min(max(r.i, 0), VOCAB - 1));
-    if (cx == 0 && tid == 0) {  // argmax_commit, with the records into the shadow arrays
-      if (p >= a.st.max_pos) atomicOr(a.st.err, 1);
-      if (j < a.st.plan_stride) {
-        a.st.tok_plan[(size_t)b * a.st.plan_stride + j] = r.i;
-        if (a.st.margin_plan) a.st.margin_plan[(size_t)b * a.st.plan_stride + j] = r.v - r.v2;
-      }
-      a.st.prev[sl] = r.i;
-      a.st.pos[sl] = p;
-      a.st.rowstep[b] = j + 1;
-    }
+    const Best r = row_best_merge(sv, sv2, si, a.st.logits + (size_t)b * VOCAB, lane);
+    rn = deferred_record(a.st, ri, rx, r);
+    if (cx == 0 && tid == 0) deferred_commit(a.st, b, ri.x, ri.y + 1, rx.x, r, true);
   }
-  if (cx == 0 && tid == 0) {
+  if (cx == 0 && tid == 0) {  // the records into the shadow arrays
     a.st.rowinfo_n[b] = rn;
     a.st.rowx_n[b] = make_int2(tk ? rx.x + 1 : rx.x, 0);  // attention layer 0 looks up the next text id
   }
@@ -2514,9 +2468,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_q0_rows_kernel(GemvArg
     if (lane == 0) sst = s4;
   }
   __syncthreads();
-  const float4 st = sst;
-  const float cz = rn.y == 0 ? 0.f : 1.f;  // position 0: the codebook half of the input is zero
-  const float o = rn.x < 0 ? 0.f : st.z * (((tq + cz * tc) * st.x + tpo) - st.y * gq);
+  const float o = rn.x < 0 ? 0.f : q0_out(sst, rn.y, tq, tc, tpo, gq);
   if (n < D) {
     a.st.q[(size_t)b * D + n] = o;
   } else if (rn.x >= 0) {  // K / V append at the row's (slot, pos), as c_attn's epilogue
@@ -2912,8 +2864,8 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
     wf[kk] = *reinterpret_cast<const uint4*>(
         reinterpret_cast<const bf16_t*>(a.Wf) + (((size_t)(n0 >> 4) * (K / 32) + wave * 6 + kk) * 64 + lane) * 8);
   if constexpr (MODE == MLMODE_EMBED_SELECT) {
-    // commit the previous step's select (ar_embed_select_kernel's argmax_commit, B <= 2 GIN_EMBED_SELECT's shadow
-    // records); reduction and record select unconditional so that the granule loads stay up front
+    // commit the previous step's select (deferred_commit; the records into the shadow arrays, as the B <= 2
+    // GIN_EMBED_SELECT); reduction and record select unconditional so that the granule loads stay up front
 #pragma unroll
     for (int i = 0; i < SR; ++i) {
       const int b = wave + NW * i, bc = min(b, B - 1);
@@ -2921,18 +2873,9 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
       const int4 r0 = ri[i];
       const int s = r0.x, j = rxp[i].x, p = r0.y + 1;
       const bool take = selpend && s >= 0;
-      const int4 rn = take ? make_int4(s, min(p, a.st.max_pos - 1), rxp[i].y, min(max(r.i, 0), VOCAB - 1)) : r0;
+      const int4 rn = take ? deferred_record(a.st, r0, rxp[i], r) : r0;
       if (b < B && blockIdx.x == 0 && lane == 0) {
-        if (take) {
-          if (p >= a.st.max_pos) atomicOr(a.st.err, 1);
-          if (j < a.st.plan_stride) {
-            a.st.tok_plan[(size_t)b * a.st.plan_stride + j] = r.i;
-            if (a.st.margin_plan) a.st.margin_plan[(size_t)b * a.st.plan_stride + j] = r.v - r.v2;
-          }
-          a.st.prev[s] = r.i;
-          a.st.pos[s] = p;
-          a.st.rowstep[b] = j + 1;
-        }
+        if (take) deferred_commit(a.st, b, s, p, j, r, true);
         a.st.rowx_n[b] = make_int2(take ? j + 1 : j, 0);  // attention layer 0 looks up the next text id
         a.st.rowinfo_n[b] = rn;
       }
@@ -3488,21 +3431,21 @@ static void launch_attn(const ArState& st, int kvdtype, int B, int l, hipStream_
   // t = 384-639 fp8 KV 103.9 vs 98.3 us/step, bf16 KV 109.6 vs 100.1)
   if (qkv && kvdtype != LVX_DTYPE_F32) return;  // (no such path: the K split is the fp32 parity mode's)
   if (nw8 && kvdtype == LVX_DTYPE_BF16)  // 8 waves, 128-key tiles: twice the KV bytes in flight per block
-    hipLaunchKernelGGL((ar_attn_v2_kernel<bf16_t, 2, 8>), grid, dim3(512), 0, s, st, l, ns_max, direct, selcopy);
+    hipLaunchKernelGGL((ar_attn_v2_kernel<bf16_t, 8>), grid, dim3(512), 0, s, st, l, ns_max, direct, selcopy);
   // (round 5, measured slower: 3 / 4 fp8 KV tiles in flight per wave at B = 8, t = 384-639 99.2 / 100.1
   // vs 98.0 us/step)
   else if (nw8 && kvdtype == LVX_DTYPE_FP8)
-    hipLaunchKernelGGL((ar_attn_v2_kernel<fp8_t, 2, 8>), grid, dim3(512), 0, s, st, l, ns_max, direct, selcopy);
+    hipLaunchKernelGGL((ar_attn_v2_kernel<fp8_t, 8>), grid, dim3(512), 0, s, st, l, ns_max, direct, selcopy);
   // (round 4, fp32 KV at B = 32, measured slower: 8 waves with 128-key tiles 212.6, 3 tiles in flight
   // per wave 218.0 vs 211.7 us/step)
   else if (qkv)  // fp32 parity mode: ar_qkv_ksplit_f32_kernel's partials (the only K-split c_attn)
-    hipLaunchKernelGGL((ar_attn_v2_kernel<float, 2, 4, true>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
+    hipLaunchKernelGGL((ar_attn_v2_kernel<float, 4, true>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
   else if (kvdtype == LVX_DTYPE_BF16)
-    hipLaunchKernelGGL((ar_attn_v2_kernel<bf16_t, 2, 4>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
+    hipLaunchKernelGGL((ar_attn_v2_kernel<bf16_t, 4>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
   else if (kvdtype == LVX_DTYPE_FP8)
-    hipLaunchKernelGGL((ar_attn_v2_kernel<fp8_t, 2, 4>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
+    hipLaunchKernelGGL((ar_attn_v2_kernel<fp8_t, 4>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
   else
-    hipLaunchKernelGGL((ar_attn_v2_kernel<float, 2, 4>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
+    hipLaunchKernelGGL((ar_attn_v2_kernel<float, 4>), grid, dim3(256), 0, s, st, l, ns_max, direct, selcopy);
 }
 
 // ArWeights q0_* tables (lvx_finalize, once): out[r][n] = sum_k<K (src[r][k] * g[k0 + k]) * W[n][k0 + k],
@@ -3868,7 +3811,7 @@ __global__ __launch_bounds__(64) void ar_select_final_kernel(ArState st) {
 // Test hook (lvx_select_probe): the greedy select of each production path over given logits
 // (st.logits). path 0: ar_argmax_kernel; 1: per-block lm_head granules formed as GOUT_LOGITS_GRAN forms them
 // (8 consecutive vocabulary rows per block), reduced by ar_select_final_kernel (lmg_reduce +
-// softmax_ties, the same code as the deferred select in c_attn layer 0, GIN_EMBED_SELECT); 2: the batched
+// softmax_ties, the functions the deferred select in c_attn layer 0, GIN_EMBED_SELECT, calls); 2: the batched
 // deferred select, ar_embed_select_kernel; 4: the sampled select, ar_sample_kernel.
 __global__ void ar_select_probe_prep_kernel(ArState st, int B, int path) {
   const int blk = blockIdx.x, b = threadIdx.x;
