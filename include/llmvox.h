@@ -930,6 +930,29 @@ int lvx_encode(lvx_enc* enc, const float* audio_dev, int B, int N, float* featur
                void* stream);
 /* test hook: the pre-quantisation embedding [B][T][512] of the last lvx_encode */
 int lvx_enc_embedding(lvx_enc* enc, float* dst_dev, int B, int T, void* stream);
+/* Test hook (tests/test_gpu_encoder_stages.py): stages [first, last] of lvx_encode on caller-supplied input,
+ * through lvx_encode's own stage list, launch helpers, SConv1d geometry, scratch and capacity checks (lvx_encode
+ * is the window [0, LVX_ENC_STAGES - 1] of the same walk); the counterpart of lvx_codec_stages for the encoder.
+ * It adds no kernel and no launch to lvx_encode. Activations are time-major float32, as the kernels use them.
+ * Stages (LVX_ENC_STAGES of them), d = 32, 64, 128, 256 for the ratios r = 2, 4, 5, 8:
+ *    0           conv "0" (k7, 1 -> 32)                        in: audio [B][L]     out: [B][L][32]
+ *    1, 3, 5, 7  residual block of ratio 2, 4, 5, 8: block.1,
+ *                shortcut, block.3 + shortcut                  [B][L][d]         -> [B][L][d]
+ *    2, 4, 6, 8  ELU + strided down conv of that ratio         [B][L][d]         -> [B][ceil(L / r)][2 d]
+ *    9           SLSTM: both layers and the skip               [B][T][512]       -> [B][T][512]
+ *   10           ELU + conv "15" (k7)                          [B][T][512]       -> [B][T][512]
+ *   11           quantiser: scores + select                    [B][T][512]       -> codes_dev int32 [B][T],
+ *                                                                                   features_dev [B][512][T]
+ * L is the length per stream of the input of stage `first`; any L >= 1 is legal at any stage. in_dev holds that
+ * input; out_dev receives the output of stage `last` when last < 11 (it may be null otherwise); a window that
+ * ends at 11 writes codes_dev and features_dev and, where scores_dev is not null, the scores x . e it selected
+ * from, [B][T][4096]. Buffers are device buffers, copied / written in stream order. Arguments are checked as
+ * lvx_encode checks them (LVX_E_CAPACITY: an intermediate of the window beyond the scratch sized by max_samples,
+ * B beyond 1,024, and B * L beyond max_samples where first = 0; LVX_E_ARG), plus
+ * 0 <= first <= last < LVX_ENC_STAGES. */
+#define LVX_ENC_STAGES 12
+int lvx_enc_stages(lvx_enc* enc, int first, int last, const float* in_dev, int B, int L, float* out_dev,
+                   int32_t* codes_dev, float* features_dev, float* scores_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,7 @@ _SIGS = {
     "lvx_enc_frames": (_I, [_I]),
     "lvx_encode": (_I, [_P, _P, _I, _I, _P, _P, _P]),
     "lvx_enc_embedding": (_I, [_P, _P, _I, _I, _P]),
+    "lvx_enc_stages": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -183,6 +184,7 @@ ROUTE_MFMA64, ROUTE_BF16_128, ROUTE_GLDS, ROUTE_SKINNY = 0, 1, 2, 3
 AR_OUT_Q, AR_OUT_QKV_PARTS, AR_OUT_ATTN_ROWS, AR_OUT_ATTN_PARTS, AR_OUT_X, AR_OUT_H, AR_OUT_LOGITS = range(7)
 AR_OPS, AR_INFO = 21, 12
 CODEC_STAGES = 21  # LVX_CODEC_STAGES
+ENC_STAGES = 12  # LVX_ENC_STAGES
 
 
 def error_for(code: int, bits: int = 0):

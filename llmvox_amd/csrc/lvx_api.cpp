@@ -1676,6 +1676,8 @@ ConvGeo conv_geo(int L, int k, int stride, int dil) {
   const int ex0 = L <= max_pad ? max_pad - L + 1 : 0;
   return {pl, L + ex0, (pl + L + right - keff) / stride + 1};
 }
+// channels of the output of stage st < 11 (stages: llmvox.h, lvx_enc_stages)
+int enc_stage_channels(int st) { return st >= 9 ? 512 : 32 << (st / 2); }
 int enc_frames_of(int n) {
   int L = n;
   for (const EncConv& cv : enc_convs()) L = conv_geo(L, cv.k, cv.stride, cv.dil).T;
@@ -1808,59 +1810,111 @@ int lvx_enc_finalize(lvx_enc* e) {
   return LVX_OK;
 }
 
-// audio [B][N] -> features [B][512][T], codes [B][T] (device pointers; T = lvx_enc_frames(N))
-int lvx_encode(lvx_enc* e, const float* audio, int B, int N, float* features, int32_t* codes, void* stream) {
-  if (!e) return fail(LVX_E_ARG, "null argument");
-  if (!e->finalized) return fail(LVX_E_STATE, "call lvx_enc_finalize first");
-  if (B < 1 || N < 1 || !audio || !features || !codes) return fail(LVX_E_ARG, "bad audio / outputs");
-  if ((long long)B * N > e->max_samples || B > e->bmax)
-    return fail(LVX_E_CAPACITY, "B*N = " + std::to_string((long long)B * N) + " exceeds max_samples " + std::to_string(e->max_samples));
-  HIP_TRY(hipSetDevice(e->device));
-  hipStream_t s = (hipStream_t)stream;
+// Stages [first, last] of the encoder (the table at lvx_enc_stages in llmvox.h) on `in`, the input of stage
+// `first` with L frames per stream: the one stage list of lvx_encode (the window [0, last stage]) and of the
+// test hook. It is walked twice per call: launch = false holds every intermediate of the window against the
+// scratch and launches nothing, launch = true launches. A stage reads the caller's pointer or the buffer its
+// predecessor wrote; *out / *Lout name what the last stage left (stage 11: the embedding it read, with the
+// scores in buf[1]).
+static int enc_walk(lvx_enc* e, int first, int last, const float* in, int B, int L, float* features, int32_t* codes,
+                    bool launch, hipStream_t s, const float** out, int* Lout) {
   float** buf = e->buf;
-  // the whole chain's sizes first (every intermediate within a buffer)
-  {
-    int L = N;
-    for (const EncConv& cv : e->convs) {
-      const ConvGeo g = conv_geo(L, cv.k, cv.stride, cv.dil);
-      if ((size_t)B * g.T * cv.cout > e->buf_floats || (size_t)B * L * cv.cin > e->buf_floats)
-        return fail(LVX_E_CAPACITY, "encoder activations exceed the scratch sized by max_samples");
-      L = g.T;
-    }
-    if ((size_t)B * L * 4096 > e->buf_floats) return fail(LVX_E_CAPACITY, "quantiser scores exceed the scratch");
-  }
+  bool fits = true;
   auto conv = [&](int i, const float* x, int L, float* y, const float* res) {
     const EncConv& cv = e->convs[i];
     const ConvGeo g = conv_geo(L, cv.k, cv.stride, cv.dil);
-    enc_launch_conv(x, e->cw[i], e->cb[i], res, y, B, L, g.T, cv.cin, cv.cout, cv.k, cv.stride, cv.dil, g.pl, g.lext, cv.elu, s);
+    if (!launch)
+      fits = fits && (size_t)B * g.T * cv.cout <= e->buf_floats && (size_t)B * L * cv.cin <= e->buf_floats;
+    else
+      enc_launch_conv(x, e->cw[i], e->cb[i], res, y, B, L, g.T, cv.cin, cv.cout, cv.k, cv.stride, cv.dil, g.pl, g.lext, cv.elu, s);
     return g.T;
   };
-  // conv 0, then per ratio: t1 = block.1(ELU x), sc = shortcut(x), x' = block.3(ELU t1) + sc, down(ELU x')
-  int L = conv(0, audio, N, buf[0], nullptr);
-  for (int blk = 0; blk < 4; ++blk) {
-    const int i = 1 + 4 * blk;
-    conv(i, buf[0], L, buf[1], nullptr);
-    conv(i + 2, buf[0], L, buf[2], nullptr);
-    conv(i + 1, buf[1], L, buf[3], buf[2]);
-    L = conv(i + 3, buf[3], L, buf[0], nullptr);
+  // the LSTM's input projections and the quantiser's scores: a 1-tap "conv" with the matrix as weights
+  auto proj = [&](const float* x, const float* w, const float* bias, float* y, int n) {
+    if (!launch)
+      fits = fits && (size_t)B * L * n <= e->buf_floats;
+    else
+      enc_launch_conv(x, w, bias, nullptr, y, B, L, L, 512, n, 1, 1, 1, 0, L, false, s);
+  };
+  const float* x = in;
+  for (int st = first; st <= last; ++st) {
+    if (st == 0) {
+      L = conv(0, x, L, buf[0], nullptr);
+      x = buf[0];
+    } else if (st <= 8) {
+      const int i = 1 + 4 * ((st - 1) / 2);
+      if (st & 1) {  // residual block: t1 = block.1(ELU x), sc = shortcut(x), x' = block.3(ELU t1) + sc
+        conv(i, x, L, buf[1], nullptr);
+        conv(i + 2, x, L, buf[2], nullptr);
+        conv(i + 1, buf[1], L, buf[3], buf[2]);
+        x = buf[3];
+      } else {  // down(ELU x')
+        L = conv(i + 3, x, L, buf[0], nullptr);
+        x = buf[0];
+      }
+    } else if (st == 9) {  // SLSTM: layer 0 -> buf[2], layer 1 (+ skip from the LSTM input) -> buf[3]
+      for (int l = 0; l < 2; ++l) {
+        float* yout = l == 0 ? buf[2] : buf[3];
+        proj(l == 0 ? x : buf[2], e->wih[l], e->bih[l], buf[1], 2048);
+        if (!launch) continue;
+        HIP_TRY(hipMemsetAsync(e->h, 0, (size_t)B * 512 * 4, s));
+        HIP_TRY(hipMemsetAsync(e->c, 0, (size_t)B * 512 * 4, s));
+        for (int t = 0; t < L; ++t)
+          enc_launch_lstm_step(buf[1], e->whh[l], e->bhh[l], e->h + (size_t)(t & 1) * e->bmax * 512,
+                               e->h + (size_t)((t + 1) & 1) * e->bmax * 512, e->c, yout, l == 1 ? x : nullptr, B, L, t, s);
+      }
+      x = buf[3];
+    } else if (st == 10) {  // ELU -> final conv: embedding [B][T][512]
+      conv(17, x, L, buf[0], nullptr);
+      x = buf[0];
+    } else {  // quantiser: scores x . e, then argmax + gather
+      proj(x, e->codebook, nullptr, buf[1], 4096);
+      if (launch) enc_launch_vq(x, buf[1], e->esq, e->codebook, codes, features, B, L, s);
+    }
   }
-  const int T = L;  // x = buf[0] [B][T][512]
-  // SLSTM: layer 0 -> buf[2], layer 1 (+ skip from the LSTM input) -> buf[3]
-  for (int l = 0; l < 2; ++l) {
-    const float* xin = l == 0 ? buf[0] : buf[2];
-    float* yout = l == 0 ? buf[2] : buf[3];
-    enc_launch_conv(xin, e->wih[l], e->bih[l], nullptr, buf[1], B, T, T, 512, 2048, 1, 1, 1, 0, T, false, s);
-    HIP_TRY(hipMemsetAsync(e->h, 0, (size_t)B * 512 * 4, s));
-    HIP_TRY(hipMemsetAsync(e->c, 0, (size_t)B * 512 * 4, s));
-    for (int t = 0; t < T; ++t)
-      enc_launch_lstm_step(buf[1], e->whh[l], e->bhh[l], e->h + (size_t)(t & 1) * e->bmax * 512,
-                           e->h + (size_t)((t + 1) & 1) * e->bmax * 512, e->c, yout, l == 1 ? buf[0] : nullptr, B, T, t, s);
-  }
-  conv(17, buf[3], T, buf[0], nullptr);  // ELU -> final conv: embedding [B][T][512]
-  // quantiser: scores x . e (a 1-tap conv with the codebook as weights), then argmax + gather
-  enc_launch_conv(buf[0], e->codebook, nullptr, nullptr, buf[1], B, T, T, 512, 4096, 1, 1, 1, 0, T, false, s);
-  enc_launch_vq(buf[0], buf[1], e->esq, e->codebook, codes, features, B, T, s);
+  if (!fits) return fail(LVX_E_CAPACITY, "encoder activations exceed the scratch sized by max_samples");
+  *out = x;
+  *Lout = L;
+  return LVX_OK;
+}
+
+// the checks of a call, the capacity walk, then the launches
+static int enc_run(lvx_enc* e, int first, int last, const float* in, int B, int L, float* features, int32_t* codes,
+                   hipStream_t s, const float** out, int* Lout) {
+  if (!e) return fail(LVX_E_ARG, "null argument");
+  if (!e->finalized) return fail(LVX_E_STATE, "call lvx_enc_finalize first");
+  if (B < 1 || L < 1 || !in || (last == LVX_ENC_STAGES - 1 && (!features || !codes)))
+    return fail(LVX_E_ARG, "bad audio / outputs");
+  if ((first == 0 && (long long)B * L > e->max_samples) || B > e->bmax)
+    return fail(LVX_E_CAPACITY, "B*N = " + std::to_string((long long)B * L) + " exceeds max_samples " + std::to_string(e->max_samples));
+  HIP_TRY(hipSetDevice(e->device));
+  if (int r = enc_walk(e, first, last, in, B, L, features, codes, false, s, out, Lout)) return r;
+  if (int r = enc_walk(e, first, last, in, B, L, features, codes, true, s, out, Lout)) return r;
   HIP_TRY(hipGetLastError());
+  return LVX_OK;
+}
+
+// audio [B][N] -> features [B][512][T], codes [B][T] (device pointers; T = lvx_enc_frames(N))
+int lvx_encode(lvx_enc* e, const float* audio, int B, int N, float* features, int32_t* codes, void* stream) {
+  const float* x;
+  int T;
+  return enc_run(e, 0, LVX_ENC_STAGES - 1, audio, B, N, features, codes, (hipStream_t)stream, &x, &T);
+}
+
+// test hook: a window of the stage list on the caller's input
+int lvx_enc_stages(lvx_enc* e, int first, int last, const float* in, int B, int L, float* out, int32_t* codes,
+                   float* features, float* scores, void* stream) {
+  if (first < 0 || last >= LVX_ENC_STAGES || first > last)
+    return fail(LVX_E_ARG, "stage window must satisfy 0 <= first <= last < " + std::to_string(LVX_ENC_STAGES));
+  if (last < LVX_ENC_STAGES - 1 && !out) return fail(LVX_E_ARG, "null out");
+  hipStream_t s = (hipStream_t)stream;
+  const float* x;
+  int T;
+  if (int r = enc_run(e, first, last, in, B, L, features, codes, s, &x, &T)) return r;
+  if (last < LVX_ENC_STAGES - 1)
+    HIP_TRY(hipMemcpyAsync(out, x, (size_t)B * T * enc_stage_channels(last) * 4, hipMemcpyDeviceToDevice, s));
+  else if (scores)
+    HIP_TRY(hipMemcpyAsync(scores, e->buf[1], (size_t)B * T * 4096 * 4, hipMemcpyDeviceToDevice, s));
   return LVX_OK;
 }
 

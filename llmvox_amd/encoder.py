@@ -67,6 +67,32 @@ class WavEncoder:
         _lib.check(self.lib.lvx_enc_embedding(self.h, ctypes.c_void_p(out.data_ptr()), B, T, s))
         return out.permute(0, 2, 1)
 
+    def stages(self, first: int, last: int, inp: torch.Tensor, scores: bool = False):
+        """Test hook: stages ``first .. last`` of the encode (the table at lvx_enc_stages in llmvox.h) on
+        ``inp``, time-major fp32: audio [B, L] for stage 0, [B, L, d] otherwise. Returns the output of stage
+        ``last`` [B, T, d'], or for last = 11 (codes int32 [B, T], features [B, 512, T], and with ``scores``
+        the quantiser's scores [B, T, 4096] or None)."""
+        x = inp.to(self.device, torch.float32).contiguous()
+        B, L = int(x.shape[0]), int(x.shape[1])
+        T = L
+        for st in range(first, last + 1):
+            if st in (2, 4, 6, 8):
+                r = {2: 2, 4: 4, 6: 5, 8: 8}[st]
+                T = -(-T // r)
+        s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        out = codes = feats = sc = None
+        if last == _lib.ENC_STAGES - 1:
+            codes = torch.empty(B, T, dtype=torch.int32, device=self.device)
+            feats = torch.empty(B, 512, T, dtype=torch.float32, device=self.device)
+            sc = torch.empty(B, T, 4096, dtype=torch.float32, device=self.device) if scores else None
+        else:
+            d = 512 if last >= 9 else 32 << (last // 2)
+            out = torch.empty(B, T, d, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.lvx_enc_stages(self.h, int(first), int(last), ptr(x), B, L, ptr(out), ptr(codes),
+                                           ptr(feats), ptr(sc), s))
+        return out if out is not None else (codes, feats, sc)
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.lvx_enc_destroy(self.h)

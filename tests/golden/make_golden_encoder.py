@@ -12,7 +12,12 @@ audio:
 * per frame the gap between the best and second-best quantiser score (which codes are robust to
   summation-order rounding).
 
-usage: python tests/golden/make_golden_encoder.py [/root/reference]  -> tests/golden/encoder_golden.npz
+The edge cases (EDGE_CASES -> encoder_edge_golden.npz, same keys) are the shapes at which the SConv1d zero
+extension (N no longer than a pad, down to one sample), a second and third group of 16 LSTM streams and
+lengths just past a frame boundary occur.
+
+usage: python tests/golden/make_golden_encoder.py [/root/reference]
+  -> tests/golden/encoder_golden.npz, tests/golden/encoder_edge_golden.npz
 """
 import os
 import sys
@@ -25,6 +30,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
 CASES = ((2, 12000), (1, 6400), (3, 4800), (1, 1000), (1, 300))
+EDGE_CASES = ((1, 1), (2, 2), (1, 7), (2, 319), (1, 321), (17, 640), (33, 961))
 
 
 def synth_audio(B, N, seed):
@@ -53,32 +59,33 @@ def main(ref_root="/root/reference"):
     vq = fe.encodec.quantizer.vq.layers[0]._codebook
     vq.inited.fill_(1.0)
     fe.eval()
-    out = {}
     with torch.inference_mode():
-        for i, (B, N) in enumerate(CASES):
-            audio = synth_audio(B, N, 100 + i)
-            a = torch.from_numpy(audio)
-            feats, codes = wt.encode_infer(a, bandwidth_id=torch.tensor([0]))
-            emb = fe.encodec.encoder(a.unsqueeze(1))
-            x = emb.permute(0, 2, 1).reshape(-1, emb.shape[1])
-            e = vq.embed.t()
-            dist = -(x.pow(2).sum(1, keepdim=True) - 2 * x @ e + e.pow(2).sum(0, keepdim=True))
-            top = torch.topk(dist, 2, dim=-1).values
-            assert torch.equal(feats, torch.nn.functional.embedding(codes[0], vq.embed).transpose(1, 2))
-            tag = f"{B}x{N}"
-            out[f"audio_{tag}"] = audio
-            out[f"codes_{tag}"] = codes.numpy().astype(np.int32)
-            out[f"gap_{tag}"] = (top[:, 0] - top[:, 1]).numpy().astype(np.float32)
-            en = emb.numpy().astype(np.float32)
-            if en.size <= 16384:
-                out[f"emb_{tag}"] = en
-            else:
-                out[f"emb_{tag}_rms"] = np.float64(np.sqrt(np.mean(en.astype(np.float64) ** 2)))
-                out[f"emb_{tag}_every7"] = en.reshape(-1)[::7].copy()
-                out[f"emb_{tag}_shape"] = np.array(en.shape, np.int32)
-            print(tag, "T", codes.shape[-1], "codes[:8]", codes.reshape(-1)[:8].tolist(),
-                  "min gap", float(out[f"gap_{tag}"].min()), "emb rms", float(np.sqrt(np.mean(en ** 2))))
-    np.savez_compressed(os.path.join(HERE, "encoder_golden.npz"), **out)
+        for fname, cases, seed0 in (("encoder_golden.npz", CASES, 100), ("encoder_edge_golden.npz", EDGE_CASES, 200)):
+            out = {}
+            for i, (B, N) in enumerate(cases):
+                audio = synth_audio(B, N, seed0 + i)
+                a = torch.from_numpy(audio)
+                feats, codes = wt.encode_infer(a, bandwidth_id=torch.tensor([0]))
+                emb = fe.encodec.encoder(a.unsqueeze(1))
+                x = emb.permute(0, 2, 1).reshape(-1, emb.shape[1])
+                e = vq.embed.t()
+                dist = -(x.pow(2).sum(1, keepdim=True) - 2 * x @ e + e.pow(2).sum(0, keepdim=True))
+                top = torch.topk(dist, 2, dim=-1).values
+                assert torch.equal(feats, torch.nn.functional.embedding(codes[0], vq.embed).transpose(1, 2))
+                tag = f"{B}x{N}"
+                out[f"audio_{tag}"] = audio
+                out[f"codes_{tag}"] = codes.numpy().astype(np.int32)
+                out[f"gap_{tag}"] = (top[:, 0] - top[:, 1]).numpy().astype(np.float32)
+                en = emb.numpy().astype(np.float32)
+                if en.size <= 16384:
+                    out[f"emb_{tag}"] = en
+                else:
+                    out[f"emb_{tag}_rms"] = np.float64(np.sqrt(np.mean(en.astype(np.float64) ** 2)))
+                    out[f"emb_{tag}_every7"] = en.reshape(-1)[::7].copy()
+                    out[f"emb_{tag}_shape"] = np.array(en.shape, np.int32)
+                print(tag, "T", codes.shape[-1], "codes[:8]", codes.reshape(-1)[:8].tolist(),
+                      "min gap", float(out[f"gap_{tag}"].min()), "emb rms", float(np.sqrt(np.mean(en ** 2))))
+            np.savez_compressed(os.path.join(HERE, fname), **out)
 
 
 if __name__ == "__main__":
