@@ -909,6 +909,75 @@ int lvx_pcm_flac(lvx_ctx* ctx, const int16_t* s16_dev, long long in_stride_bytes
                  const int32_t* slots_host, const uint8_t* final_host, int sample_rate, void* out_dev,
                  long long out_stride_bytes, int32_t* n_frames_host, void* stream);
 
+/* ---- PCM pause -------------------------------------------------------------------
+ * The pacing between sentences: the LAST stage, behind lvx_pcm_convert (or behind whichever stage produced the rows
+ * of a 24 kHz f32le format, whose conversion does not run). It drops nothing on the device: it cuts the rows, in the
+ * format's own encoding (LVX_PCM_F32LE, _S16LE, _ULAW, _ALAW) at any of the four rates, into blocks of 10 ms, marks
+ * each silent or not and says where the sentence ends; the host then trims, caps and spaces by whole blocks
+ * (llmvox_amd/audio.py: PauseMux, the rule stated there as pause_ref). Bytes are copied and integers compared, so THE
+ * DEVICE'S SLOTS ARE THOSE OF A HOST EVALUATION (lvx_pause_slots; audio.py: pause_slots_ref) AND DO NOT DEPEND ON HOW
+ * A SEGMENT IS CUT INTO CALLS. One segment is one sentence of one stream.
+ *
+ * Blocks. bl = sample_rate / 100: 80, 160, 240, 480 samples. A sentence of T > 0 samples is ceil(T / bl) blocks;
+ * block j holds samples j bl .. min((j + 1) bl, T) - 1, so every block has bl samples but the last, which has
+ * 1 .. bl. A sentence of no samples has no block.
+ *
+ * Slots. One per block, LVX_PAUSE_SLOT(rate, bytes per sample) = 8 + bl * bytes bytes, a multiple of 8:
+ *   the record {uint16 n (samples of the block, 1 .. bl, little endian), uint8 active, uint8 last (1 on the
+ *   sentence's last block), uint32 0};
+ *   the payload: the block's n samples, byte for byte as the stage before wrote them, then the encoding's silence up
+ *   to bl samples (the G.711 code of 0: 0xFF mu-law, 0xD5 A-law; zero bytes otherwise).
+ *
+ * The mark. active = 1 iff some sample of the block is louder than LVX_PAUSE_THRESH = 103 on the 16-bit scale
+ * (about -50 dBFS): s16le |q| > 103, the magnitude taken in 32 bits (q = -32768 is active); f32le |v| > 103 / 32768
+ * (= 0.003143310546875, exact in fp32), a NaN counting as active; mu-law / A-law the s16le test on the decoded sample
+ * (lvx_pcm_g711_decode: the decoded magnitudes nearest the threshold are 96 and 104 for mu-law, 88 and 104 for A-law;
+ * A-law's silence 0xD5 decodes to 8 and is silent). THE MARK IS A PROPERTY OF THE ENCODED SAMPLES: the same audio can
+ * mark differently as f32le and as s16le at the edge (103.4 / 32768 is loud as f32le and rounds to 103, silent, as
+ * s16le).
+ *
+ * Streaming. After a non-final call that brings the segment's input to T > 0 the blocks emitted so far are
+ * floor((T - 1) / bl): the complete ones that at least one more sample follows; a final call emits the rest,
+ * ceil(T / bl) in all. So the sentence's last block always leaves with the final call and always carries last = 1,
+ * and the stage HOLDS BACK 1 .. bl SAMPLES (UP TO 10 ms) UNTIL THE SENTENCE ENDS. The library keeps them per KV slot
+ * (two buffers of 480 * 4 bytes per slot: a launch reads one and writes the other) and, on the host, a mirror of the
+ * slot's count, rate and encoding. A segment has one rate and one encoding: another before its final call is
+ * LVX_E_ARG.
+ *
+ * The host's rule (audio.py), per request, P = pause_ms / 10 blocks and C = max_pause_ms / 10 blocks or none, with
+ * LVX_PAUSE_LEAD = 2 and LVX_PAUSE_TRAIL = 5 blocks: a sentence without an active block delivers nothing; any other
+ * delivers its blocks from max(first active - 2, 0) through min(last active + 5, its last block), the sentence's last
+ * block with its n samples only; with C, a run of more than C silent blocks between two active ones keeps its first
+ * C - 2 and its last 2; between two delivering sentences come exactly P blocks of the encoding's silence. With only
+ * max_pause_ms named no edge is trimmed and no gap inserted. There is no crossfade at a cut: both sides of every cut
+ * are blocks whose peak is at most the threshold, -50 dBFS; nothing more is claimed. */
+#define LVX_PAUSE_THRESH 103
+#define LVX_PAUSE_LEAD 2
+#define LVX_PAUSE_TRAIL 5
+#define LVX_PAUSE_SLOT(rate, sample_bytes) (8 + (rate) / 100 * (sample_bytes))
+/* host only: blocks a call emits for a slot that has consumed t0 inputs of its segment (negative: LVX_E_ARG for an
+ * unsupported rate, t0 < 0 or n_in < 0) */
+int lvx_pcm_pause_emitted(int sample_rate, long long t0, int n_in, int final);
+/* host only: bytes of one slot (negative: LVX_E_ARG for an unsupported rate or encoding) */
+int lvx_pcm_pause_slot(int sample_rate, int encoding);
+/* host only: the slots of blocks j0 .. j1 - 1 of the finished sentence y (T samples of the encoding) by the rule
+ * above, serially. Returns their bytes. LVX_E_ARG: an unsupported rate or encoding, a null pointer, T < 0, blocks
+ * outside 0 <= j0 <= j1 <= ceil(T / bl), slots of 2^31 bytes or more in one call; LVX_E_CAPACITY: cap is smaller
+ * than the slots (nothing is written). */
+int lvx_pause_slots(int sample_rate, int encoding, const void* y, long long T, long long j0, long long j1, uint8_t* out,
+                    long long cap);
+/* lvx_pcm_flac's conventions: rows b of in_dev (samples of the encoding, row b at in_dev + b * in_stride_bytes, n_in
+ * samples) continue the pause segments of slots_host[b]; final_host[b] != 0 emits the sentence's last block and
+ * resets the slot; n_in may be 0 with final. out row b starts at out_dev + b * out_stride_bytes; n_blocks_host[b] =
+ * slots written. LVX_E_ARG (and no slot's state changed): an unsupported rate or encoding, or another pair than the
+ * slot's open segment has, B < 1, n_in < 0, a slot out of range or named twice, in_dev or in_stride_bytes no multiple
+ * of the sample's bytes, in_stride_bytes smaller than a row, out_dev or out_stride_bytes no multiple of 8.
+ * LVX_E_CAPACITY (and no slot's state changed): out_stride_bytes smaller than a row's slots. lvx_pcm_reset also
+ * forgets a slot's pause state. */
+int lvx_pcm_pause(lvx_ctx* ctx, const void* in_dev, long long in_stride_bytes, int B, int n_in,
+                  const int32_t* slots_host, const uint8_t* final_host, int sample_rate, int encoding, void* out_dev,
+                  long long out_stride_bytes, int32_t* n_blocks_host, void* stream);
+
 /* ---- WavTokenizer encoder, a context of its own (its weights are not needed for TTS).
  * Replaces WavTokenizer.encode_infer (WavTokenizer/decoder/pretrained.py:185-190 ->
  * decoder/feature_extractors.py:122-133): SEANet encoder (encoder/modules/seanet.py:94-143) + the

@@ -143,6 +143,10 @@ _SIGS = {
     "lvx_flac_subframe": (_I, [_P, _I, _P, _I]),
     "lvx_flac_finish": (_I, [_I, _P, _I, ctypes.POINTER(ctypes.c_ulonglong), _P, _I]),
     "lvx_pcm_flac": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _P, _P, _I, _P, ctypes.c_longlong, _P, _P]),
+    "lvx_pcm_pause_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
+    "lvx_pcm_pause_slot": (_I, [_I, _I]),
+    "lvx_pause_slots": (_I, [_I, _I, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, ctypes.c_longlong]),
+    "lvx_pcm_pause": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _P, _P, _I, _I, _P, ctypes.c_longlong, _P, _P]),
     "lvx_enc_create": (_I, [_I, ctypes.c_longlong, ctypes.POINTER(_P)]),
     "lvx_enc_set_weight": (_I, [_P, ctypes.c_char_p, _P, ctypes.c_int64]),
     "lvx_enc_finalize": (_I, [_P]),

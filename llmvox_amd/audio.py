@@ -13,7 +13,9 @@ short-time Fourier correction of the spectral envelope, between the ratio and th
 ``formant_ref``. And the G.711 encodings ("PCM G.711": the s16 quantisation companded to 8-bit mu-law or A-law, integer
 arithmetic only): ``g711_encode``, ``g711_decode``. And the FLAC output ("PCM FLAC": the s16 samples cut into frames of
 40 ms, each a CONSTANT, FIXED or VERBATIM subframe, integer arithmetic only): ``flac_subframe``, ``flac_frame``,
-``flac_encode_ref``, and ``FlacMux``, which finishes the device's subframes into frames on the delivery path."""
+``flac_encode_ref``, and ``FlacMux``, which finishes the device's subframes into frames on the delivery path. And the
+pause control ("PCM pause": the encoded samples cut into slots of 10 ms, each marked silent or not on the device, and
+the host's rule that trims, caps and spaces sentences by whole blocks): ``pause_slots_ref``, ``pause_ref``, ``PauseMux``."""
 from __future__ import annotations
 
 import struct
@@ -59,6 +61,11 @@ FORMANT_G2_MIN, FORMANT_G2_MAX = np.float32(1.0 / 256.0), np.float32(256.0)  # t
 FORMANT_MAX_TERM = 40000  # Fn and Fd of a correction ratio the stage takes: 1 .. 40000, coprime, within 1/2 .. 2
 FORMANT_HISTORY = 1792  # inputs of history a slot keeps between formant calls (7 H)
 FLAC_MAX_K = 14         # the largest Rice parameter the FLAC stage chooses (the escape code is never used)
+PAUSE_THRESH = 103      # a sample louder than this on the 16-bit scale makes its block active (LVX_PAUSE_THRESH): -50 dBFS
+PAUSE_LEAD = 2          # silent blocks kept in front of a sentence's first active one (LVX_PAUSE_LEAD): 20 ms of onset
+PAUSE_TRAIL = 5         # silent blocks kept behind its last active one (LVX_PAUSE_TRAIL): 50 ms of decay
+PAUSE_MS_MAX = 2000     # the largest pause_ms and max_pause_ms
+MAX_PAUSE_MS_MIN = 100  # the smallest max_pause_ms: C >= 10 blocks, so the kept head of a capped run covers the trail
 
 
 def pitch_plan(speed_pct: int, pitch_pct: int) -> Tuple[int, int, int]:
@@ -115,6 +122,10 @@ class AudioFormat:
     # where the formants sit, in percent of the model's own (``formant_ref`` behind the resampling; None: they follow
     # the pitch, no stage)
     formant_pct: Optional[int] = None
+    # the pacing (``pause_ref``): the silence between two sentences in ms, their edges trimmed (None: as rendered), and
+    # the longest silence inside a sentence in ms (None: as rendered)
+    pause_ms: Optional[int] = None
+    max_pause_ms: Optional[int] = None
 
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
@@ -139,6 +150,18 @@ class AudioFormat:
             raise ValueError(f"volume_pct must be an integer in [{VOLUME_MIN}, {VOLUME_MAX}], got {self.volume_pct!r}")
         if self.formant_pct is not None:
             formant_plan(self.speed_pct, self.pitch_pct, self.formant_pct)  # (the three together: the ratio must exist)
+        for name, v, lo in (("pause_ms", self.pause_ms, 0), ("max_pause_ms", self.max_pause_ms, MAX_PAUSE_MS_MIN)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= PAUSE_MS_MAX or v % 10):
+                raise ValueError(f"{name} must be an integer multiple of 10 in [{lo}, {PAUSE_MS_MAX}] or null, got {v!r}")
+        if self.pauses and self.encoding == "flac":
+            raise ValueError("pause_ms / max_pause_ms with encoding 'flac': its frames are cut on the device, per "
+                             "sentence, before the host could trim")
+
+    @property
+    def pauses(self) -> bool:
+        """The format names a pause or a longest pause: the stream's rows pass the pause stage (``pause_slots_ref``)
+        and its body ``PauseMux``."""
+        return self.pause_ms is not None or self.max_pause_ms is not None
 
     @property
     def is_default(self) -> bool:
@@ -151,7 +174,8 @@ class AudioFormat:
         """The samples differ from the codec's (another rate, encoding, speed, pitch, volume or formant, or joined
         dumps): the stream needs the device stage."""
         return (self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
-                or self.pitch_pct != 100 or self.join or self.volume_pct != 100 or self.formant != (1, 1))
+                or self.pitch_pct != 100 or self.join or self.volume_pct != 100 or self.formant != (1, 1)
+                or self.pauses)
 
     @property
     def stretch_pct(self) -> int:
@@ -663,6 +687,177 @@ class FlacMux:
         return out.raw[:n]
 
 
+# ---- the pause rule (include/llmvox.h, "PCM pause"), in numpy: bytes copied, integers compared -----------
+
+def pause_block(sample_rate: int) -> int:
+    """bl = sample_rate / 100: the samples of a block, 10 ms."""
+    if sample_rate not in RATES:
+        raise ValueError(f"unsupported sample rate {sample_rate}")
+    return sample_rate // 100
+
+
+def pause_slot_bytes(fmt: AudioFormat) -> int:
+    """Bytes of one slot of the device's output (LVX_PAUSE_SLOT, ``lvx_pcm_pause_slot``): the 8-byte record and a whole
+    block of the format's samples."""
+    return 8 + pause_block(fmt.sample_rate) * fmt.sample_bytes
+
+
+def pause_blocks_upto(sample_rate: int, T: int, final: bool) -> int:
+    """Blocks of a sentence emitted once T samples are consumed: after a non-final call the complete ones that at
+    least one more sample follows, after a final call all ceil(T / bl)."""
+    bl = pause_block(sample_rate)
+    return 0 if T <= 0 else -(-T // bl) if final else (T - 1) // bl
+
+
+def pause_emitted(sample_rate: int, t0: int, n_in: int, final: bool) -> int:
+    """Blocks a pause call emits for a slot that has consumed t0 inputs of its segment (``lvx_pcm_pause_emitted``)."""
+    if t0 < 0 or n_in < 0:
+        raise ValueError("t0 and n_in must be >= 0")
+    return pause_blocks_upto(sample_rate, t0 + n_in, final) - pause_blocks_upto(sample_rate, t0, False)
+
+
+def pause_loud(y, fmt) -> np.ndarray:
+    """Per encoded sample of y (the dtype of ``fmt``, an AudioFormat or an encoding's name): louder than PAUSE_THRESH
+    on the 16-bit scale. s16le: |q| > 103 (in 32 bits); f32le: |v| > 103 / 32768, a NaN counting as loud; G.711: the
+    s16le test on the decoded sample."""
+    enc = getattr(fmt, "encoding", fmt)
+    y = np.asarray(y, dtype=_SAMPLE_DTYPE[enc])
+    if enc == "f32le":
+        return ~(np.abs(y) <= np.float32(PAUSE_THRESH / 32768.0))
+    q = g711_decode(y, enc) if enc in G711_LAWS else y
+    return np.abs(q.astype(np.int32)) > PAUSE_THRESH
+
+
+def pause_slots_ref(y, fmt: AudioFormat, j0: int, j1: int) -> np.ndarray:
+    """Blocks j0 .. j1 - 1 of the finished sentence y (encoded samples of ``fmt``) as the device writes them
+    (``lvx_pcm_pause``, ``lvx_pause_slots``): slots of ``pause_slot_bytes``, each the record {u16 n, u8 active, u8 last,
+    u32 0} and the block's n samples, the encoding's silence up to bl (uint8)."""
+    y = np.ascontiguousarray(y, dtype=fmt.dtype).reshape(-1)
+    bl, size, bps = pause_block(fmt.sample_rate), pause_slot_bytes(fmt), fmt.sample_bytes
+    blocks = pause_blocks_upto(fmt.sample_rate, y.size, True)
+    if not 0 <= j0 <= j1 <= blocks:
+        raise ValueError(f"blocks {j0} .. {j1} outside the sentence's {blocks}")
+    raw, loud = y.view(np.uint8), pause_loud(y, fmt)
+    out = np.full((j1 - j0) * size, silence_byte(fmt), dtype=np.uint8)
+    for j in range(j0, j1):
+        n, at = min(bl, y.size - j * bl), (j - j0) * size
+        rec = struct.pack("<HBBI", n, int(loud[j * bl:j * bl + n].any()), int(j == blocks - 1), 0)
+        out[at:at + 8] = np.frombuffer(rec, dtype=np.uint8)
+        out[at + 8:at + 8 + n * bps] = raw[j * bl * bps:(j * bl + n) * bps]
+    return out
+
+
+def _pause_blocks(fmt: AudioFormat) -> Tuple[Optional[int], Optional[int]]:
+    """(P, C) of a format in blocks: the gap between sentences and the longest run inside one (None: not named)."""
+    if not fmt.pauses:
+        raise ValueError("the format names neither pause_ms nor max_pause_ms")
+    return (None if fmt.pause_ms is None else fmt.pause_ms // 10,
+            None if fmt.max_pause_ms is None else fmt.max_pause_ms // 10)
+
+
+def pause_ref(sentences, fmt: AudioFormat) -> bytes:
+    """The body of a request whose finished sentences are ``sentences`` (encoded samples of ``fmt`` each, in speaking
+    order), in one shot. P = pause_ms / 10 blocks, C = max_pause_ms / 10 blocks or none. With P: a sentence without an
+    active block delivers nothing and takes part in no gap; any other delivers its blocks from max(first active -
+    PAUSE_LEAD, 0) through min(last active + PAUSE_TRAIL, its last block), and between two delivering sentences come
+    exactly P blocks of the encoding's silence. Without P (only max_pause_ms named) every sentence delivers all its
+    blocks and no gap is inserted. With C, of the blocks a sentence delivers, a run of r > C silent ones between two
+    active ones keeps its first C - 2 and its last 2. The sentence's last block is delivered with its n samples only.
+    No crossfade: both sides of every cut are blocks whose peak is at most PAUSE_THRESH, -50 dBFS."""
+    P, C = _pause_blocks(fmt)
+    bl, bps = pause_block(fmt.sample_rate), fmt.sample_bytes
+    gap = bytes([silence_byte(fmt)]) * (bl * bps)
+    out, spoke = [], False
+    for y in sentences:
+        y = np.ascontiguousarray(y, dtype=fmt.dtype).reshape(-1)
+        K = pause_blocks_upto(fmt.sample_rate, y.size, True)
+        loud = pause_loud(y, fmt)
+        active = [bool(loud[j * bl:(j + 1) * bl].any()) for j in range(K)]
+        on = [j for j in range(K) if active[j]]
+        if P is not None and not on:
+            continue
+        keep = set(range(K)) if P is None else set(range(max(on[0] - PAUSE_LEAD, 0), min(on[-1] + PAUSE_TRAIL, K - 1) + 1))
+        if C is not None:
+            for a, b in zip(on, on[1:]):  # the run a + 1 .. b - 1 between two active blocks
+                if b - a - 1 > C:
+                    keep -= set(range(a + 1 + C - 2, b - 2))
+        if not keep:
+            continue
+        if P is not None and spoke:
+            out.append(gap * P)
+        spoke = True
+        raw = y.view(np.uint8)
+        out.extend(raw[j * bl * bps:(j + 1) * bl * bps].tobytes() for j in sorted(keep))
+    return b"".join(out)
+
+
+class PauseMux:
+    """The host end of a pausing stream: ``push(blob)`` takes the slots one call of the device stage delivered (bytes
+    or uint8, whole slots of ``pause_slot_bytes``, the request's sentences in speaking order) and returns the bytes that
+    may leave now; the concatenation over a request is ``pause_ref`` of its sentences, however the pushes and the
+    device calls were cut. An active block leaves at once, behind the silent blocks kept in front of it; the first
+    PAUSE_TRAIL silent blocks behind an active one (the first C - 2 where no edge is trimmed) leave at once; further
+    silent blocks wait until an active block or the sentence's last one decides their fate; the gap is emitted in
+    front of the next delivering sentence's first block. Only silence ever waits: at most C blocks of it where the rule
+    lets the middle of a long run go (a trimmed format with max_pause_ms), a sentence's silence otherwise."""
+
+    def __init__(self, fmt: AudioFormat):
+        self.P, self.C = _pause_blocks(fmt)
+        self.fmt, self.slot = fmt, pause_slot_bytes(fmt)
+        self.bps = fmt.sample_bytes
+        self.gap = bytes([silence_byte(fmt)]) * (pause_block(fmt.sample_rate) * self.bps)
+        self.spoke = False  # some sentence of the request has delivered
+        self._sentence()
+
+    def _sentence(self):
+        self.seen = False          # the sentence has had an active block
+        self.run = 0               # silent blocks since its last active one
+        self.held: List[bytes] = []  # silent blocks that wait
+
+    def push(self, blob) -> bytes:
+        blob = blob.tobytes() if isinstance(blob, np.ndarray) else bytes(blob)
+        if len(blob) % self.slot:
+            raise ValueError(f"{len(blob)} bytes are no whole slots of {self.slot}")
+        out: List[bytes] = []
+        for at in range(0, len(blob), self.slot):
+            n, active, last, zero = struct.unpack_from("<HBBI", blob, at)
+            if not 1 <= n <= (self.slot - 8) // self.bps or active > 1 or last > 1 or zero or (n * self.bps != self.slot - 8 and not last):
+                raise ValueError("a record that is none of the pause stage's")
+            # (the sentence's last block: its n samples only)
+            self._block(blob[at + 8:at + 8 + (n * self.bps if last else self.slot - 8)], bool(active), bool(last), out)
+        return b"".join(out)
+
+    def _block(self, payload: bytes, active: bool, last: bool, out: List[bytes]):
+        P, C = self.P, self.C
+        at_once = PAUSE_TRAIL if P is not None else C - 2  # silent blocks behind an active one that never wait
+        if active:
+            if not self.seen and P is not None and self.spoke:
+                out.append(self.gap * P)
+            if P is None and self.run > C:  # (the run's first C - 2 have left; a trimmed format pruned as it went)
+                self.held = self.held[-2:]
+            out.extend(self.held)
+            out.append(payload)
+            self.held, self.run, self.seen, self.spoke = [], 0, True, True
+        elif not self.seen:  # in front of the first active block: the last PAUSE_LEAD wait, or nothing is trimmed
+            if P is None:
+                out.append(payload)
+                self.spoke = True
+            else:
+                self.held = (self.held + [payload])[-PAUSE_LEAD:]
+        else:
+            self.run += 1
+            if self.run <= at_once:
+                out.append(payload)
+            else:
+                self.held.append(payload)
+                if P is not None and C is not None and len(self.held) > C - 2 - at_once + 2:
+                    del self.held[C - 2 - at_once]  # (neither of the run's first C - 2 nor of its last 2)
+        if last:
+            if P is None:  # no edge is trimmed: a run that no active block follows is kept whole
+                out.extend(self.held)
+            self._sentence()
+
+
 # ---- the time stretch's rule (include/llmvox.h, "PCM time stretch"), in numpy -------------------------
 
 def stretch_window() -> Tuple[np.ndarray, np.ndarray]:
@@ -1070,7 +1265,7 @@ class StreamRef:
     ``lvx_pcm_stretch`` when the plan has a stretch, then ``lvx_pcm_ratio`` when it has a ratio, then
     ``lvx_pcm_formant`` when it has an envelope correction, then ``lvx_pcm_level`` when it has a volume, then
     ``lvx_pcm_convert`` and, a FLAC format, ``lvx_pcm_flac`` behind it as s16le: the slots of the frames the call
-    emits). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the whole segment; for
+    emits; a pausing format, ``lvx_pcm_pause`` last: the slots of the blocks the call emits). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the whole segment; for
     tests and stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
 
     def __init__(self, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, join_windows=None, level_win=None,
@@ -1106,6 +1301,8 @@ class StreamRef:
         self.lvl_t0 = 0
         self.fq: List[np.ndarray] = []  # the FLAC stage's view: the segment's s16 samples and their count
         self.fq_t0 = 0
+        self.pq: List[np.ndarray] = []  # the pause stage's view: the segment's encoded samples and their count
+        self.pq_t0 = 0
 
     def _ratio(self, x, final: bool) -> np.ndarray:
         m0 = ratio_emitted_upto(self.L, self.M, self.mid_t0, False)
@@ -1173,6 +1370,14 @@ class StreamRef:
             y = flac_slots_ref(np.concatenate(self.fq), rate, j0, j1) if j1 > j0 else np.zeros(0, np.uint8)
         else:
             y = encode_ref(y, self.fmt)
+        if self.fmt.pauses:  # the last stage: the encoded samples cut into blocks of 10 ms, whole slots out
+            j0 = pause_blocks_upto(rate, self.pq_t0, False)
+            j1 = pause_blocks_upto(rate, self.pq_t0 + y.size, final)
+            self.pq.append(y)
+            self.pq_t0 += y.size
+            # (a block that leaves now holds the same samples in the sentence as it stands as in the finished one,
+            # and the sentence's last block leaves only with the final call)
+            y = pause_slots_ref(np.concatenate(self.pq), self.fmt, j0, j1) if j1 > j0 else np.zeros(0, np.uint8)
         if final:
             self.reset()
         return y
@@ -1184,6 +1389,8 @@ __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "re
            "flac_block", "flac_slot_bytes", "flac_frames_upto", "flac_emitted", "flac_frames_of", "flac_subframe",
            "flac_frame", "flac_finish_ref", "flac_stream_header", "flac_encode_ref", "flac_slots_ref", "flac_crc8",
            "flac_crc16", "FlacMux", "FLAC_MAX_K", "BASE_RATE", "HISTORY",
+           "pause_block", "pause_slot_bytes", "pause_blocks_upto", "pause_emitted", "pause_loud", "pause_slots_ref",
+           "pause_ref", "PauseMux", "PAUSE_THRESH", "PAUSE_LEAD", "PAUSE_TRAIL", "PAUSE_MS_MAX", "MAX_PAUSE_MS_MIN",
            "stretch_window", "stretch_ref", "stretch_emitted", "stretch_emitted_upto", "SPEED_MIN", "SPEED_MAX",
            "STRETCH_H", "STRETCH_D", "STRETCH_C", "STRETCH_HISTORY", "pitch_plan", "ratio_design", "ratio_emitted",
            "ratio_emitted_upto", "ratio_ref", "PITCH_MIN", "PITCH_MAX", "RATIO_MAX", "RATIO_HISTORY",

@@ -212,7 +212,7 @@ struct lvx_ctx {
   int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
   // The PCM stages (pcm_host.h: the skeleton of their calls). Each has its device tables, a pool of two buffers per
   // slot [2][max_streams][*_HIST] and, in seg (under mu), the host mirror of every slot's segment.
-  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_FLAC, SEG_FORMANT, SEG_STAGES };
+  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_FLAC, SEG_FORMANT, SEG_PAUSE, SEG_STAGES };
   std::vector<PcmSeg> seg[SEG_STAGES];
   float* pcm_taps = nullptr;  // rate and encoding: the taps of the three resampling rates
   float* pcm_hist = nullptr;
@@ -233,6 +233,7 @@ struct lvx_ctx {
   int16_t* flac_hist = nullptr;  // FLAC: the s16 samples no frame has taken yet
   float* fmt_tab = nullptr;   // formant: the tables [FMT_TABLES]: w, c, the twiddles
   float* fmt_hist = nullptr;
+  unsigned char* pause_hist = nullptr;  // pause: the 1 .. bl encoded samples no block has taken yet (bytes)
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -748,6 +749,9 @@ int lvx_finalize(lvx_ctx* c) {
     HIP_TRY(hipMemcpy(c->fmt_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(c->fmt_hist, 0, (size_t)2 * S * FMT_HIST * 4));
   }
+  // ---- PCM pause (allocated last: every other buffer stays where it was) ----
+  if ((r = c->dalloc(&c->pause_hist, (size_t)2 * S * PAUSE_HIST))) return r;
+  HIP_TRY(hipMemset(c->pause_hist, 0, (size_t)2 * S * PAUSE_HIST));
   for (auto& v : c->seg) v.assign(S, PcmSeg{});
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
@@ -1632,6 +1636,55 @@ int lvx_pcm_flac(lvx_ctx* c, const int16_t* s16, long long in_stride, int B, int
   }
   return pcm_launches<FlacRows>(c, rows, [&](const FlacRows& pk, int nr, int max_out) {
     pcm_launch_flac(pk, nr, max_out, bs, s16, n_in, in_stride, c->flac_hist, out, out_stride, (hipStream_t)stream);
+  });
+}
+
+// ---- PCM pause ----
+int lvx_pcm_pause_emitted(int sample_rate, long long t0, int n_in, int final) {
+  const int bl = pause_block(sample_rate);
+  if (!bl) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate));
+  if (t0 < 0 || n_in < 0) return fail(LVX_E_ARG, "t0 and n_in must be >= 0");
+  return (int)(pause_blocks_upto(bl, t0 + n_in, final != 0) - pause_blocks_upto(bl, t0, false));
+}
+
+int lvx_pcm_pause_slot(int sample_rate, int encoding) {
+  const int bl = pause_block(sample_rate), bps = pcm_sample_bytes(encoding);
+  if (!bl || !bps) return fail(LVX_E_ARG, "an unsupported sample rate or encoding");
+  return pause_slot_bytes(bl, bps);
+}
+
+int lvx_pause_slots(int sample_rate, int encoding, const void* y, long long T, long long j0, long long j1, uint8_t* out,
+                    long long cap) {
+  if (j1 - j0 > 0x7FFFFFFF / pause_slot_bytes(PAUSE_MAX_BL, 4)) return fail(LVX_E_ARG, "too many blocks for one call");
+  const long long r = pause_slots(sample_rate, encoding, y, T, j0, j1, out, cap);
+  if (r == LVX_E_CAPACITY) return fail(LVX_E_CAPACITY, "cap is smaller than the slots");
+  if (r < 0) return fail(LVX_E_ARG, "an unsupported sample rate or encoding, a null pointer, T < 0 or blocks outside the sentence");
+  return (int)r;
+}
+
+int lvx_pcm_pause(lvx_ctx* c, const void* in, long long in_stride, int B, int n_in, const int32_t* slots,
+                  const uint8_t* final_host, int sample_rate, int encoding, void* out, long long out_stride,
+                  int32_t* n_blocks_host, void* stream) {
+  NEED_FINAL(c);
+  const int bl = pause_block(sample_rate), bps = pcm_sample_bytes(encoding);
+  if (!bl) return fail(LVX_E_ARG, "unsupported sample rate " + std::to_string(sample_rate) + " (24000, 16000, 8000, 48000)");
+  if (!bps) return fail(LVX_E_ARG, "encoding must be LVX_PCM_F32LE, LVX_PCM_S16LE, LVX_PCM_ULAW or LVX_PCM_ALAW");
+  if (int r = pcm_args(B, n_in, in, slots && final_host && n_blocks_host ? slots : nullptr, true, out, out_stride)) return r;
+  if ((reinterpret_cast<uintptr_t>(out) & 7) || (out_stride & 7)) return fail(LVX_E_ARG, "out_dev and out_stride_bytes must be multiples of 8");
+  if ((reinterpret_cast<uintptr_t>(in) % bps) || in_stride < 0 || (in_stride % bps))
+    return fail(LVX_E_ARG, "in_dev and in_stride_bytes must be multiples of the sample's bytes");
+  std::vector<PauseRow> rows;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    bool capacity = false;
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_PAUSE], PAUSE_HIST, B, n_in, slots, final_host, n_blocks_host, pause_key(sample_rate, encoding), true,
+        [](long long k) { return std::to_string(k >> 8) + " Hz, encoding " + std::to_string(k & 0xff); }, rows,
+        [&](const PcmCall& q, PauseRow& r) { return plan_pause(q, n_in, sample_rate, encoding, in_stride, out_stride, &capacity, r); });
+    if (!e.empty()) return fail(capacity ? LVX_E_CAPACITY : LVX_E_ARG, e);
+  }
+  return pcm_launches<PauseRows>(c, rows, [&](const PauseRows& pk, int nr, int max_out) {
+    pcm_launch_pause(pk, nr, max_out, bl, encoding, in, n_in, in_stride, c->pause_hist, out, out_stride, (hipStream_t)stream);
   });
 }
 

@@ -294,5 +294,8 @@ void pcm_launch_formant(const PcmRows& rows, int n_rows, int max_out, int Fn, in
                         const float* tab, float* hist, float* out, long long out_stride, hipStream_t s);
 void pcm_launch_flac(const FlacRows& rows, int n_rows, int max_frames, int bs, const int16_t* s16, int n_in,
                      long long in_stride, int16_t* hist, void* out, long long out_stride, hipStream_t s);
+// bl: the block of the rate; enc: LVX_PCM_*; in: rows of that encoding; hist: the byte pool [2][slots][PAUSE_HIST]
+void pcm_launch_pause(const PauseRows& rows, int n_rows, int max_blocks, int bl, int enc, const void* in, int n_in,
+                      long long in_stride, unsigned char* hist, void* out, long long out_stride, hipStream_t s);
 
 }  // namespace lvx

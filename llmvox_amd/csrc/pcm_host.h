@@ -1,8 +1,9 @@
 // Host side of the PCM stages (include/llmvox.h: "PCM output stage", "PCM time stretch", "PCM pitch shift", "PCM dump
-// join", "PCM level", "PCM formant", "PCM G.711", "PCM FLAC"): the stages' constants and kernel row packets, the tables and streaming
+// join", "PCM level", "PCM formant", "PCM G.711", "PCM FLAC", "PCM pause"): the stages' constants and kernel row packets, the tables and streaming
 // counts of llmvox.h's rules in double, the G.711 companding, the FLAC stage's selection arithmetic and the host side of
 // its frames, and the one skeleton every stage's entry point runs (lvx_api.cpp). No HIP header and no device:
-// tests/host/pcm_stage_check.cpp, g711_check.cpp, flac_check.cpp and formant_check.cpp drive all of it with the system compiler.
+// tests/host/pcm_stage_check.cpp, g711_check.cpp, flac_check.cpp, formant_check.cpp and pause_check.cpp drive all of it
+// with the system compiler.
 #pragma once
 #include <stdint.h>
 
@@ -107,6 +108,23 @@ struct FlacRow {
 };
 struct FlacRows {
   FlacRow r[PCM_ROWS];
+};
+
+// PCM pause: the encoded rows cut into blocks of 10 ms, one slot (a record and the block's bytes) each
+constexpr int PAUSE_MAX_BL = 480;            // the block at 48 kHz, the largest
+constexpr int PAUSE_HIST = PAUSE_MAX_BL * 4;  // bytes a slot keeps between calls: the 1 .. bl samples no block has taken yet
+struct PauseRow {
+  long long t0;  // inputs of the slot's segment consumed before this call
+  long long j0;  // blocks of the segment emitted before this call = index of the call's first block
+  int n_out;     // blocks of this call
+  int last_n;    // samples of the call's last block (every block before it has bl)
+  int hist_in;   // byte offset of the slot's history [PAUSE_HIST] (inputs t0 - bl .. t0 - 1 at its front) in the pool
+  int hist_out;  // where the history after this call goes (the slot's other buffer); -1: none kept
+  int row;       // row of in / out
+  int last;      // 1: the call is final, its last block is the sentence's last
+};
+struct PauseRows {
+  PauseRow r[PCM_ROWS];
 };
 
 // PCM formant: the spectral-envelope correction. The rows travel as PcmRows: t0 the inputs consumed before the call,
@@ -365,6 +383,65 @@ inline int g711_decode(int encoding, const uint8_t* in, long long n, int16_t* ou
 // bytes of one output sample of an encoding lvx_pcm_convert takes; 0: not one
 constexpr int pcm_sample_bytes(int encoding) {
   return encoding == LVX_PCM_F32LE ? 4 : encoding == LVX_PCM_S16LE ? 2 : is_g711(encoding) ? 1 : 0;
+}
+
+// ---- PCM pause: the blocks, the mark and the slots (llmvox.h) ----
+// The constexpr functions are the one statement of the mark that pcm_pause_kernel and lvx_pause_slots both call.
+constexpr int pause_block(int rate) {  // bl = rate / 100 (10 ms); 0: not a rate of the stage
+  return rate == 8000 || rate == 16000 || rate == 24000 || rate == 48000 ? rate / 100 : 0;
+}
+constexpr int pause_slot_bytes(int bl, int bps) { return 8 + bl * bps; }
+static_assert(pause_slot_bytes(pause_block(8000), 1) == LVX_PAUSE_SLOT(8000, 1) && pause_slot_bytes(PAUSE_MAX_BL, 4) % 8 == 0, "");
+// blocks of a segment emitted once T inputs are consumed: after a non-final call the complete ones that at least one
+// more sample follows; a final call adds the rest, so the sentence's last block always leaves with the final call
+constexpr long long pause_blocks_upto(int bl, long long T, bool final) {
+  return T <= 0 ? 0 : final ? (T + bl - 1) / bl : (T - 1) / bl;
+}
+constexpr bool pause_loud_s16(int q) { return (q < 0 ? -q : q) > LVX_PAUSE_THRESH; }  // (in 32 bits: -32768 is loud)
+// 103 / 32768 = 0.003143310546875 is exact in fp32, the bits 0x3B4E0000; of two fp32 that are no NaN the one of the
+// larger magnitude has the larger bits below the sign, and a NaN's are above every number's
+constexpr uint32_t PAUSE_THRESH_F32_BITS = 0x3B4E0000u;
+// the sample whose little-endian bits are `bits` (the low 8 * bps of them) is louder than the threshold
+template <int ENC> constexpr bool pause_loud(uint32_t bits) {
+  if (ENC == LVX_PCM_F32LE) return (bits & 0x7FFFFFFFu) > PAUSE_THRESH_F32_BITS;  // |v| > 103 / 32768, or a NaN
+  if (ENC == LVX_PCM_S16LE) return pause_loud_s16((int16_t)(uint16_t)bits);
+  return pause_loud_s16(ENC == LVX_PCM_ULAW ? g711_ulaw_linear((int)(bits & 0xFFu)) : g711_alaw_linear((int)(bits & 0xFFu)));
+}
+constexpr int pause_silence(int encoding) { return encoding == LVX_PCM_ULAW ? 0xFF : encoding == LVX_PCM_ALAW ? 0xD5 : 0; }
+inline bool pause_loud_of(int encoding, uint32_t bits) {
+  return encoding == LVX_PCM_F32LE   ? pause_loud<LVX_PCM_F32LE>(bits)
+         : encoding == LVX_PCM_S16LE ? pause_loud<LVX_PCM_S16LE>(bits)
+         : encoding == LVX_PCM_ULAW  ? pause_loud<LVX_PCM_ULAW>(bits)
+                                     : pause_loud<LVX_PCM_ALAW>(bits);
+}
+
+// lvx_pause_slots: the slots of blocks j0 .. j1 - 1 of the finished sentence y (T encoded samples), serially. Their
+// bytes, or LVX_E_ARG (a bad rate or encoding, a null pointer, T < 0, blocks outside 0 <= j0 <= j1 <= ceil(T / bl)) or
+// LVX_E_CAPACITY (cap smaller than the slots; nothing is written)
+inline long long pause_slots(int rate, int encoding, const void* y, long long T, long long j0, long long j1, uint8_t* out,
+                             long long cap) {
+  const int bl = pause_block(rate), bps = pcm_sample_bytes(encoding);
+  if (!bl || !bps || T < 0 || cap < 0 || j0 < 0 || j1 < j0 || j1 > pause_blocks_upto(bl, T, true)) return LVX_E_ARG;
+  if (j1 > j0 && (!y || !out)) return LVX_E_ARG;
+  const long long slot = pause_slot_bytes(bl, bps);
+  if ((j1 - j0) * slot > cap) return LVX_E_CAPACITY;
+  const uint8_t* src = static_cast<const uint8_t*>(y);
+  const long long blocks = pause_blocks_upto(bl, T, true);
+  for (long long j = j0; j < j1; ++j) {
+    uint8_t* s = out + (j - j0) * slot;
+    const int n = (int)std::min<long long>(bl, T - j * bl);
+    bool active = false;
+    for (int i = 0; i < n; ++i) {
+      uint32_t bits = 0;
+      for (int k = 0; k < bps; ++k) bits |= (uint32_t)src[((size_t)j * bl + i) * bps + k] << (8 * k);
+      active = active || pause_loud_of(encoding, bits);
+    }
+    const uint8_t rec[8] = {(uint8_t)n, (uint8_t)(n >> 8), (uint8_t)active, (uint8_t)(j == blocks - 1), 0, 0, 0, 0};
+    std::copy(rec, rec + 8, s);
+    std::copy(src + (size_t)j * bl * bps, src + ((size_t)j * bl + n) * bps, s + 8);
+    std::fill(s + 8 + (size_t)n * bps, s + slot, (uint8_t)pause_silence(encoding));
+  }
+  return (j1 - j0) * slot;
 }
 
 // ---- PCM FLAC: the frame cuts, the subframe's selection arithmetic and the host side of a frame (llmvox.h) ----
@@ -751,6 +828,23 @@ inline std::string plan_flac(const PcmCall& c, int n_in, int rate, long long in_
   if ((j1 - j0) * flac_slot_bytes(bs) > out_stride) return stride_msg("out_stride_bytes", out_stride, (j1 - j0) * flac_slot_bytes(bs));
   const long long last = c.final ? t0 + n_in - flac_full_frames(bs, t0 + n_in) * bs : bs;
   r = FlacRow{t0, j0, (int)(j1 - j0), (int)last, c.cur, n_in > 0 && !c.final ? c.other : -1, c.row};
+  return {};
+}
+
+// the key is (rate, encoding); every call that brings samples keeps the ones no block has taken (so it turns the
+// buffers). *capacity: the error is out_stride's (LVX_E_CAPACITY, not LVX_E_ARG)
+constexpr long long pause_key(int rate, int encoding) { return ((long long)rate << 8) | encoding; }
+inline std::string plan_pause(const PcmCall& c, int n_in, int rate, int encoding, long long in_stride, long long out_stride,
+                              bool* capacity, PauseRow& r) {
+  const int bl = pause_block(rate), bps = pcm_sample_bytes(encoding);
+  if ((long long)n_in * bps > in_stride) return stride_msg("in_stride_bytes", in_stride, (long long)n_in * bps);
+  const long long t0 = c.seg.t0, j0 = pause_blocks_upto(bl, t0, false), j1 = pause_blocks_upto(bl, t0 + n_in, c.final);
+  if ((j1 - j0) * pause_slot_bytes(bl, bps) > out_stride) {
+    *capacity = true;
+    return stride_msg("out_stride_bytes", out_stride, (j1 - j0) * pause_slot_bytes(bl, bps));
+  }
+  const long long last = c.final && j1 > 0 ? t0 + n_in - (j1 - 1) * bl : bl;
+  r = PauseRow{t0, j0, (int)(j1 - j0), (int)last, c.cur, n_in > 0 && !c.final ? c.other : -1, c.row, c.final ? 1 : 0};
   return {};
 }
 

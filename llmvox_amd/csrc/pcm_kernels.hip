@@ -12,8 +12,11 @@
 // another volume than 100. And, behind the rate conversion's s16le rows, the lossless compressed output
 // ("PCM FLAC"): one FLAC subframe a workgroup, launched only for a stream that asked for "flac". And the
 // formant control between the pitch control and the volume control ("PCM formant"): a short-time Fourier
-// correction of the spectral envelope in LDS, launched only for a stream that named a formant.
+// correction of the spectral envelope in LDS, launched only for a stream that named a formant. And, last of all, the
+// marks of the pause control ("PCM pause"): the encoded rows cut into slots of 10 ms, each marked silent or not,
+// launched only for a stream that named a pause.
 #include <algorithm>
+#include <type_traits>
 
 #include "lvx_internal.h"
 
@@ -942,7 +945,130 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_formant_kernel(PcmRows rows, 
   }
 }
 
+// ---- PCM pause (llmvox.h, "PCM pause"): one slot a block of 10 ms, a copy and one vote ----
+// Grid (groups of `group` blocks, rows of the launch). Workgroup (x, y) writes the slots of blocks [x group,
+// (x + 1) group) of row y's call, a wave a block at a time: a lane moves 16 bytes of the payload, the unit u of the
+// block, from the call's row (or, the call's first block, sample by sample from the slot's kept ones) to the slot,
+// tests its samples against the threshold (pcm_host.h's pause_loud, the one lvx_pause_slots runs), and the block's mark
+// is one wave vote; lane 0 writes the record. No LDS and no atomics. A slot starts on an 8-byte boundary, so a payload
+// unit is stored as 16 bytes where its address allows and as two 8-byte halves where not. A block's first sample sits
+// wherever the segment's count puts it in the row: a unit whose address is a multiple of 16 is one 16-byte load; any
+// other is the five aligned words around it, shifted into place (the fifth only where the shift needs it and the row
+// still holds it); a unit that reaches into the kept samples, past the block's n samples or before the row's first
+// word is assembled sample by sample, the encoding's silence behind the n. Block (0, y) also writes the slot's next
+// history: the call's last bl samples.
+constexpr int PAUSE_WAVES = PCM_THREADS / 64;
+constexpr int PAUSE_WGS = 1024;  // workgroups a launch aims at: four a CU
+
+template <int ENC>
+__global__ __launch_bounds__(PCM_THREADS) void pcm_pause_kernel(PauseRows rows, int bl, const unsigned char* __restrict__ in,
+                                                                int n_in, long long in_stride, unsigned char* hist,
+                                                                unsigned char* __restrict__ out, long long out_stride,
+                                                                int group) {
+  constexpr int BPS = pcm_sample_bytes(ENC), SPU = 16 / BPS;  // bytes of a sample, samples of a 16-byte unit
+  constexpr uint32_t MASK = BPS == 4 ? 0xFFFFFFFFu : (1u << (8 * (BPS & 3))) - 1u;
+  constexpr uint32_t SIL = (uint32_t)pause_silence(ENC);
+  using T = typename std::conditional<BPS == 4, uint32_t, typename std::conditional<BPS == 2, uint16_t, uint8_t>::type>::type;
+  const PauseRow r = rows.r[blockIdx.y];
+  const unsigned char* __restrict__ xb = in + (size_t)r.row * (size_t)in_stride;
+  const T* __restrict__ x = reinterpret_cast<const T*>(xb);
+  const T* kept = reinterpret_cast<const T*>(hist + r.hist_in);  // inputs t0 - bl .. t0 - 1
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
+  auto sample = [&](long long g) -> uint32_t {  // segment input g, t0 - bl <= g < t1, from the row or the kept ones
+    return g >= r.t0 ? x[g - r.t0] : kept[bl - (int)(r.t0 - g)];
+  };
+  if (blockIdx.x == 0 && r.hist_out >= 0) {
+    T* next = reinterpret_cast<T*>(hist + r.hist_out);
+    for (int i = tid; i < bl; i += PCM_THREADS) {
+      const long long g = t1 - bl + i;
+      next[i] = g >= 0 ? (T)sample(g) : (T)0;
+    }
+  }
+
+  const int lb0 = blockIdx.x * group, lb1 = min(lb0 + group, r.n_out);
+  const int slot_bytes = pause_slot_bytes(bl, BPS), units = bl * BPS / 16;
+  unsigned char* orow = out + (size_t)r.row * (size_t)out_stride;
+  for (int f = lb0 + wave; f < lb1; f += PAUSE_WAVES) {
+    const int n = f == r.n_out - 1 ? r.last_n : bl;  // samples of the block
+    const long long s0 = (r.j0 + f) * bl;            // its first sample in the segment
+    unsigned char* slot = orow + (size_t)f * (size_t)slot_bytes;
+    bool loud = false;
+    for (int u = lane; u < units; u += 64) {
+      const int i0 = u * SPU;  // the unit's first sample within the block
+      const long long g0 = s0 + i0;
+      uint32_t w[4] = {0u, 0u, 0u, 0u};
+      bool done = false;
+      if (g0 >= r.t0 && i0 + SPU <= n) {  // the whole unit lies in the call's row
+        const unsigned char* p = xb + (size_t)(g0 - r.t0) * BPS;
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+        const int sh = (int)(a & 3);
+        const uint32_t* pa = reinterpret_cast<const uint32_t*>(p - sh);
+        if ((a & 15) == 0) {
+          const uint4 v = *reinterpret_cast<const uint4*>(p);
+          w[0] = v.x, w[1] = v.y, w[2] = v.z, w[3] = v.w;
+          done = true;
+        } else if (sh == 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) w[k] = pa[k];
+          done = true;
+        } else if (reinterpret_cast<const unsigned char*>(pa) >= xb &&
+                   reinterpret_cast<const unsigned char*>(pa) + 20 <= xb + (size_t)n_in * BPS) {
+          uint32_t d[5];
+#pragma unroll
+          for (int k = 0; k < 5; ++k) d[k] = pa[k];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) w[k] = (uint32_t)((((unsigned long long)d[k + 1] << 32) | d[k]) >> (8 * sh));
+          done = true;
+        }
+      }
+      if (!done) {
+#pragma unroll
+        for (int e = 0; e < SPU; ++e) {
+          const uint32_t bits = i0 + e < n ? sample(g0 + e) : SIL;
+          w[e * BPS / 4] |= bits << (8 * ((e * BPS) & 3));
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < SPU; ++e) loud = loud || pause_loud<ENC>((w[e * BPS / 4] >> (8 * ((e * BPS) & 3))) & MASK);
+      unsigned char* o = slot + 8 + (size_t)u * 16;
+      if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+        *reinterpret_cast<uint4*>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+      } else {
+        *reinterpret_cast<uint2*>(o) = make_uint2(w[0], w[1]);
+        *reinterpret_cast<uint2*>(o + 8) = make_uint2(w[2], w[3]);
+      }
+    }
+    const bool active = __any(loud ? 1 : 0) != 0;  // the block's mark: one vote of the wave
+    if (lane == 0) {
+      const bool last = r.last != 0 && f == r.n_out - 1;
+      *reinterpret_cast<uint2*>(slot) = make_uint2((uint32_t)n | (active ? 1u << 16 : 0u) | (last ? 1u << 24 : 0u), 0u);
+    }
+  }
+}
+
+template <int ENC>
+void launch_pause(dim3 grid, const PauseRows& rows, int bl, const void* in, int n_in, long long in_stride, unsigned char* hist,
+                  void* out, long long out_stride, int group, hipStream_t s) {
+  pcm_pause_kernel<ENC><<<grid, PCM_THREADS, 0, s>>>(rows, bl, (const unsigned char*)in, n_in, in_stride, hist,
+                                                     (unsigned char*)out, out_stride, group);
+}
+
 }  // namespace
+
+void pcm_launch_pause(const PauseRows& rows, int n_rows, int max_blocks, int bl, int enc, const void* in, int n_in,
+                      long long in_stride, unsigned char* hist, void* out, long long out_stride, hipStream_t s) {
+  // the smallest group, a whole number of blocks a wave, at which the launch has at most PAUSE_WGS workgroups
+  const int per_row = std::max(1, PAUSE_WGS / n_rows);
+  const int group = (std::max(1, (max_blocks + per_row - 1) / per_row) + PAUSE_WAVES - 1) / PAUSE_WAVES * PAUSE_WAVES;
+  const dim3 grid((unsigned)std::max(1, (max_blocks + group - 1) / group), (unsigned)n_rows);
+  switch (enc) {
+    case LVX_PCM_S16LE: launch_pause<LVX_PCM_S16LE>(grid, rows, bl, in, n_in, in_stride, hist, out, out_stride, group, s); break;
+    case LVX_PCM_ULAW: launch_pause<LVX_PCM_ULAW>(grid, rows, bl, in, n_in, in_stride, hist, out, out_stride, group, s); break;
+    case LVX_PCM_ALAW: launch_pause<LVX_PCM_ALAW>(grid, rows, bl, in, n_in, in_stride, hist, out, out_stride, group, s); break;
+    default: launch_pause<LVX_PCM_F32LE>(grid, rows, bl, in, n_in, in_stride, hist, out, out_stride, group, s); break;
+  }
+}
 
 void pcm_launch_formant(const PcmRows& rows, int n_rows, int max_out, int Fn, int Fd, const float* pcm, int n_in,
                         const float* tab, float* hist, float* out, long long out_stride, hipStream_t s) {

@@ -517,7 +517,10 @@ class Engine:
         L / M (lvx_pcm_ratio), the envelope correction by the plan's Fn / Fd (lvx_pcm_formant), the gain and limiter at
         volume_pct (lvx_pcm_level), the rate and the encoding (lvx_pcm_convert). A "flac" format runs that last stage as
         s16le and one more behind it (lvx_pcm_flac): its rows are uint8, whole slots of LVX_FLAC_SLOT bytes (a record
-        and a subframe each; ``audio.FlacMux`` makes them frames), and counts[b] is their bytes. Rows may leave a stage with different counts: they pass the next one grouped by count.
+        and a subframe each; ``audio.FlacMux`` makes them frames), and counts[b] is their bytes. A format that
+        ``pauses`` (``pause_ms`` / ``max_pause_ms``) runs one more stage behind the format's encoded rows (lvx_pcm_pause):
+        its rows are uint8 too, whole slots of LVX_PAUSE_SLOT bytes (a record and a block of 10 ms each;
+        ``audio.PauseMux`` trims and spaces by them), and counts[b] is their bytes. Rows may leave a stage with different counts: they pass the next one grouped by count.
         Asynchronous on the current stream; a slot's calls must be issued in order on one stream."""
         stretch_pct, (L, M), vol, (Fn, Fd) = fmt.stretch_pct, fmt.ratio, fmt.volume_pct, fmt.formant
         slots, finals = [int(s) for s in slots], [bool(f) for f in finals]
@@ -548,6 +551,14 @@ class Engine:
                 return out, [n * slot for n in frames]
             stages.append(flac)
         dtype = _PCM_ENCODINGS[fmt.encoding][1]
+        if fmt.pauses:  # the last stage, behind the format's encoded rows: whole slots, counted in bytes
+            slot = 8 + fmt.sample_rate // 100 * fmt.sample_bytes
+
+            def pause(sub, sl, fl):
+                out, blocks = self.pcm_pause(sub, sl, fl, fmt)
+                return out, [n * slot for n in blocks]
+            stages.append(pause)
+            dtype = torch.uint8
 
         def run(i, sub, sl, fl):  # stage i and, grouped by what it hands on, the stages behind it
             out, cnt = stages[i](sub, sl, fl)
@@ -606,6 +617,35 @@ class Engine:
         out = torch.empty(B, width, device=self.device, dtype=torch.uint8)
         _lib.check(self.lib.lvx_pcm_flac(self.h, _ptr(s16) if n_in else None, stride, B, n_in, sl, fl, int(sample_rate),
                                          _ptr(out), width, cnt, self.stream_handle()))
+        return out, list(cnt)
+
+    def pcm_pause(self, rows: Optional[torch.Tensor], slots, finals, fmt):
+        """The pause stage alone (lvx_pcm_pause): ``rows`` (a device tensor [B, n_in] of the samples ``fmt`` encodes to,
+        what ``pcm_convert`` writes for it: float32, int16 or uint8; rows may be strided; None or n_in 0: flush only)
+        continue the pause segments of ``slots``; a true ``finals[b]`` emits the sentence's last block and ends the
+        segment. Returns (out, blocks): a device uint8 tensor [B, width] whose row b holds blocks[b] slots of
+        LVX_PAUSE_SLOT bytes, each the record {u16 n, u8 active, u8 last, u32 0} and the block's samples. The stage
+        holds back 1 .. bl samples until the final call. Asynchronous on the current stream; a slot's calls must be
+        issued in order on one stream."""
+        slots = [int(s) for s in slots]
+        enc, dtype = _PCM_ENCODINGS[fmt.encoding]
+        if enc is None:
+            raise ValueError(f"the pause stage takes no {fmt.encoding!r} rows")
+        B, n_in, stride, bps = len(slots), 0, 0, fmt.sample_bytes
+        if rows is not None and rows.shape[1]:
+            if rows.shape[0] != B or rows.dtype != dtype or rows.device != self.device:
+                raise ValueError(f"rows must be a {dtype} [{B}, n_in] tensor on {self.device}")
+            if rows.stride(1) != 1 or (B > 1 and rows.stride(0) < rows.shape[1]):
+                rows = rows.contiguous()
+            n_in, stride = int(rows.shape[1]), bps * int(rows.stride(0) if B > 1 else rows.shape[1])
+        sl, fl = (ctypes.c_int32 * B)(*slots), (ctypes.c_uint8 * B)(*[1 if f else 0 for f in finals])
+        cnt = (ctypes.c_int32 * B)()
+        bl = fmt.sample_rate // 100
+        # (a call emits at most the blocks of its own samples and the kept bl; a slot is a multiple of 8 bytes)
+        width = ((n_in + bl - 1) // bl + 1) * (8 + bl * bps)
+        out = torch.empty(B, width, device=self.device, dtype=torch.uint8)
+        _lib.check(self.lib.lvx_pcm_pause(self.h, _ptr(rows) if n_in else None, stride, B, n_in, sl, fl, fmt.sample_rate, enc,
+                                          _ptr(out), width, cnt, self.stream_handle()))
         return out, list(cnt)
 
     def _pcm_resample(self, pcm: Optional[torch.Tensor], slots, finals, fmt):

@@ -322,7 +322,9 @@ class TTSService:
         frames of that duration, the last one filled with the encoding's silence (``audio.frame_chunks``); None:
         the scheduler's chunks as they come. A "flac" session: the stream header first, then every chunk (the device's
         slots of subframes) made frames here, where the speaking order and so each frame's sample number is known
-        (``audio.FlacMux``); FLAC frames have no fixed size, so ``frame_ms`` with it is a ValueError."""
+        (``audio.FlacMux``); FLAC frames have no fixed size, so ``frame_ms`` with it is a ValueError. A session whose
+        format ``pauses``: every chunk (the device's slots of 10 ms blocks) passes ``audio.PauseMux`` here, behind the
+        WAV header and in front of the framing, so ``frame_ms`` cuts what the trimming left."""
         w = session.worker
         flac = session.audio is not None and session.audio.encoding == "flac"
         if flac and frame_ms is not None:
@@ -338,6 +340,9 @@ class TTSService:
                 mux = FlacMux(session.audio.sample_rate)
                 yield mux.header()
                 body = (frames for frames in map(mux.push, body) if frames)
+            if session.audio is not None and session.audio.pauses:
+                from .audio import PauseMux
+                body = (kept for kept in map(PauseMux(session.audio).push, body) if kept)
             if frame_ms is not None:
                 from .audio import AudioFormat, frame_chunks
                 body = frame_chunks(body, session.audio if session.audio is not None else AudioFormat(), frame_ms)
@@ -420,7 +425,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
                min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0,
                join: bool = False, volume: float = 1.0, frame_ms: Optional[int] = None,
-               formant: Optional[float] = None):
+               formant: Optional[float] = None, pause_ms: Optional[int] = None, max_pause_ms: Optional[int] = None):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -464,6 +469,13 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     included: 422) cuts the body behind the WAV header, on the host, into chunks of whole frames of that duration, the
     last frame filled with the encoding's silence (``audio.frame_chunks``); it reaches ``service.chunks`` as a keyword,
     never ``submit``; the response carries it in ``X-Audio-Frame-Ms`` (0 without).
+    ``pause_ms`` (an integer multiple of 10 in 0 .. 2000; null or absent: the server's default, which is none) is the
+    pacing between sentences: every sentence's leading and trailing silence is trimmed to 20 ms of onset and 50 ms of
+    decay and exactly pause_ms of silence is put between two sentences; ``max_pause_ms`` (an integer multiple of 10 in
+    100 .. 2000) caps a silence inside a sentence. The device marks every 10 ms block of the encoded samples silent or
+    not and the host trims by whole blocks (``audio.pause_ref``), which holds back up to 10 ms of every sentence until
+    its end; a bool, a float, a value out of range or either field with "flac": 422; the response carries them in
+    ``X-Audio-Pause`` / ``X-Audio-Max-Pause`` ("none" where absent).
     The reference's /voicechat, /multimodalchat and /vlmschat differ from /tts only in the
     producer (ASR / multimodal LLM, out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
@@ -478,7 +490,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     extra_defaults = {"top_p": top_p, "min_p": min_p, "repetition_penalty": repetition_penalty,
                       "repetition_window": repetition_window}
     default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join,
-                                volume_pct_of(volume), formant_pct_of(formant))
+                                volume_pct_of(volume), formant_pct_of(formant), pause_ms, max_pause_ms)
     default_frame_ms = frame_ms_of(frame_ms)
     if default_frame_ms is not None and default_audio.encoding == "flac":
         raise ValueError("frame_ms with encoding 'flac': FLAC frames have no fixed byte size")
@@ -501,6 +513,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         volume: Optional[Union[StrictInt, StrictFloat]] = None  # (strict: true / false are not numbers here)
         formant: Optional[Union[StrictInt, StrictFloat]] = None  # (null: the server's default)
         frame_ms: Any = None  # (checked by frame_ms_of: an integer of audio.FRAME_MS, no bool, no float)
+        pause_ms: Any = None  # (checked by AudioFormat, as max_pause_ms is: integers, no bool, no float)
+        max_pause_ms: Any = None
 
     def audio_of(request):
         """The request's AudioFormat (the defaults for the fields it does not name)."""
@@ -513,7 +527,9 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                default_audio.join if request.join is None else request.join,
                                default_audio.volume_pct if request.volume is None else volume_pct_of(request.volume),
                                default_audio.formant_pct if request.formant is None
-                               else formant_pct_of(request.formant))
+                               else formant_pct_of(request.formant),
+                               default_audio.pause_ms if request.pause_ms is None else request.pause_ms,
+                               default_audio.max_pause_ms if request.max_pause_ms is None else request.max_pause_ms)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -560,7 +576,7 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         if ms is not None and fmt.encoding == "flac":
             raise HTTPException(status_code=422, detail="frame_ms with encoding 'flac': FLAC frames have no fixed byte size")
         kw = {} if sp is None else {"sampling": sp}
-        if not fmt.is_default:  # (a default request reaches submit exactly as it always did)
+        if not fmt.is_default or fmt.pauses:  # (a default request reaches submit exactly as it always did)
             kw["audio"] = fmt
         try:
             session = service.submit(request.text, **kw)
@@ -575,7 +591,10 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                           "X-Audio-Join": "1" if fmt.join else "0",
                                           "X-Audio-Volume": f"{fmt.volume_pct / 100:.2f}",
                                           "X-Audio-Formant": f"{fmt.formant_moved:.4f}",
-                                          "X-Audio-Frame-Ms": str(ms or 0)})
+                                          "X-Audio-Frame-Ms": str(ms or 0),
+                                          "X-Audio-Pause": "none" if fmt.pause_ms is None else str(fmt.pause_ms),
+                                          "X-Audio-Max-Pause": "none" if fmt.max_pause_ms is None
+                                          else str(fmt.max_pause_ms)})
 
     @app.get("/health")
     def health():
@@ -629,6 +648,12 @@ def arg_parser():
     ap.add_argument("--formant", type=float, default=None,
                     help="formant factor of requests that name none (0.5 .. 2.0; 1.0: the model's own timbre at any "
                          "pitch; default: none, the formants follow the pitch)")
+    ap.add_argument("--pause-ms", type=int, default=None,
+                    help="silence between two sentences of requests that name none, in ms (a multiple of 10 in 0 .. 2000; "
+                         "their edges are trimmed; default: none, the sentences as rendered)")
+    ap.add_argument("--max-pause-ms", type=int, default=None,
+                    help="longest silence inside a sentence of requests that name none, in ms (a multiple of 10 in "
+                         "100 .. 2000; default: none)")
     ap.add_argument("--join", action="store_true",
                     help="click-free dump joins for requests that do not name `join` (context frames and a crossfade)")
     return ap
@@ -639,7 +664,8 @@ def app_options(a) -> dict:
     return dict(temperature=a.temperature, top_k=a.top_k, sample_rate=a.sample_rate, encoding=a.encoding,
                 container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
                 repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch,
-                join=a.join, volume=a.volume, frame_ms=a.frame_ms, formant=a.formant)
+                join=a.join, volume=a.volume, frame_ms=a.frame_ms, formant=a.formant, pause_ms=a.pause_ms,
+                max_pause_ms=a.max_pause_ms)
 
 
 def main(argv=None):

@@ -528,7 +528,7 @@ class _PcmPass:
     must reach the engine in dump order, whatever order the codec groups are decoded in, and no call may
     name a slot twice: ``run()`` converts, in rounds, every dump that is the next one of its stream and
     whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch, join, volume,
-    formant), and leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
+    formant, pauses or not), and leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
 
     def __init__(self, sched, dumps, finals):
         self.sched, self.dumps, self.finals = sched, dumps, finals
@@ -562,7 +562,7 @@ class _PcmPass:
                     continue
                 buckets.setdefault((id(self.where[i][0]), st.audio.sample_rate, st.audio.encoding,
                                     st.audio.speed_pct, st.audio.pitch_pct, st.audio.join, st.audio.volume_pct,
-                                    st.audio.formant_pct),
+                                    st.audio.formant_pct, st.audio.pauses),
                                    []).append(i)
             if not buckets:
                 return calls
@@ -677,7 +677,9 @@ class FusedScheduler:
         int16 or, G.711, uint8 arrays with ``to_bytes=False``). None (or 24 kHz f32le): today's items, and the engine's
         ``pcm_*`` are never called. A format with ``join``: every dump of a sentence after its first is decoded
         with context in front, the last min(16, frames of the sentence dumped so far, max_codec_frames - the
-        dump's length) tokens dumped before it (``_join_row``), and the output stage crossfades the seam."""
+        dump's length) tokens dumped before it (``_join_row``), and the output stage crossfades the seam. A format
+        that ``pauses``: the items are uint8, whole slots of the pause stage (``audio.pause_slots_ref``), which
+        ``audio.PauseMux`` turns into the paced samples where the speaking order is known."""
         if sampling is not None and not sampling.temperature > 0:
             sampling = None
         if sampling is not None and not hasattr(self.engine, "set_sampling"):
