@@ -405,9 +405,9 @@ int lvx_stream_position(lvx_ctx* ctx, int slot, int* pos_out, void* stream);
  *                     0: the three launches (bit-identical: tests/test_gpu_la_fused.py). The per-op entry
  *                     points (lvx_probe_kernel, lvx_attn_probe, lvx_ar_ops) plan without the tables, so
  *                     they go on running and timing the separate kernels whatever this option says;
- *   "fmt_group"    0: lvx_pcm_formant chooses, per launch, how many output hop blocks a workgroup writes (few
- *                     in a small launch, up to 32 in a large one); 1 .. 32: that many (bit-identical at every
- *                     value: tests/test_gpu_pcm_formant.py). */
+ *   "fmt_group"    0: lvx_pcm_formant and lvx_pcm_mark choose, per launch, how many output hop blocks a workgroup
+ *                     writes (few in a small launch, up to 32 in a large one); 1 .. 32: that many (bit-identical at
+ *                     every value: tests/test_gpu_pcm_formant.py, tests/test_gpu_pcm_mark.py). */
 int lvx_set_option(lvx_ctx* ctx, const char* name, int value);
 /* The stream the decode graphs are captured on (then replayed on the caller's stream). NULL (default):
  * the caller's stream. Name another one when something may query, from another thread, an event
@@ -835,6 +835,60 @@ int lvx_pcm_formant_emitted(long long t0, int n_in, int final);
 int lvx_pcm_formant(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
                     const uint8_t* final_host, int Fn, int Fd, float* out_dev, long long out_stride_bytes,
                     int32_t* n_out_host, void* stream);
+
+/* ---- PCM mark -----------------------------------------------------------------
+ * The synthetic-speech watermark: a keyed, blind, multiplicative mark in 562 .. 3,375 Hz, so that a detector that
+ * holds the key (llmvox_amd/audio.py: mark_detect) can say of delivered audio, the 8 kHz G.711 path included, that
+ * this service made it, and read one payload byte. It runs AFTER the formant stage and BEFORE the level stage,
+ * always at the nominal 24 kHz, so the limiter's ceiling still holds behind it. A stream without a mark never comes
+ * here and makes exactly the calls it made before.
+ *
+ * The frames, the window w, the twiddles, DFT_N, the inverse transform, the overlap-add and the scale s are those of
+ * "PCM formant": N = 1024, H = 256, lvx_pcm_formant_tables' tables, the same fp32 order, no fused multiply-add.
+ * Frame j (j >= 0) covers the inputs [(j - 3) H, (j + 1) H). The formant rule's steps 2 to 6 are replaced by a table
+ * lookup, so the device output is bit-identical to audio.mark_ref and INDEPENDENT OF CHUNKING.
+ * Constants: K0 = 24 the first marked bin, BW = 5 the bins of a sub-band, U = 24 the sub-bands (sub-band u is the
+ * bins K0 + 5 u .. K0 + 5 u + 4); pair m = 0 .. 11 is the sub-bands (2 m, 2 m + 1); Q = 4 frames make a block,
+ * P = 64 blocks a period (2.73 s); strength is 1, 2 or 3 and a = 2^-(7 - strength) (1/64, 1/32, 1/16);
+ * g+ = 1 + a and g- = 1 - a, both exact in fp32.
+ * The sign table (host, integers only; lvx_pcm_mark_table): 64 words of 16 bits. Bit m of word p is
+ *   c(p, m) XOR bit ((12 p + m) mod 8) of the payload id (0 .. 255, bit 0 the lowest),
+ * c from SplitMix64 over the 64-bit key: state = key; for i = 12 p + m ascending: state += 0x9E3779B97F4A7C15,
+ * z = state, z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) * 0x94D049BB133111EB, z = z ^ (z >> 31),
+ * all modulo 2^64; c is the top bit of z. Bits 12 .. 15 of a word are clear. A set bit: the pair's even sub-band
+ * gets g- and its odd one g+; a clear bit: the opposite. (The antipodal pair lets the detector cancel the speech's
+ * own envelope.)
+ *   Gain of frame j at bin k: 1 outside [K0, K0 + U BW); inside, the pair's gain from word (j div Q) mod P.
+ *   Y[k] = (fl(G re), fl(G im)), k = 0 .. N / 2, X the formant rule's step 1; then that rule's steps 7 (the Hermitian
+ *   extension) and 8 and its output sum. (G = 1 leaves a bin's bits; silence stays exactly silent.)
+ * THE CONCATENATED OUTPUTS OF ANY CHUNKING OF A SEGMENT ARE BIT-IDENTICAL TO ITS ONE-SHOT OUTPUT, and, for finite
+ * input, bit-identical to audio.mark_ref. Zero input gives zero output.
+ *
+ * Streaming: exactly the formant stage's counts (lvx_pcm_mark_emitted is lvx_pcm_formant_emitted's rule): a stream
+ * holds back 768 .. 1023 samples until more arrives or its sentence's final call, on top of the formant stage's own
+ * where both run; the library keeps 1792 inputs of history per slot in two buffers of the stage's own. Every segment
+ * (sentence) starts the pattern again at frame 0. A segment has one (table, strength): another before its final call
+ * is LVX_E_ARG. The 128-byte table travels with every launch as a kernel argument: nothing is uploaded or kept on
+ * the device. No error text names the key. */
+#define LVX_MARK_K0 24
+#define LVX_MARK_BW 5
+#define LVX_MARK_U 24
+#define LVX_MARK_Q 4
+#define LVX_MARK_P 64
+/* host only: the 64 words of the sign table of (key, id). LVX_E_ARG: id outside 0 .. 255, cap < 64, words_host NULL */
+int lvx_pcm_mark_table(unsigned long long key, int id, uint16_t* words_host, int cap);
+/* host only: samples a mark call emits for a slot that has consumed t0 inputs of its segment (negative:
+ * LVX_E_ARG for t0 < 0 or n_in < 0) */
+int lvx_pcm_mark_emitted(long long t0, int n_in, int final);
+/* lvx_pcm_formant's conventions: rows b of pcm_dev [B][n_in] f32 continue the mark segments of slots_host[b];
+ * final_host[b] != 0 emits the rest and resets the slot; n_in may be 0 with final (flush only). out row b (f32)
+ * starts at out_dev + b * out_stride_bytes; n_out_host[b] = samples written. LVX_E_ARG (and no slot's state
+ * changed): id outside 0 .. 255, strength outside 1 .. 3, another mark than the slot's open segment has, B < 1,
+ * n_in < 0, a slot out of range or named twice, out_dev / out_stride_bytes not a multiple of 4 or a stride smaller
+ * than a row's output. lvx_pcm_reset also forgets a slot's mark state. */
+int lvx_pcm_mark(lvx_ctx* ctx, const float* pcm_dev, int B, int n_in, const int32_t* slots_host,
+                 const uint8_t* final_host, unsigned long long key, int id, int strength, float* out_dev,
+                 long long out_stride_bytes, int32_t* n_out_host, void* stream);
 
 /* ---- PCM FLAC ------------------------------------------------------------------
  * A lossless compressed output: a sixth stage BEHIND lvx_pcm_convert. Its input is the s16le samples of the

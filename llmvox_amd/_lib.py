@@ -137,6 +137,9 @@ _SIGS = {
     "lvx_pcm_formant_tables": (_I, [_P, _I, _P, _I, _P, _I]),
     "lvx_pcm_formant_emitted": (_I, [ctypes.c_longlong, _I, _I]),
     "lvx_pcm_formant": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P, ctypes.c_longlong, _P, _P]),
+    "lvx_pcm_mark_table": (_I, [ctypes.c_ulonglong, _I, _P, _I]),
+    "lvx_pcm_mark_emitted": (_I, [ctypes.c_longlong, _I, _I]),
+    "lvx_pcm_mark": (_I, [_P, _P, _I, _I, _P, _P, ctypes.c_ulonglong, _I, _I, _P, ctypes.c_longlong, _P, _P]),
     "lvx_pcm_flac_block": (_I, [_I]),
     "lvx_pcm_flac_emitted": (_I, [_I, ctypes.c_longlong, _I, _I]),
     "lvx_flac_stream_header": (_I, [_I, _P, _I]),

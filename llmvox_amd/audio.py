@@ -15,11 +15,13 @@ arithmetic only): ``g711_encode``, ``g711_decode``. And the FLAC output ("PCM FL
 40 ms, each a CONSTANT, FIXED or VERBATIM subframe, integer arithmetic only): ``flac_subframe``, ``flac_frame``,
 ``flac_encode_ref``, and ``FlacMux``, which finishes the device's subframes into frames on the delivery path. And the
 pause control ("PCM pause": the encoded samples cut into slots of 10 ms, each marked silent or not on the device, and
-the host's rule that trims, caps and spaces sentences by whole blocks): ``pause_slots_ref``, ``pause_ref``, ``PauseMux``."""
+the host's rule that trims, caps and spaces sentences by whole blocks): ``pause_slots_ref``, ``pause_ref``, ``PauseMux``.
+And the watermark ("PCM mark": the formant stage's transform under a keyed table of signs, between the formant and the
+level, and the blind detector of delivered audio): ``mark_table``, ``mark_ref``, ``mark_detect``."""
 from __future__ import annotations
 
 import struct
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from math import gcd
 from typing import List, Optional, Tuple
 
@@ -60,6 +62,13 @@ FORMANT_EPS = np.float32(1e-10)  # the floor added to both envelope values
 FORMANT_G2_MIN, FORMANT_G2_MAX = np.float32(1.0 / 256.0), np.float32(256.0)  # the clamp on the squared gain: +-24 dB
 FORMANT_MAX_TERM = 40000  # Fn and Fd of a correction ratio the stage takes: 1 .. 40000, coprime, within 1/2 .. 2
 FORMANT_HISTORY = 1792  # inputs of history a slot keeps between formant calls (7 H)
+MARK_K0 = 24            # the watermark's first marked bin (LVX_MARK_K0): 562.5 Hz
+MARK_BW = 5             # bins of a sub-band (LVX_MARK_BW)
+MARK_U = 24             # sub-bands (LVX_MARK_U): the band ends below bin 144, 3375 Hz
+MARK_PAIRS = MARK_U // 2  # pair m is the sub-bands (2 m, 2 m + 1)
+MARK_Q = 4              # frames of a block (LVX_MARK_Q)
+MARK_P = 64             # blocks of a period (LVX_MARK_P): 2.73 s
+MARK_STRENGTH_MIN, MARK_STRENGTH_MAX = 1, 3  # a = 2^-(7 - strength): 1/64, 1/32, 1/16
 FLAC_MAX_K = 14         # the largest Rice parameter the FLAC stage chooses (the escape code is never used)
 PAUSE_THRESH = 103      # a sample louder than this on the 16-bit scale makes its block active (LVX_PAUSE_THRESH): -50 dBFS
 PAUSE_LEAD = 2          # silent blocks kept in front of a sentence's first active one (LVX_PAUSE_LEAD): 20 ms of onset
@@ -126,6 +135,11 @@ class AudioFormat:
     # the longest silence inside a sentence in ms (None: as rendered)
     pause_ms: Optional[int] = None
     max_pause_ms: Optional[int] = None
+    # the watermark (``mark_ref`` behind the formant stage, in front of the level stage; None: no mark, no stage): its
+    # 64-bit key, which no header, error text or info endpoint repeats, its payload byte and its strength
+    mark_key: Optional[int] = field(default=None, repr=False)
+    mark_id: int = 0
+    mark_strength: int = 2
 
     def __post_init__(self):
         if isinstance(self.sample_rate, bool) or not isinstance(self.sample_rate, int) or self.sample_rate not in RATES:
@@ -153,6 +167,8 @@ class AudioFormat:
         for name, v, lo in (("pause_ms", self.pause_ms, 0), ("max_pause_ms", self.max_pause_ms, MAX_PAUSE_MS_MIN)):
             if v is not None and (isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= PAUSE_MS_MAX or v % 10):
                 raise ValueError(f"{name} must be an integer multiple of 10 in [{lo}, {PAUSE_MS_MAX}] or null, got {v!r}")
+        if self.mark_key is not None or self.mark_id != 0 or self.mark_strength != 2:
+            _check_mark(0 if self.mark_key is None else self.mark_key, self.mark_id, self.mark_strength)
         if self.pauses and self.encoding == "flac":
             raise ValueError("pause_ms / max_pause_ms with encoding 'flac': its frames are cut on the device, per "
                              "sentence, before the host could trim")
@@ -164,10 +180,15 @@ class AudioFormat:
         return self.pause_ms is not None or self.max_pause_ms is not None
 
     @property
+    def marks(self) -> bool:
+        """The format names a watermark key: the stream's rows pass the mark stage (``mark_ref``)."""
+        return self.mark_key is not None
+
+    @property
     def is_default(self) -> bool:
         return (self.sample_rate == BASE_RATE and self.encoding == "f32le" and self.container == "raw"
                 and self.speed_pct == 100 and self.pitch_pct == 100 and not self.join and self.volume_pct == 100
-                and self.formant_pct is None)
+                and self.formant_pct is None and self.mark_key is None)
 
     @property
     def converts(self) -> bool:
@@ -175,7 +196,7 @@ class AudioFormat:
         dumps): the stream needs the device stage."""
         return (self.sample_rate != BASE_RATE or self.encoding != "f32le" or self.speed_pct != 100
                 or self.pitch_pct != 100 or self.join or self.volume_pct != 100 or self.formant != (1, 1)
-                or self.pauses)
+                or self.pauses or self.marks)
 
     @property
     def stretch_pct(self) -> int:
@@ -1163,11 +1184,12 @@ def _formant_dft(re: np.ndarray, im: np.ndarray, tr: np.ndarray, ti: np.ndarray)
     return re, im
 
 
-def _formant_frames(x: np.ndarray, Fn: int, Fd: int, j0: int, j1: int, tables) -> Tuple[np.ndarray, np.ndarray]:
-    """Frames j0 .. j1 - 1 of the segment x[..., T) by the rule's eight steps: (y float32 [..., j1 - j0, N], the
-    gains G float32 [..., j1 - j0, N / 2 + 1])."""
-    N, H, K = FORMANT_N, FORMANT_H, FORMANT_K
-    w, c, tw = tables
+def _formant_stft(x: np.ndarray, j0: int, j1: int, tables, gains) -> Tuple[np.ndarray, np.ndarray]:
+    """Frames j0 .. j1 - 1 of the segment x[..., T) by the rule's steps 1, 7 and 8 around ``gains(re, im)``, which
+    turns the bins 0 .. N / 2 of the frames' spectra into their gains (the formant rule's steps 2 to 6, the mark
+    rule's table): (y float32 [..., j1 - j0, N], the gains G float32 [..., j1 - j0, N / 2 + 1])."""
+    N, H = FORMANT_N, FORMANT_H
+    w, _, tw = tables
     tr, ti = tw[:N // 2], tw[N // 2:]
     T = x.shape[-1]
     lo, hi = (j0 - 3) * H, (j1 + 3) * H  # frame j covers [(j - 3) H, (j + 1) H); the rest is slack
@@ -1179,6 +1201,33 @@ def _formant_frames(x: np.ndarray, Fn: int, Fd: int, j0: int, j1: int, tables) -
     with np.errstate(invalid="ignore", over="ignore", under="ignore", divide="ignore"):
         re, im = _formant_dft(w * fr, np.zeros(fr.shape, dtype=np.float32), tr, ti)  # 1.
         re, im = re[..., :N // 2 + 1], im[..., :N // 2 + 1]
+        G = gains(re, im)
+        yr, yi = G * re, G * im  # 7.
+        yr = np.concatenate([yr, yr[..., N // 2 - 1:0:-1]], axis=-1)
+        yi = np.concatenate([yi, -yi[..., N // 2 - 1:0:-1]], axis=-1)
+        back = _formant_dft(yr, yi, tr, -ti)[0]
+        y = w * (np.float32(2.0 ** -10) * back)  # 8.
+    return y.astype(np.float32), G
+
+
+def _formant_sum(y: np.ndarray, nb: int) -> np.ndarray:
+    """The output sum of nb hop blocks from the frames y [..., nb + 3, N] that cover them, in ascending j:
+    fl(s (((y_b + y_b+1) + y_b+2) + y_b+3)), float32 [..., nb H]."""
+    H = FORMANT_H
+    acc = y[..., 0:nb, 3 * H:]
+    for q in (1, 2, 3):
+        acc = acc + y[..., q:q + nb, (3 - q) * H:(4 - q) * H]
+    out = np.float32(2.0 / 3.0) * acc
+    return out.reshape(y.shape[:-2] + (nb * H,))
+
+
+def _formant_frames(x: np.ndarray, Fn: int, Fd: int, j0: int, j1: int, tables) -> Tuple[np.ndarray, np.ndarray]:
+    """Frames j0 .. j1 - 1 of the segment x[..., T) by the rule's eight steps: (y float32 [..., j1 - j0, N], the
+    gains G float32 [..., j1 - j0, N / 2 + 1])."""
+    N, K = FORMANT_N, FORMANT_K
+    c = tables[1]
+
+    def gains(re, im):
         P = re * re + im * im  # 2.
         at = np.abs(np.arange(-K, N // 2 + 1 + K))
         Pe = P[..., np.where(at > N // 2, N - at, at)]  # 3.
@@ -1192,13 +1241,9 @@ def _formant_frames(x: np.ndarray, Fn: int, Fd: int, j0: int, j1: int, tables) -
         e0 = E[..., i0]
         Es = np.where(i >= N // 2, E[..., N // 2:], e0 + f * (E[..., i0 + 1] - e0))
         G2 = np.minimum(np.maximum((Es + FORMANT_EPS) / (E + FORMANT_EPS), FORMANT_G2_MIN), FORMANT_G2_MAX)  # 6.
-        G = np.sqrt(G2).astype(np.float32)
-        yr, yi = G * re, G * im  # 7.
-        yr = np.concatenate([yr, yr[..., N // 2 - 1:0:-1]], axis=-1)
-        yi = np.concatenate([yi, -yi[..., N // 2 - 1:0:-1]], axis=-1)
-        back = _formant_dft(yr, yi, tr, -ti)[0]
-        y = w * (np.float32(2.0 ** -10) * back)  # 8.
-    return y.astype(np.float32), G
+        return np.sqrt(G2).astype(np.float32)
+
+    return _formant_stft(x, j0, j1, tables, gains)
 
 
 def formant_gains(x, Fn: int, Fd: int, tables=None) -> np.ndarray:
@@ -1232,19 +1277,177 @@ def formant_ref(x, Fn: int, Fd: int, tables=None, n0: int = 0, n1: Optional[int]
     tables = formant_tables() if tables is None else tuple(np.asarray(t, dtype=np.float32) for t in tables)
     b0, b1 = n0 // H, -(-n1 // H)  # the hop blocks of the outputs; block b is covered by the frames b .. b + 3
     y = _formant_frames(x, Fn, Fd, b0, b1 + 3, tables)[0]
-    nb = b1 - b0
-    acc = y[..., 0:nb, 3 * H:]  # the frames in ascending j: ((y_b + y_b+1) + y_b+2) + y_b+3
-    for q in (1, 2, 3):
-        acc = acc + y[..., q:q + nb, (3 - q) * H:(4 - q) * H]
-    out = np.float32(2.0 / 3.0) * acc
-    return out.reshape(x.shape[:-1] + (nb * H,))[..., :n1 - n0].astype(np.float32)
+    return _formant_sum(y, b1 - b0)[..., :n1 - n0].astype(np.float32)
+
+
+# ---- the watermark's rule (include/llmvox.h, "PCM mark"), in numpy, and its detector --------------------
+
+_MASK64 = (1 << 64) - 1
+
+
+def _check_mark(key, mark_id, strength):
+    # (no message repeats the key)
+    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) <= _MASK64:
+        raise ValueError("mark_key must be an integer in 0 .. 2^64 - 1")
+    if isinstance(mark_id, bool) or not isinstance(mark_id, (int, np.integer)) or not 0 <= mark_id <= 255:
+        raise ValueError(f"mark_id must be an integer in [0, 255], got {mark_id!r}")
+    if isinstance(strength, bool) or not isinstance(strength, (int, np.integer)) \
+            or not MARK_STRENGTH_MIN <= strength <= MARK_STRENGTH_MAX:
+        raise ValueError(f"mark_strength must be an integer in [{MARK_STRENGTH_MIN}, {MARK_STRENGTH_MAX}], "
+                         f"got {strength!r}")
+
+
+def mark_table(key: int, mark_id: int = 0) -> np.ndarray:
+    """uint16 [64]: the watermark's sign table (``lvx_pcm_mark_table``), integers only. Bit m of word p is
+    c(p, m) XOR bit ((12 p + m) mod 8) of ``mark_id``, c the top bit of output number 12 p + m of SplitMix64 started
+    at ``key``. A set bit: pair m of block p has g- on its even sub-band and g+ on its odd one; clear: the opposite."""
+    _check_mark(key, mark_id, MARK_STRENGTH_MIN)
+    state, words = int(key), np.zeros(MARK_P, dtype=np.uint16)
+    for p in range(MARK_P):
+        word = 0
+        for m in range(MARK_PAIRS):
+            state = (state + 0x9E3779B97F4A7C15) & _MASK64
+            z = state
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+            z ^= z >> 31
+            word |= ((z >> 63) ^ ((int(mark_id) >> ((MARK_PAIRS * p + m) % 8)) & 1)) << m
+        words[p] = word
+    return words
+
+
+def mark_emitted_upto(T: int, final: bool) -> int:
+    """Samples of a segment the mark stage has emitted once T inputs are consumed: the formant stage's count."""
+    return formant_emitted_upto(T, final)
+
+
+def mark_emitted(t0: int, n_in: int, final: bool) -> int:
+    """Samples a mark call emits for a slot that has consumed t0 inputs of its segment (``lvx_pcm_mark_emitted``)."""
+    return formant_emitted(t0, n_in, final)
+
+
+def mark_gains(words, strength: int, j0: int, j1: int) -> np.ndarray:
+    """The gains G[j, k] float32 [j1 - j0, 513] of the frames j0 .. j1 - 1 under the sign table ``words``: 1 outside
+    the band, inside the pair's g+ = 1 + a or g- = 1 - a from word (j div Q) mod P, a = 2^-(7 - strength)."""
+    a = np.float32(2.0 ** -(7 - int(strength)))
+    gp, gm = np.float32(1.0) + a, np.float32(1.0) - a
+    words = np.asarray(words, dtype=np.uint16).astype(np.int64)
+    word = words[(np.arange(j0, j1) // MARK_Q) % MARK_P]  # [frames]
+    u = np.arange(MARK_U)
+    bit = (word[:, None] >> (u // 2)[None, :]) & 1  # [frames, U]
+    g = np.where(bit == (u % 2)[None, :], gp, gm).astype(np.float32)  # a set bit: g- on the even, g+ on the odd
+    G = np.ones((j1 - j0, FORMANT_N // 2 + 1), dtype=np.float32)
+    G[:, MARK_K0:MARK_K0 + MARK_U * MARK_BW] = np.repeat(g, MARK_BW, axis=1)
+    return G
+
+
+def mark_ref(x, key: int, mark_id: int = 0, strength: int = 2, tables=None, n0: int = 0, n1: Optional[int] = None,
+             words=None) -> np.ndarray:
+    """Outputs n0 .. n1 - 1 (default: all T; n0 a multiple of H) of the segment x[0 .. T) (float32 at 24 kHz, zero
+    outside) under the watermark of (key, mark_id, strength): the formant stage's frames, transform and output sum
+    (``formant_ref``), the gain of a bin a lookup in ``mark_table``, every operation fp32 in the rule's order: the bits
+    the device computes (``lvx_pcm_mark``) with the same fp32 tables. ``tables``: the formant stage's (w, c, tw)
+    (default: built here); ``words``: the sign table (default: built here; the device tests pass the library's)."""
+    _check_mark(key, mark_id, strength)
+    H = FORMANT_H
+    x = np.asarray(x, dtype=np.float32)
+    T = x.shape[-1]
+    if n1 is None:
+        n1 = T
+    if n0 % H:
+        raise ValueError("n0 must be a multiple of the hop")
+    if n1 <= n0:
+        return np.zeros(x.shape[:-1] + (0,), dtype=np.float32)
+    tables = formant_tables() if tables is None else tuple(np.asarray(t, dtype=np.float32) for t in tables)
+    words = mark_table(key, mark_id) if words is None else np.asarray(words, dtype=np.uint16)
+    b0, b1 = n0 // H, -(-n1 // H)  # the hop blocks of the outputs; block b is covered by the frames b .. b + 3
+    G = mark_gains(words, strength, b0, b1 + 3)
+    y = _formant_stft(x, b0, b1 + 3, tables, lambda re, im: G)[0]
+    return _formant_sum(y, b1 - b0)[..., :n1 - n0].astype(np.float32)
+
+
+_MARK_TO_BASE = {8000: (3, 1), 16000: (3, 2), 24000: (1, 1), 48000: (1, 2)}  # (L, M) that bring a rate to 24 kHz
+MARK_DETECT_STEP = 64      # the detector's hop and the step of its sample offsets
+MARK_DETECT_MIN = 8.0      # detected: S >= 8 (P(S >= 8) <= 2^8 P(N(0, 1) >= 8) per candidate under no mark)
+
+
+def _mark_search(z: np.ndarray, signs: np.ndarray) -> Tuple[float, np.ndarray, int]:
+    """The detector's search over one stretch of 24 kHz audio z (float64): (S, z_b [8], offset) of the best of the
+    16 sample offsets x 64 block phases. ``signs``: +-1 [P, 12] from the key alone."""
+    N, H, Q, P, U, BW, K0, step = FORMANT_N, FORMANT_H, MARK_Q, MARK_P, MARK_U, MARK_BW, MARK_K0, MARK_DETECT_STEP
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(N) + 0.5) / N)
+    zp = np.concatenate([np.zeros(3 * H), z, np.zeros(N)])
+    n_fr = (zp.size - N) // step
+    best = (-1.0, np.zeros(8), 0)
+    if n_fr <= 0:
+        return best
+    fr = np.lib.stride_tricks.sliding_window_view(zp, N)[::step][:n_fr]
+    X = np.fft.rfft(w * fr, axis=-1)[:, K0:K0 + U * BW]
+    Pw = (X.real ** 2 + X.imag ** 2).reshape(n_fr, U, BW).sum(-1)  # the power of every sub-band at every hop
+    per, bits = H // step, (MARK_PAIRS * np.arange(P)[:, None] + np.arange(MARK_PAIRS)[None, :]) % 8
+    for off in range(0, Q * H, step):  # where a block starts, in samples
+        o = off // step
+        nb = (n_fr - o - 3 * per) // (Q * per)
+        if nb < 3:
+            continue
+        i1 = o + (np.arange(nb) * Q + 1) * per  # the block's two middle frames
+        L = np.log(Pw[i1] + Pw[i1 + per] + 1e-12)
+        D = L[:, 0::2] - L[:, 1::2]  # even sub-band over odd, per pair
+        d = D[1:-1] - 0.5 * (D[:-2] + D[2:])  # against the neighbouring blocks: the speech's own envelope cancels
+        sd = 1.48 * np.median(np.abs(d))
+        d = np.clip(d, -2.0 * sd, 2.0 * sd)
+        d2 = d * d
+        for ph in range(P):  # which block of the period the first one is
+            q = (np.arange(1, nb - 1) + ph) % P
+            c, ii = d * signs[q], bits[q]
+            num = np.array([c[ii == b].sum() for b in range(8)])
+            den = np.sqrt(np.array([d2[ii == b].sum() for b in range(8)]))
+            zb = num / np.maximum(den, 1e-30)
+            S = float(np.abs(zb).sum() / np.sqrt(8.0))
+            if S > best[0]:
+                best = (S, zb, off)
+    return best
+
+
+def mark_detect(x, sample_rate: int, key: int, window_s: Optional[float] = None) -> Tuple[float, bool, int, int]:
+    """The watermark's blind detector: (S, detected, id, offset) of the audio x (float samples at ``sample_rate``, one
+    of the service's four) under ``key``. x is brought to 24 kHz (``ratio_ref`` by 3/1, 3/2, 1/1 or 1/2); the powers
+    of the 24 sub-bands are taken at a hop of 64; for every candidate alignment (16 sample offsets x 64 block phases)
+    each block gives D[m] = log power of pair m's even sub-band minus its odd one's from the block's two middle
+    frames, d = D_q - (D_{q-1} + D_{q+1}) / 2 clipped at twice its robust spread, and every payload bit b
+    z_b = sum(d sign) / sqrt(sum d^2) over its chips, the signs from the key alone; S = sum |z_b| / sqrt(8). The best
+    candidate is reported; ``id`` from the signs of its z_b; ``detected`` is S >= 8; ``offset`` the sample (at 24 kHz)
+    at which its blocks start, plus the window's start. ``window_s``: search windows of that many seconds at half that
+    step instead of the whole signal and report the best (every sentence of a request restarts the pattern)."""
+    _check_mark(key, 0, MARK_STRENGTH_MIN)
+    if sample_rate not in _MARK_TO_BASE:
+        raise ValueError(f"sample_rate must be one of {sorted(_MARK_TO_BASE)}, got {sample_rate!r}")
+    x = np.asarray(x, dtype=np.float32).reshape(-1)
+    L, M = _MARK_TO_BASE[sample_rate]
+    z = (ratio_ref(x, L, M) if L != M else x).astype(np.float64)
+    signs = 1.0 - 2.0 * ((mark_table(key, 0).astype(np.int64)[:, None] >> np.arange(MARK_PAIRS)[None, :]) & 1)
+    if window_s is None:
+        starts, n = [0], max(z.size, 1)
+    else:
+        n = int(round(window_s * BASE_RATE))
+        if n < 8 * MARK_Q * FORMANT_H:
+            raise ValueError(f"window_s must cover at least 8 blocks ({8 * MARK_Q * FORMANT_H / BASE_RATE:.3f} s)")
+        starts = list(range(0, max(z.size - n, 0) + 1, max(n // 2, 1)))
+    best = (-1.0, np.zeros(8), 0)
+    for s0 in starts:
+        S, zb, off = _mark_search(z[s0:s0 + n], signs)
+        if S > best[0]:
+            best = (S, zb, s0 + off)
+    S, zb, off = best
+    mark_id = int(sum(1 << b for b in range(8) if zb[b] < 0))
+    return max(S, 0.0), bool(S >= MARK_DETECT_MIN), mark_id, int(off)
 
 
 def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, level_win=None,
                 formant_tabs=None) -> np.ndarray:
     """A whole segment x (float32 at 24 kHz) at the format's speed, pitch, volume, rate and encoding (a float32,
     int16 or uint8 array): stretched at the plan's stretch_pct, resampled by its L / M, its envelope corrected by
-    the plan's Fn / Fd, levelled at its volume_pct, then resampled to the rate and encoded. ``ratio_taps``: the fp32
+    the plan's Fn / Fd, watermarked where it names a key, levelled at its volume_pct, then resampled to the rate and encoded. ``ratio_taps``: the fp32
     table of the format's ratio (default: designed here); ``level_win``: the level stage's fp32 window (default:
     built here); ``formant_tabs``: the formant stage's fp32 tables (default: built here)."""
     stretch, (L, M), (Fn, Fd) = fmt.stretch_pct, fmt.ratio, fmt.formant
@@ -1254,6 +1457,8 @@ def convert_ref(x, fmt: AudioFormat, taps=None, windows=None, ratio_taps=None, l
         x = ratio_ref(x, L, M, ratio_taps)
     if Fn != Fd:
         x = formant_ref(x, Fn, Fd, formant_tabs)
+    if fmt.marks:
+        x = mark_ref(x, fmt.mark_key, fmt.mark_id, fmt.mark_strength, formant_tabs)
     if fmt.volume_pct != 100:
         x = level_ref(x, fmt.volume_pct, level_win)[0]
     return encode_ref(resample_ref(x, fmt.sample_rate, taps), fmt)
@@ -1263,7 +1468,7 @@ class StreamRef:
     """The streaming form of the rule for one slot, on the host: ``push(x, final)`` returns the samples the
     call emits (``Engine.pcm_convert`` for one row: ``lvx_pcm_join`` when the format joins its dumps, then
     ``lvx_pcm_stretch`` when the plan has a stretch, then ``lvx_pcm_ratio`` when it has a ratio, then
-    ``lvx_pcm_formant`` when it has an envelope correction, then ``lvx_pcm_level`` when it has a volume, then
+    ``lvx_pcm_formant`` when it has an envelope correction, then ``lvx_pcm_mark`` when it names a watermark key, then ``lvx_pcm_level`` when it has a volume, then
     ``lvx_pcm_convert`` and, a FLAC format, ``lvx_pcm_flac`` behind it as s16le: the slots of the frames the call
     emits; a pausing format, ``lvx_pcm_pause`` last: the slots of the blocks the call emits). ``ctx_frames``: the context frames in front of x (a joined format only). Keeps the whole segment; for
     tests and stand-in engines. ``last_d``: the d_j of the hops the last push emitted."""
@@ -1272,9 +1477,11 @@ class StreamRef:
                  formant_tabs=None):
         self.fmt, self.taps, self.ratio_taps = fmt, taps, ratio_taps
         self.Fn, self.Fd = fmt.formant
-        if self.Fn != self.Fd:
+        if self.Fn != self.Fd or fmt.marks:
             tabs = formant_tables() if formant_tabs is None else formant_tabs
             self.formant_tabs = tuple(np.asarray(t, dtype=np.float32) for t in tabs)
+        if fmt.marks:
+            self.mark_words = mark_table(fmt.mark_key, fmt.mark_id)
         if fmt.volume_pct != 100:
             self.level_win = level_window() if level_win is None else np.asarray(level_win, dtype=np.float32)
         if fmt.join:
@@ -1297,6 +1504,8 @@ class StreamRef:
         self.join_tail: Optional[np.ndarray] = None  # the join's view: the held-back frame (None: closed)
         self.fmn: List[np.ndarray] = []  # the formant stage's view: the resampled segment and its count
         self.fmn_t0 = 0
+        self.mrk: List[np.ndarray] = []  # the mark stage's view: the segment in front of it and its count
+        self.mrk_t0 = 0
         self.lvl: List[np.ndarray] = []  # the level stage's view: the resampled segment and its count
         self.lvl_t0 = 0
         self.fq: List[np.ndarray] = []  # the FLAC stage's view: the segment's s16 samples and their count
@@ -1317,6 +1526,14 @@ class StreamRef:
         self.fmn.append(x)
         self.fmn_t0 += x.size
         return formant_ref(np.concatenate(self.fmn), self.Fn, self.Fd, self.formant_tabs, n0, n1)
+
+    def _mark(self, x, final: bool) -> np.ndarray:
+        n0 = mark_emitted_upto(self.mrk_t0, False)
+        n1 = mark_emitted_upto(self.mrk_t0 + x.size, final)
+        self.mrk.append(x)
+        self.mrk_t0 += x.size
+        return mark_ref(np.concatenate(self.mrk), self.fmt.mark_key, self.fmt.mark_id, self.fmt.mark_strength,
+                        self.formant_tabs, n0, n1, self.mark_words)
 
     def _level(self, x, final: bool) -> np.ndarray:
         pct = self.fmt.volume_pct
@@ -1351,6 +1568,8 @@ class StreamRef:
             x = self._ratio(x, final)
         if self.Fn != self.Fd:
             x = self._formant(x, final)
+        if self.fmt.marks:
+            x = self._mark(x, final)
         if self.fmt.volume_pct != 100:
             x = self._level(x, final)
         rate = self.fmt.sample_rate
@@ -1399,4 +1618,6 @@ __all__ = ["AudioFormat", "wav_header", "design", "emitted", "emitted_upto", "re
            "LEVEL_A", "LEVEL_R", "LEVEL_CEIL", "LEVEL_HISTORY",
            "formant_plan", "formant_tables", "formant_emitted", "formant_emitted_upto", "formant_ref", "formant_gains",
            "FORMANT_MIN", "FORMANT_MAX", "FORMANT_N", "FORMANT_H", "FORMANT_K", "FORMANT_EPS", "FORMANT_MAX_TERM",
-           "FORMANT_HISTORY"]
+           "FORMANT_HISTORY",
+           "mark_table", "mark_emitted", "mark_emitted_upto", "mark_gains", "mark_ref", "mark_detect", "MARK_K0", "MARK_BW",
+           "MARK_U", "MARK_PAIRS", "MARK_Q", "MARK_P", "MARK_STRENGTH_MIN", "MARK_STRENGTH_MAX", "MARK_DETECT_MIN"]

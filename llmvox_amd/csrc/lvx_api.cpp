@@ -212,7 +212,7 @@ struct lvx_ctx {
   int n_sampling = 0;           // slots with temperature > 0: while any, the steps plan with sample = true
   // The PCM stages (pcm_host.h: the skeleton of their calls). Each has its device tables, a pool of two buffers per
   // slot [2][max_streams][*_HIST] and, in seg (under mu), the host mirror of every slot's segment.
-  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_FLAC, SEG_FORMANT, SEG_PAUSE, SEG_STAGES };
+  enum { SEG_CONVERT, SEG_STRETCH, SEG_RATIO, SEG_JOIN, SEG_LEVEL, SEG_FLAC, SEG_FORMANT, SEG_PAUSE, SEG_MARK, SEG_STAGES };
   std::vector<PcmSeg> seg[SEG_STAGES];
   float* pcm_taps = nullptr;  // rate and encoding: the taps of the three resampling rates
   float* pcm_hist = nullptr;
@@ -234,6 +234,7 @@ struct lvx_ctx {
   float* fmt_tab = nullptr;   // formant: the tables [FMT_TABLES]: w, c, the twiddles
   float* fmt_hist = nullptr;
   unsigned char* pause_hist = nullptr;  // pause: the 1 .. bl encoded samples no block has taken yet (bytes)
+  float* mrk_hist = nullptr;  // mark: its own [FMT_HIST] buffers (the tables are the formant stage's, the signs an argument)
   std::mutex mu;
 
   bool sampling_snapshot() {
@@ -752,6 +753,9 @@ int lvx_finalize(lvx_ctx* c) {
   // ---- PCM pause (allocated last: every other buffer stays where it was) ----
   if ((r = c->dalloc(&c->pause_hist, (size_t)2 * S * PAUSE_HIST))) return r;
   HIP_TRY(hipMemset(c->pause_hist, 0, (size_t)2 * S * PAUSE_HIST));
+  // ---- PCM mark (allocated last: every other buffer stays where it was) ----
+  if ((r = c->dalloc(&c->mrk_hist, (size_t)2 * S * FMT_HIST))) return r;
+  HIP_TRY(hipMemset(c->mrk_hist, 0, (size_t)2 * S * FMT_HIST * 4));
   for (auto& v : c->seg) v.assign(S, PcmSeg{});
   HIP_TRY(hipDeviceSynchronize());
   c->host.clear();
@@ -1580,6 +1584,40 @@ int lvx_pcm_formant(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t
   OptScope os(&o);
   return pcm_launches<PcmRows>(c, rows, [&](const PcmRows& pk, int nr, int max_out) {
     pcm_launch_formant(pk, nr, max_out, Fn, Fd, pcm, n_in, c->fmt_tab, c->fmt_hist, out, out_stride, (hipStream_t)stream);
+  });
+}
+
+// ---- PCM mark ----
+int lvx_pcm_mark_table(unsigned long long key, int id, uint16_t* words_host, int cap) {
+  if (id < 0 || id > 255) return fail(LVX_E_ARG, "id must be in 0 .. 255, got " + std::to_string(id));
+  if (!words_host || cap < MRK_P) return fail(LVX_E_ARG, "words_host is null or holds fewer than 64 words");
+  const MarkTab t = mark_table(key, id);
+  std::memcpy(words_host, t.w, sizeof t.w);
+  return LVX_OK;
+}
+
+int lvx_pcm_mark_emitted(long long t0, int n_in, int final) { return lvx_pcm_formant_emitted(t0, n_in, final); }
+
+int lvx_pcm_mark(lvx_ctx* c, const float* pcm, int B, int n_in, const int32_t* slots, const uint8_t* final_host,
+                 unsigned long long key, int id, int strength, float* out, long long out_stride, int32_t* n_out_host,
+                 void* stream) {
+  NEED_FINAL(c);
+  if (!mark_ok(id, strength)) return fail(LVX_E_ARG, mark_msg(id, strength));
+  if (int r = pcm_args(B, n_in, pcm, slots && final_host && n_out_host ? slots : nullptr, true, out, out_stride)) return r;
+  const MarkTab mt = mark_table(key, id);
+  std::vector<PcmRow> rows;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    const std::string e = pcm_plan(
+        c->seg[lvx_ctx::SEG_MARK], FMT_HIST, B, n_in, slots, final_host, n_out_host, mark_digest(mt, strength), true,
+        [](long long) { return std::string("another mark (key, id or strength)"); }, rows,
+        [&](const PcmCall& q, PcmRow& r) { return plan_mark(q, n_in, out_stride, r); });
+    if (!e.empty()) return fail(LVX_E_ARG, e);
+  }
+  const Opts o = c->opts_snapshot();
+  OptScope os(&o);
+  return pcm_launches<PcmRows>(c, rows, [&](const PcmRows& pk, int nr, int max_out) {
+    pcm_launch_mark(pk, nr, max_out, mt, mark_a(strength), pcm, n_in, c->fmt_tab, c->mrk_hist, out, out_stride, (hipStream_t)stream);
   });
 }
 

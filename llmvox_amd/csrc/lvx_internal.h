@@ -292,6 +292,10 @@ void pcm_launch_level(const PcmRows& rows, int n_rows, int max_out, float gain, 
 // Fn / Fd: the correction ratio, coprime, each <= FMT_MAX; tab: w [FMT_N], c [FMT_TAPS], the twiddles [FMT_N]
 void pcm_launch_formant(const PcmRows& rows, int n_rows, int max_out, int Fn, int Fd, const float* pcm, int n_in,
                         const float* tab, float* hist, float* out, long long out_stride, hipStream_t s);
+// mt: the sign table (by value into the launch); a = 2^-(7 - strength); tab: the formant stage's tables; hist: the
+// mark stage's own pool
+void pcm_launch_mark(const PcmRows& rows, int n_rows, int max_out, const MarkTab& mt, float a, const float* pcm, int n_in,
+                     const float* tab, float* hist, float* out, long long out_stride, hipStream_t s);
 void pcm_launch_flac(const FlacRows& rows, int n_rows, int max_frames, int bs, const int16_t* s16, int n_in,
                      long long in_stride, int16_t* hist, void* out, long long out_stride, hipStream_t s);
 // bl: the block of the rate; enc: LVX_PCM_*; in: rows of that encoding; hist: the byte pool [2][slots][PAUSE_HIST]

@@ -1,8 +1,8 @@
 // Host side of the PCM stages (include/llmvox.h: "PCM output stage", "PCM time stretch", "PCM pitch shift", "PCM dump
-// join", "PCM level", "PCM formant", "PCM G.711", "PCM FLAC", "PCM pause"): the stages' constants and kernel row packets, the tables and streaming
+// join", "PCM level", "PCM formant", "PCM mark", "PCM G.711", "PCM FLAC", "PCM pause"): the stages' constants and kernel row packets, the tables and streaming
 // counts of llmvox.h's rules in double, the G.711 companding, the FLAC stage's selection arithmetic and the host side of
 // its frames, and the one skeleton every stage's entry point runs (lvx_api.cpp). No HIP header and no device:
-// tests/host/pcm_stage_check.cpp, g711_check.cpp, flac_check.cpp, formant_check.cpp and pause_check.cpp drive all of it
+// tests/host/pcm_stage_check.cpp, g711_check.cpp, flac_check.cpp, formant_check.cpp, pause_check.cpp and mark_check.cpp drive all of it
 // with the system compiler.
 #pragma once
 #include <stdint.h>
@@ -137,6 +137,20 @@ constexpr int FMT_BINS = FMT_N / 2 + 1;   // bins 0 .. N / 2 of a real signal's 
 constexpr int FMT_HIST = 7 * FMT_H;       // inputs of history a slot keeps between calls (a call's first output reaches back <= 7 H - 1)
 constexpr int FMT_MAX = 40000;            // Fn and Fd of a correction ratio: 1 .. 40000 (the plan's are <= 100 * 200 and 200 * 200)
 constexpr int FMT_TABLES = FMT_N + FMT_TAPS + FMT_N;  // floats of the device tables: w, c, then the twiddles (re then im)
+
+// PCM mark: the watermark. The formant stage's frames, tables, counts, history and rows (PcmRows); its own pool of
+// [FMT_HIST] buffers. The sign table travels by value with every launch.
+constexpr int MRK_K0 = LVX_MARK_K0;       // first marked bin
+constexpr int MRK_BW = LVX_MARK_BW;       // bins of a sub-band
+constexpr int MRK_U = LVX_MARK_U;         // sub-bands: pair m is the sub-bands (2 m, 2 m + 1)
+constexpr int MRK_PAIRS = MRK_U / 2;
+constexpr int MRK_Q = LVX_MARK_Q;         // frames of a block
+constexpr int MRK_P = LVX_MARK_P;         // blocks of a period
+constexpr int MRK_STRENGTH_MIN = 1, MRK_STRENGTH_MAX = 3;
+struct MarkTab {
+  uint16_t w[MRK_P];  // bit m of word p: pair m of block p has g- on its even sub-band and g+ on its odd one
+};
+static_assert(MRK_K0 + MRK_U * MRK_BW <= FMT_N / 2 && MRK_PAIRS <= 16 && MRK_U % 2 == 0, "the band lies below N / 2 and a word holds the pairs");
 
 // ---------------- the rules' tables and counts ----------------
 // ---- PCM dump join: the window tables and the counts (llmvox.h) ----
@@ -322,6 +336,41 @@ inline void formant_design(float* w, float* c, float* tw) {
 inline long long formant_emitted_upto(long long T, bool final) {
   if (final) return T;
   return std::max(0ll, (T / FMT_H - 3) * FMT_H);
+}
+
+// ---- PCM mark: the sign table, its digest and the gain step (llmvox.h); the counts are the formant stage's ----
+inline bool mark_ok(int id, int strength) { return id >= 0 && id <= 255 && strength >= MRK_STRENGTH_MIN && strength <= MRK_STRENGTH_MAX; }
+inline std::string mark_msg(int id, int strength) {
+  return "id must be in 0 .. 255 and strength in 1 .. 3, got id " + std::to_string(id) + ", strength " + std::to_string(strength);
+}
+// bit m of word p: c(p, m) XOR bit ((12 p + m) mod 8) of id, c the top bit of SplitMix64's output number 12 p + m
+inline MarkTab mark_table(uint64_t key, int id) {
+  MarkTab t{};
+  uint64_t state = key;
+  for (int p = 0; p < MRK_P; ++p)
+    for (int m = 0; m < MRK_PAIRS; ++m) {
+      state += 0x9E3779B97F4A7C15ull;
+      uint64_t z = state;
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      z ^= z >> 31;
+      const unsigned bit = (unsigned)(z >> 63) ^ (((unsigned)id >> ((MRK_PAIRS * p + m) % 8)) & 1u);
+      t.w[p] = (uint16_t)(t.w[p] | (bit << m));
+    }
+  return t;
+}
+// a = 2^-(7 - strength): 1/64, 1/32, 1/16
+inline float mark_a(int strength) { return 1.0f / (float)(1 << (7 - strength)); }
+// what a segment is open at (PcmSeg::key): FNV-1a over the table's words and the strength, the sign bit cleared
+inline long long mark_digest(const MarkTab& t, int strength) {
+  uint64_t h = 0xCBF29CE484222325ull;
+  auto eat = [&](unsigned byte) { h = (h ^ (byte & 0xffu)) * 0x100000001B3ull; };
+  for (int p = 0; p < MRK_P; ++p) {
+    eat(t.w[p]);
+    eat(t.w[p] >> 8u);
+  }
+  eat((unsigned)strength);
+  return (long long)(h & 0x7FFFFFFFFFFFFFFFull);
 }
 
 // ---- PCM G.711: the companding of an s16 sample and its inverse (llmvox.h), integers only ----
@@ -792,6 +841,11 @@ inline std::string plan_level(const PcmCall& c, int n_in, int pct, long long out
 inline std::string plan_formant(const PcmCall& c, int n_in, int Fn, int Fd, long long out_stride, PcmRow& r) {
   r = PcmRow{0, 0, n_in, 0, -1, c.row};
   if (Fn == Fd) return {};  // 1 / 1: the rows of pcm_dev are the output
+  return plan_counted(c, n_in, [&](long long T, bool f) { return formant_emitted_upto(T, f); }, true, true, 4, out_stride, r);
+}
+
+// the formant stage's counts and history; every call launches (there is no identity mark)
+inline std::string plan_mark(const PcmCall& c, int n_in, long long out_stride, PcmRow& r) {
   return plan_counted(c, n_in, [&](long long T, bool f) { return formant_emitted_upto(T, f); }, true, true, 4, out_stride, r);
 }
 

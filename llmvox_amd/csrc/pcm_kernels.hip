@@ -14,7 +14,8 @@
 // formant control between the pitch control and the volume control ("PCM formant"): a short-time Fourier
 // correction of the spectral envelope in LDS, launched only for a stream that named a formant. And, last of all, the
 // marks of the pause control ("PCM pause"): the encoded rows cut into slots of 10 ms, each marked silent or not,
-// launched only for a stream that named a pause.
+// launched only for a stream that named a pause. And the watermark between the formant and the volume control ("PCM
+// mark"): the formant stage's transform and frame loop under a keyed table of signs, launched only for a marked stream.
 #include <algorithm>
 #include <type_traits>
 
@@ -833,38 +834,31 @@ __device__ __forceinline__ void fmt_stages(float* s_re, float* s_im, const float
   }
 }
 
-__global__ __launch_bounds__(PCM_THREADS) void pcm_formant_kernel(PcmRows rows, int Fn, int Fd, const float* __restrict__ pcm,
-                                                                  int n_in, const float* __restrict__ tab, float* hist,
-                                                                  unsigned char* __restrict__ out, long long out_stride,
-                                                                  int group) {
-#pragma clang fp contract(off)
-  const PcmRow r = rows.r[blockIdx.y];
-  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
-  const int tid = threadIdx.x;
-  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
-  const SegInput<FMT_HIST> input{x, hist, r.t0, t1, r.hist_in};
-  if (blockIdx.x == 0 && r.hist_out >= 0)
-    for (int i = tid; i < FMT_HIST; i += PCM_THREADS) hist[r.hist_out + i] = input(t1 - FMT_HIST + i);
-
-  const int n_blocks = (r.n_out + FMT_H - 1) / FMT_H;  // hop blocks of this call (the last may be cut by a final call)
-  const int lb0 = blockIdx.x * group;                  // the group's first, counted from the call's first
-  if (lb0 >= n_blocks) return;
-  const int lb1 = min(lb0 + group, n_blocks);
-  const long long b_first = r.m0 / FMT_H;  // (m0 is a multiple of H: only a final call emits part of a block)
-
-  __shared__ float s_re[FMT_N], s_im[FMT_N], s_acc[FMT_N], s_w[FMT_N];
-  __shared__ float s_tr[FMT_HALF], s_ti[FMT_HALF], s_c[FMT_TAPS];
-  __shared__ float s_P[FMT_BINS], s_E[FMT_BINS], s_G[FMT_BINS];
+// The tables both transforms need, from the stage's device tables to LDS: the window and the twiddles. Ends behind no
+// barrier: the caller's own follows.
+__device__ __forceinline__ void fmt_load_tables(const float* __restrict__ tab, float* s_w, float* s_tr, float* s_ti, int tid) {
   for (int i = tid; i < FMT_N; i += PCM_THREADS) s_w[i] = tab[i];
-  if (tid < FMT_TAPS) s_c[tid] = tab[FMT_N + tid];
   for (int i = tid; i < FMT_HALF; i += PCM_THREADS) {
     s_tr[i] = tab[FMT_N + FMT_TAPS + i];
     s_ti[i] = tab[FMT_N + FMT_TAPS + FMT_HALF + i];
   }
-  __syncthreads();
+}
 
-  const float eps = 1e-10f, g2_lo = 1.f / 256.f, g2_hi = 256.f, two_thirds = (float)(2.0 / 3.0);
-  float* __restrict__ o = reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride);
+// The slot's next history: the last FMT_HIST inputs of the segment once the call is consumed
+__device__ __forceinline__ void fmt_keep_history(const SegInput<FMT_HIST>& input, float* hist, int hist_out, long long t1, int tid) {
+  for (int i = tid; i < FMT_HIST; i += PCM_THREADS) hist[hist_out + i] = input(t1 - FMT_HIST + i);
+}
+
+// The frame loop of a workgroup, one template over the gain step: the frames lb0 .. lb1 + 2 of the call (frame
+// j = b_first + lj), each windowed, transformed, multiplied by its gains, transformed back and added to the ring of
+// hop blocks. Gain: prepare(s_re, s_im, j, tid), which sees the spectrum behind a barrier and ends behind one where it
+// wrote LDS, then operator()(k), the gain of bin k <= N / 2.
+template <class Gain>
+__device__ __forceinline__ void fmt_frames(const PcmRow& r, const SegInput<FMT_HIST>& input, float* __restrict__ o, int lb0, int lb1,
+                                           long long b_first, float* s_re, float* s_im, float* s_acc, const float* s_w,
+                                           const float* s_tr, const float* s_ti, Gain& gain, int tid) {
+#pragma clang fp contract(off)
+  const float two_thirds = (float)(2.0 / 3.0);
   for (int lj = lb0; lj < lb1 + 3; ++lj) {  // frame j = b_first + lj covers the call's hop blocks lj - 3 .. lj
     const long long g0 = (b_first + lj - 3) * FMT_H;  // its first input
     // 1. the windowed frame, to bit-reversed places
@@ -876,6 +870,53 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_formant_kernel(PcmRows rows, 
     }
     __syncthreads();
     fmt_stages(s_re, s_im, s_tr, s_ti, false, tid);
+    // 2 .. 6. the gains of the frame's bins
+    gain.prepare(s_re, s_im, b_first + lj, tid);
+    // 7. Y = G X on 0 .. N / 2 and its Hermitian extension, through registers to bit-reversed places
+    float yr[FMT_PER], yi[FMT_PER];
+#pragma unroll
+    for (int q = 0; q < FMT_PER; ++q) {
+      const int k = tid + q * PCM_THREADS, kk = k <= FMT_HALF ? k : FMT_N - k;
+      const float g = gain(kk);
+      yr[q] = g * s_re[kk];
+      const float im = g * s_im[kk];
+      yi[q] = k <= FMT_HALF ? im : -im;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < FMT_PER; ++q) {
+      const int v = fmt_rev(tid + q * PCM_THREADS);
+      s_re[v] = yr[q];
+      s_im[v] = yi[q];
+    }
+    __syncthreads();
+    fmt_stages(s_re, s_im, s_tr, s_ti, true, tid);
+    // 8. the windowed frame, quarter q onto hop block lj - 3 + q: the block's first frame (q = 3) sets, the others add
+#pragma unroll
+    for (int q = 0; q < FMT_PER; ++q) {
+      const int n = tid + q * PCM_THREADS, lb = lj - 3 + q;
+      if (lb < lb0 || lb >= lb1) continue;  // a block of another group
+      const float sc = 0.0009765625f * s_re[n];
+      const float v = s_w[n] * sc;
+      float* a = s_acc + ((lb & 3) * FMT_H + tid);
+      *a = q == 3 ? v : *a + v;
+    }
+    if (lj - 3 >= lb0) {  // block lj - 3 has its four frames
+      const int nl = (lj - 3) * FMT_H + tid;
+      if (nl < r.n_out) o[nl] = two_thirds * s_acc[((lj - 3) & 3) * FMT_H + tid];
+    }
+    __syncthreads();  // (the next frame overwrites s_re)
+  }
+}
+
+// The formant rule's steps 2 to 6: the power, its smoothing, the envelope at k Fn / Fd over the envelope at k
+struct FormantGain {
+  float *s_P, *s_E, *s_G;
+  const float* s_c;
+  int Fn, Fd;
+  __device__ __forceinline__ void prepare(const float* s_re, const float* s_im, long long, int tid) {
+#pragma clang fp contract(off)
+    const float eps = 1e-10f, g2_lo = 1.f / 256.f, g2_hi = 256.f;
     // 2. the power of bins 0 .. N / 2
     for (int k = tid; k < FMT_BINS; k += PCM_THREADS) {
       const float a = s_re[k] * s_re[k], b = s_im[k] * s_im[k];
@@ -908,41 +949,83 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_formant_kernel(PcmRows rows, 
       s_G[k] = sqrtf(g2);  // (the correctly rounded one: the Makefile compiles this file with IEEE fp32 / and sqrt)
     }
     __syncthreads();
-    // 7. Y = G X on 0 .. N / 2 and its Hermitian extension, through registers to bit-reversed places
-    float yr[FMT_PER], yi[FMT_PER];
-#pragma unroll
-    for (int q = 0; q < FMT_PER; ++q) {
-      const int k = tid + q * PCM_THREADS, kk = k <= FMT_HALF ? k : FMT_N - k;
-      const float g = s_G[kk];
-      yr[q] = g * s_re[kk];
-      const float im = g * s_im[kk];
-      yi[q] = k <= FMT_HALF ? im : -im;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < FMT_PER; ++q) {
-      const int v = fmt_rev(tid + q * PCM_THREADS);
-      s_re[v] = yr[q];
-      s_im[v] = yi[q];
-    }
-    __syncthreads();
-    fmt_stages(s_re, s_im, s_tr, s_ti, true, tid);
-    // 8. the windowed frame, quarter q onto hop block lj - 3 + q: the block's first frame (q = 3) sets, the others add
-#pragma unroll
-    for (int q = 0; q < FMT_PER; ++q) {
-      const int n = tid + q * PCM_THREADS, lb = lj - 3 + q;
-      if (lb < lb0 || lb >= lb1) continue;  // a block of another group
-      const float sc = 0.0009765625f * s_re[n];
-      const float v = s_w[n] * sc;
-      float* a = s_acc + ((lb & 3) * FMT_H + tid);
-      *a = q == 3 ? v : *a + v;
-    }
-    if (lj - 3 >= lb0) {  // block lj - 3 has its four frames
-      const int nl = (lj - 3) * FMT_H + tid;
-      if (nl < r.n_out) o[nl] = two_thirds * s_acc[((lj - 3) & 3) * FMT_H + tid];
-    }
-    __syncthreads();  // (the next frame overwrites s_re)
   }
+  __device__ __forceinline__ float operator()(int k) const { return s_G[k]; }
+};
+
+// The mark rule's gain (llmvox.h, "PCM mark"): the word of the frame's block, then a bit of it per pair of sub-bands.
+// No LDS of its own beyond the table's 64 words, and no barrier.
+struct MarkGain {
+  const uint16_t* s_tab;  // the sign table [MRK_P]
+  float gp, gm;           // 1 + a, 1 - a
+  unsigned word;
+  __device__ __forceinline__ void prepare(const float*, const float*, long long j, int) { word = s_tab[(int)((j / MRK_Q) % MRK_P)]; }
+  __device__ __forceinline__ float operator()(int k) const {
+    const unsigned rel = (unsigned)(k - MRK_K0);
+    if (rel >= (unsigned)(MRK_U * MRK_BW)) return 1.f;
+    const unsigned u = rel / MRK_BW, bit = (word >> (u >> 1)) & 1u;
+    return bit == (u & 1u) ? gp : gm;  // a set bit: g- on the even sub-band, g+ on the odd one
+  }
+};
+
+__global__ __launch_bounds__(PCM_THREADS) void pcm_formant_kernel(PcmRows rows, int Fn, int Fd, const float* __restrict__ pcm,
+                                                                  int n_in, const float* __restrict__ tab, float* hist,
+                                                                  unsigned char* __restrict__ out, long long out_stride,
+                                                                  int group) {
+  const PcmRow r = rows.r[blockIdx.y];
+  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
+  const int tid = threadIdx.x;
+  const long long t1 = r.t0 + n_in;  // inputs of the segment once this call is consumed
+  const SegInput<FMT_HIST> input{x, hist, r.t0, t1, r.hist_in};
+  if (blockIdx.x == 0 && r.hist_out >= 0) fmt_keep_history(input, hist, r.hist_out, t1, tid);
+
+  const int n_blocks = (r.n_out + FMT_H - 1) / FMT_H;  // hop blocks of this call (the last may be cut by a final call)
+  const int lb0 = blockIdx.x * group;                  // the group's first, counted from the call's first
+  if (lb0 >= n_blocks) return;
+  const int lb1 = min(lb0 + group, n_blocks);
+  const long long b_first = r.m0 / FMT_H;  // (m0 is a multiple of H: only a final call emits part of a block)
+
+  __shared__ float s_re[FMT_N], s_im[FMT_N], s_acc[FMT_N], s_w[FMT_N];
+  __shared__ float s_tr[FMT_HALF], s_ti[FMT_HALF], s_c[FMT_TAPS];
+  __shared__ float s_P[FMT_BINS], s_E[FMT_BINS], s_G[FMT_BINS];
+  fmt_load_tables(tab, s_w, s_tr, s_ti, tid);
+  if (tid < FMT_TAPS) s_c[tid] = tab[FMT_N + tid];
+  __syncthreads();
+
+  FormantGain gain{s_P, s_E, s_G, s_c, Fn, Fd};
+  fmt_frames(r, input, reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride), lb0, lb1, b_first, s_re, s_im, s_acc,
+             s_w, s_tr, s_ti, gain, tid);
+}
+
+// ---- PCM mark (llmvox.h, "PCM mark"): the watermark, the formant stage's transform under a table of signs ----
+// The formant kernel's grid, group, frame loop and ring (fmt_frames); the gain of a bin is a bit of the block's word,
+// so the kernel needs no power, envelope or gain arrays. The table's 128 bytes arrive as an argument.
+__global__ __launch_bounds__(PCM_THREADS) void pcm_mark_kernel(PcmRows rows, MarkTab mt, float a, const float* __restrict__ pcm,
+                                                               int n_in, const float* __restrict__ tab, float* hist,
+                                                               unsigned char* __restrict__ out, long long out_stride, int group) {
+  const PcmRow r = rows.r[blockIdx.y];
+  const float* __restrict__ x = pcm + (size_t)r.row * (size_t)n_in;
+  const int tid = threadIdx.x;
+  const long long t1 = r.t0 + n_in;
+  const SegInput<FMT_HIST> input{x, hist, r.t0, t1, r.hist_in};
+  if (blockIdx.x == 0 && r.hist_out >= 0) fmt_keep_history(input, hist, r.hist_out, t1, tid);
+
+  const int n_blocks = (r.n_out + FMT_H - 1) / FMT_H;
+  const int lb0 = blockIdx.x * group;
+  if (lb0 >= n_blocks) return;
+  const int lb1 = min(lb0 + group, n_blocks);
+  const long long b_first = r.m0 / FMT_H;
+
+  __shared__ float s_re[FMT_N], s_im[FMT_N], s_acc[FMT_N], s_w[FMT_N];
+  __shared__ float s_tr[FMT_HALF], s_ti[FMT_HALF];
+  __shared__ uint16_t s_mt[MRK_P];
+  fmt_load_tables(tab, s_w, s_tr, s_ti, tid);
+  if (tid < MRK_P) s_mt[tid] = mt.w[tid];
+  __syncthreads();
+
+  MarkGain gain{s_mt, 1.f + a, 1.f - a, 0u};
+  fmt_frames(r, input, reinterpret_cast<float*>(out + (size_t)r.row * (size_t)out_stride), lb0, lb1, b_first, s_re, s_im, s_acc,
+             s_w, s_tr, s_ti, gain, tid);
 }
 
 // ---- PCM pause (llmvox.h, "PCM pause"): one slot a block of 10 ms, a copy and one vote ----
@@ -1070,18 +1153,30 @@ void pcm_launch_pause(const PauseRows& rows, int n_rows, int max_blocks, int bl,
   }
 }
 
-void pcm_launch_formant(const PcmRows& rows, int n_rows, int max_out, int Fn, int Fd, const float* pcm, int n_in,
-                        const float* tab, float* hist, float* out, long long out_stride, hipStream_t s) {
-  const int blocks = (max_out + FMT_H - 1) / FMT_H;
-  // the smallest group at which the launch has at most FMT_WGS workgroups (measured: DESIGN 4, "The formant: a
-  // short-time Fourier correction of the spectral envelope", "Which group")
+// hop blocks a workgroup of the formant and mark kernels writes: the option's, or the smallest group at which the
+// launch has at most FMT_WGS workgroups (measured: DESIGN 4, "The formant: a short-time Fourier correction of the
+// spectral envelope", "Which group")
+static int fmt_group_of(int blocks, int n_rows) {
   int group = opts().fmt_group;
   if (group == 0) {
     const int per_row = std::max(1, FMT_WGS / n_rows);
     group = std::min(std::max(1, (blocks + per_row - 1) / per_row), FMT_GROUP_MAX);
   }
+  return group;
+}
+
+void pcm_launch_formant(const PcmRows& rows, int n_rows, int max_out, int Fn, int Fd, const float* pcm, int n_in,
+                        const float* tab, float* hist, float* out, long long out_stride, hipStream_t s) {
+  const int blocks = (max_out + FMT_H - 1) / FMT_H, group = fmt_group_of(blocks, n_rows);
   pcm_formant_kernel<<<dim3((unsigned)std::max(1, (blocks + group - 1) / group), (unsigned)n_rows), PCM_THREADS, 0, s>>>(
       rows, Fn, Fd, pcm, n_in, tab, hist, (unsigned char*)out, out_stride, group);
+}
+
+void pcm_launch_mark(const PcmRows& rows, int n_rows, int max_out, const MarkTab& mt, float a, const float* pcm, int n_in,
+                     const float* tab, float* hist, float* out, long long out_stride, hipStream_t s) {
+  const int blocks = (max_out + FMT_H - 1) / FMT_H, group = fmt_group_of(blocks, n_rows);
+  pcm_mark_kernel<<<dim3((unsigned)std::max(1, (blocks + group - 1) / group), (unsigned)n_rows), PCM_THREADS, 0, s>>>(
+      rows, mt, a, pcm, n_in, tab, hist, (unsigned char*)out, out_stride, group);
 }
 
 void pcm_launch_flac(const FlacRows& rows, int n_rows, int max_frames, int bs, const int16_t* s16, int n_in,

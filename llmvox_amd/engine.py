@@ -20,6 +20,13 @@ def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _mark_key(key) -> int:
+    # (ctypes would wrap a key outside 64 bits silently; the message does not repeat the key)
+    if isinstance(key, bool) or not isinstance(key, int) or not 0 <= key < 1 << 64:
+        raise ValueError("the watermark key must be an integer in 0 .. 2^64 - 1")
+    return key
+
+
 class Engine:
     def __init__(self, device_index: int = 0, weight_dtype: str = "fp32", kv_dtype: str = "fp32",
                  max_streams: int = 8, max_positions: int = 8192, max_codec_frames: int = 1280,
@@ -506,6 +513,26 @@ class Engine:
                                             width * 4, cnt, self.stream_handle()))
         return out, list(cnt)
 
+    def pcm_mark_table(self, key: int, mark_id: int = 0):
+        """uint16 [64]: the watermark's sign table of (key, id) as the library builds it (lvx_pcm_mark_table)."""
+        words = np.zeros(64, dtype=np.uint16)
+        _lib.check(self.lib.lvx_pcm_mark_table(_mark_key(key), int(mark_id), words.ctypes.data_as(ctypes.c_void_p),
+                                               words.size))
+        return words
+
+    def pcm_mark(self, pcm: Optional[torch.Tensor], slots, finals, key: int, mark_id: int = 0, strength: int = 2):
+        """The watermark alone (lvx_pcm_mark): rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0:
+        flush only) continue the mark segments of ``slots`` under the 64-bit ``key``, the payload ``mark_id``
+        (0 .. 255) and ``strength`` (1 .. 3); a true ``finals[b]`` emits the held-back 768 .. 1023 samples too and
+        ends row b's segment. Returns (out, counts): a device float32 tensor [B, width] whose row b holds counts[b]
+        samples. Asynchronous on the current stream; a slot's calls must be issued in order on one stream."""
+        pcm, n_in, B, sl, fl, cnt, _ = self._pcm_args(pcm, slots, finals)
+        width = (n_in + 1023 + 7) // 8 * 8  # (the call's inputs and the held-back <= 1023; rows on 16-byte boundaries)
+        out = torch.empty(B, width, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.lvx_pcm_mark(self.h, _ptr(pcm) if n_in else None, B, n_in, sl, fl, _mark_key(key),
+                                         int(mark_id), int(strength), _ptr(out), width * 4, cnt, self.stream_handle()))
+        return out, list(cnt)
+
     def pcm_convert(self, pcm: Optional[torch.Tensor], slots, finals, fmt, ctx_frames=None):
         """Rows of ``pcm`` (device float32 [B, n_in] at 24 kHz; None or n_in 0: flush only) continue the
         segments of ``slots``; a true ``finals[b]`` flushes row b's filter and ends its segment. ``fmt``: an
@@ -514,7 +541,8 @@ class Engine:
         order, each only where the format needs it, so that a format makes exactly the calls of the stages it uses: the
         dump join (lvx_pcm_join, a format with ``join``: row b with ``ctx_frames[b]`` frames of context in front, None:
         none anywhere), the time stretch at the plan's stretch_pct (lvx_pcm_stretch), the resampling by the plan's
-        L / M (lvx_pcm_ratio), the envelope correction by the plan's Fn / Fd (lvx_pcm_formant), the gain and limiter at
+        L / M (lvx_pcm_ratio), the envelope correction by the plan's Fn / Fd (lvx_pcm_formant), the watermark of a
+        format with a ``mark_key`` (lvx_pcm_mark), the gain and limiter at
         volume_pct (lvx_pcm_level), the rate and the encoding (lvx_pcm_convert). A "flac" format runs that last stage as
         s16le and one more behind it (lvx_pcm_flac): its rows are uint8, whole slots of LVX_FLAC_SLOT bytes (a record
         and a subframe each; ``audio.FlacMux`` makes them frames), and counts[b] is their bytes. A format that
@@ -536,6 +564,8 @@ class Engine:
             stages.append(lambda sub, sl, fl: self.pcm_ratio(sub, sl, fl, L, M))
         if Fn != Fd:
             stages.append(lambda sub, sl, fl: self.pcm_formant(sub, sl, fl, Fn, Fd))
+        if fmt.mark_key is not None:  # the watermark: behind the formant, in front of the limiter
+            stages.append(lambda sub, sl, fl: self.pcm_mark(sub, sl, fl, fmt.mark_key, fmt.mark_id, fmt.mark_strength))
         if vol != 100:
             stages.append(lambda sub, sl, fl: self.pcm_level(sub, sl, fl, vol)[:2])
         # The rate and the encoding come last. At 24 kHz f32le they have nothing to do and the output of the stage

@@ -421,11 +421,27 @@ def formant_pct_of(formant) -> Optional[int]:
     return pct
 
 
+def watermark_of(value) -> bool:
+    """A request's ``watermark``: true or false and nothing else (ValueError: a number, a string, anything)."""
+    if not isinstance(value, bool):
+        raise ValueError(f"watermark must be true or false, got {value!r}")
+    return value
+
+
+def watermark_id_of(value) -> int:
+    """A watermark payload: an integer in 0 .. 255 (ValueError: a bool, a float, a string, out of range)."""
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= 255:
+        raise ValueError(f"watermark_id must be an integer in 0 .. 255, got {value!r}")
+    return value
+
+
 def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int = 0, sample_rate: int = 24000,
                encoding: str = "f32le", container: str = "raw", speed: float = 1.0, top_p: float = 1.0,
                min_p: float = 0.0, repetition_penalty: float = 1.0, repetition_window: int = 64, pitch: float = 1.0,
                join: bool = False, volume: float = 1.0, frame_ms: Optional[int] = None,
-               formant: Optional[float] = None, pause_ms: Optional[int] = None, max_pause_ms: Optional[int] = None):
+               formant: Optional[float] = None, pause_ms: Optional[int] = None, max_pause_ms: Optional[int] = None,
+               watermark: bool = False, watermark_key: Optional[int] = None, watermark_id: int = 0,
+               watermark_strength: int = 2):
     """FastAPI app with the reference's /tts contract (TTSRequest {text} -> octet-stream), its root
     info endpoint and its CORS policy (every origin, streaming_server.py:97-104, so a browser client
     on another origin can stream; ``cors=False`` leaves it off). A request may add ``temperature``
@@ -476,6 +492,14 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
     not and the host trims by whole blocks (``audio.pause_ref``), which holds back up to 10 ms of every sentence until
     its end; a bool, a float, a value out of range or either field with "flac": 422; the response carries them in
     ``X-Audio-Pause`` / ``X-Audio-Max-Pause`` ("none" where absent).
+    ``watermark`` (true or false; absent: the server's default, ``watermark`` here; anything else: 422) asks for the
+    synthetic-speech mark: the PCM passes the mark stage on the device behind the formant stage and in front of the
+    limiter (``audio.mark_ref``) under the server's ``watermark_key`` (a 64-bit integer, which no response, header,
+    error text or info endpoint repeats) at ``watermark_strength`` (1 .. 3), which holds back 32 .. 43 ms of every
+    sentence until more arrives or it ends; ``watermark_id`` (an integer in 0 .. 255; absent: the server's; a bool, a
+    float or anything else: 422) is the payload byte ``audio.mark_detect`` reads back. A server whose default is to
+    mark needs a key: without one ``create_app`` raises ValueError; a request that asks for a mark of a server without
+    a key: 422. The response says which in ``X-Audio-Watermark`` (0 or 1).
     The reference's /voicechat, /multimodalchat and /vlmschat differ from /tts only in the
     producer (ASR / multimodal LLM, out of scope): their speech path is this one."""
     from fastapi import FastAPI, HTTPException
@@ -491,6 +515,13 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                       "repetition_window": repetition_window}
     default_audio = AudioFormat(sample_rate, encoding, container, speed_pct_of(speed), pitch_pct_of(pitch), join,
                                 volume_pct_of(volume), formant_pct_of(formant), pause_ms, max_pause_ms)
+    if not isinstance(watermark, bool):
+        raise ValueError(f"watermark must be true or false, got {watermark!r}")
+    if watermark and watermark_key is None:
+        raise ValueError("watermark is on but there is no watermark key: name one (--watermark-key, a 64-bit integer)")
+    # (validated at start-up, with or without a key; never printed)
+    mark_defaults = AudioFormat(mark_key=watermark_key, mark_id=watermark_id_of(watermark_id),
+                                mark_strength=watermark_strength)
     default_frame_ms = frame_ms_of(frame_ms)
     if default_frame_ms is not None and default_audio.encoding == "flac":
         raise ValueError("frame_ms with encoding 'flac': FLAC frames have no fixed byte size")
@@ -515,10 +546,18 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
         frame_ms: Any = None  # (checked by frame_ms_of: an integer of audio.FRAME_MS, no bool, no float)
         pause_ms: Any = None  # (checked by AudioFormat, as max_pause_ms is: integers, no bool, no float)
         max_pause_ms: Any = None
+        watermark: Any = None  # (checked by watermark_of: true or false; null: the server's default)
+        watermark_id: Any = None  # (checked by watermark_id_of: an integer in 0 .. 255, no bool, no float)
 
     def audio_of(request):
         """The request's AudioFormat (the defaults for the fields it does not name)."""
         try:
+            marked = watermark if request.watermark is None else watermark_of(request.watermark)
+            mark_id = mark_defaults.mark_id if request.watermark_id is None else watermark_id_of(request.watermark_id)
+            if marked and mark_defaults.mark_key is None:
+                raise ValueError("watermark: this server has no watermark key")
+            mark = {"mark_key": mark_defaults.mark_key, "mark_id": mark_id,
+                    "mark_strength": mark_defaults.mark_strength} if marked else {}
             return AudioFormat(default_audio.sample_rate if request.sample_rate is None else request.sample_rate,
                                default_audio.encoding if request.encoding is None else request.encoding,
                                default_audio.container if request.container is None else request.container,
@@ -529,7 +568,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                default_audio.formant_pct if request.formant is None
                                else formant_pct_of(request.formant),
                                default_audio.pause_ms if request.pause_ms is None else request.pause_ms,
-                               default_audio.max_pause_ms if request.max_pause_ms is None else request.max_pause_ms)
+                               default_audio.max_pause_ms if request.max_pause_ms is None else request.max_pause_ms,
+                               **mark)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
 
@@ -594,7 +634,8 @@ def create_app(service, cors: bool = True, temperature: float = 0.0, top_k: int 
                                           "X-Audio-Frame-Ms": str(ms or 0),
                                           "X-Audio-Pause": "none" if fmt.pause_ms is None else str(fmt.pause_ms),
                                           "X-Audio-Max-Pause": "none" if fmt.max_pause_ms is None
-                                          else str(fmt.max_pause_ms)})
+                                          else str(fmt.max_pause_ms),
+                                          "X-Audio-Watermark": "1" if fmt.marks else "0"})
 
     @app.get("/health")
     def health():
@@ -654,6 +695,14 @@ def arg_parser():
     ap.add_argument("--max-pause-ms", type=int, default=None,
                     help="longest silence inside a sentence of requests that name none, in ms (a multiple of 10 in "
                          "100 .. 2000; default: none)")
+    ap.add_argument("--watermark", action="store_true",
+                    help="mark the speech of requests that do not name `watermark` as synthetic (needs --watermark-key)")
+    ap.add_argument("--watermark-key", type=lambda v: int(v, 0), default=None,
+                    help="the watermark's 64-bit key, an integer (0x... for hexadecimal); needed by --watermark and by any "
+                         "request that asks for a mark; keep it secret: it is what the detector needs")
+    ap.add_argument("--watermark-id", type=int, default=0, help="the payload byte of marked requests that name none (0 .. 255)")
+    ap.add_argument("--watermark-strength", type=int, default=2, choices=[1, 2, 3],
+                    help="the mark's depth: 1/64, 1/32 or 1/16 of a sub-band's amplitude (default 2)")
     ap.add_argument("--join", action="store_true",
                     help="click-free dump joins for requests that do not name `join` (context frames and a crossfade)")
     return ap
@@ -665,12 +714,16 @@ def app_options(a) -> dict:
                 container=a.container, speed=a.speed, top_p=a.top_p, min_p=a.min_p,
                 repetition_penalty=a.repetition_penalty, repetition_window=a.repetition_window, pitch=a.pitch,
                 join=a.join, volume=a.volume, frame_ms=a.frame_ms, formant=a.formant, pause_ms=a.pause_ms,
-                max_pause_ms=a.max_pause_ms)
+                max_pause_ms=a.max_pause_ms, watermark=a.watermark, watermark_key=a.watermark_key,
+                watermark_id=a.watermark_id, watermark_strength=a.watermark_strength)
 
 
 def main(argv=None):
     """python -m llmvox_amd.server [--port 8000] [--dtype bf16] [--ckpt ... --wavtokenizer ...]"""
-    a = arg_parser().parse_args(argv)
+    ap = arg_parser()
+    a = ap.parse_args(argv)
+    if a.watermark and a.watermark_key is None:  # (before the engines are built: the reason, and nothing started)
+        ap.error("--watermark needs --watermark-key: without a key no request can be marked")
     from .engine import build_engine
     from . import weights as W
     gw, cw, tt = W.synthetic_all(a.seed)

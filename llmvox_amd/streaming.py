@@ -528,7 +528,7 @@ class _PcmPass:
     must reach the engine in dump order, whatever order the codec groups are decoded in, and no call may
     name a slot twice: ``run()`` converts, in rounds, every dump that is the next one of its stream and
     whose codec call has been queued, one ``pcm_convert`` per (codec call, rate, encoding, speed, pitch, join, volume,
-    formant, pauses or not), and leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
+    formant, pauses or not, the mark), and leaves the others for the ``run()`` after a later group. A dump without tokens is a flush (no codec call)."""
 
     def __init__(self, sched, dumps, finals):
         self.sched, self.dumps, self.finals = sched, dumps, finals
@@ -562,7 +562,8 @@ class _PcmPass:
                     continue
                 buckets.setdefault((id(self.where[i][0]), st.audio.sample_rate, st.audio.encoding,
                                     st.audio.speed_pct, st.audio.pitch_pct, st.audio.join, st.audio.volume_pct,
-                                    st.audio.formant_pct, st.audio.pauses),
+                                    st.audio.formant_pct, st.audio.pauses, st.audio.mark_key, st.audio.mark_id,
+                                    st.audio.mark_strength),
                                    []).append(i)
             if not buckets:
                 return calls
