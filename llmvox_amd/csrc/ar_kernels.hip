@@ -51,16 +51,18 @@ __device__ uint64_t g_lvx_ts[16 * 4 * TS_BLOCKS * 4];
 
 // ---------------------------------------------------------------------------------
 // GEMV family: out[b][n] = sum_k W[n][k] * in[b][k]   (W row-major [N][K], TW in {f32,bf16})
-// IN / OUT: the GIN_ / GOUT_ codes of ar_plan.h, where the mode codes of every kernel family of this
+// IN / OUT: the GIN_ / OUT_ codes of ar_plan.h, where the mode codes of every kernel family of this
 // file are listed once. The LayerNorm is eps 1e-5, no bias (src/model.py:37-38); GIN_EMBED builds
 // x[b] first (a2-a4: text row, codebook row of the previous token or 0 at position 0, L2-normalise
 // eps 1e-8, + wpe[pos]; or, for the drop-in row forward, the caller's row + wpe[pos]), block 0
-// stores it, then LayerNorm. GOUT_QKV: q -> st.q, k/v -> KV cache at the slot's position.
+// stores it, then LayerNorm. OUT_QKV: q -> st.q, k/v -> KV cache at the slot's position.
 // A block is 4 waves; KW waves share the K range of the same RPW rows (KW in {1,4}). Each
 // lane owns 4-element K chunks. All weight loads of the wave are issued before the input
 // prologue (they do not depend on it), so the HBM/MALL latency overlaps the LN / merge /
 // embed work, and the weights stay in registers across batch groups of BG rows.
 // ---------------------------------------------------------------------------------
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // Operand rows (bf16 [B][K]) in MFMA-fragment order, the B operand of v_mfma_f32_16x16x32_bf16 as
 // the batched GEMMs load it: element (b, k) of tile b / 16, k-step k / 32, lane 16 ((k / 8) % 4) + b % 16,
 // slot k % 8 — one wave-wide 16-B load reads one contiguous KB (row-major: 16 rows x 64 B)
@@ -257,7 +259,7 @@ typedef __attribute__((address_space(1))) unsigned long long gu64;
 typedef __attribute__((address_space(1))) unsigned gu32;
 typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
 
-// Deferred select: lm_head (GOUT_LOGITS_GRAN) leaves one 16-byte granule {index << 32 | top1 bits, top2 bits}
+// Deferred select: lm_head (OUT_LOGITS_GRAN) leaves one 16-byte granule {index << 32 | top1 bits, top2 bits}
 // per (block, row) in st.lmbest; the next step's c_attn layer 0 (GIN_EMBED_SELECT) or ar_select_final_kernel
 // reduces a row's 512 granules with one wave: every load in flight at once, then a shuffle tree.
 static_assert(NSPLIT == 16, "the split merges reduce one head's splits as one 16-lane DPP row");
@@ -279,7 +281,7 @@ __device__ __forceinline__ Best lmg_reduce(const LmGran& q) {
   return best_wave(r);
 }
 
-// Batched deferred select at 4 <= B <= 8 (SEL_LN_GRAN): lm_head (ar_mfma_ln_kernel MLOUT_LOGITS, 16 vocabulary
+// Batched deferred select at 4 <= B <= 8 (SEL_LN_GRAN): lm_head (ar_mfma_ln_kernel OUT_LOGITS, 16 vocabulary
 // rows per block) leaves one granule per (block, row) in st.lmbest laid out [256 blocks][8 rows]; the
 // next step's c_attn layer 0 (ar_mfma_ln_kernel MLMODE_EMBED_SELECT) reduces a row's 256 granules with one wave
 constexpr int LM8_BLOCKS = VOCAB / 16;  // (LM8_ROWS: ar_plan.h)
@@ -312,6 +314,13 @@ __device__ __forceinline__ void store_kv(const GemvArgs& a, int which, size_t id
   if (a.kv_dtype == LVX_DTYPE_BF16) reinterpret_cast<bf16_t*>(base)[idx] = f32_to_bf16(v);
   else if (a.kv_dtype == LVX_DTYPE_FP8) reinterpret_cast<fp8_t*>(base)[idx] = f32_to_fp8(v);
   else reinterpret_cast<float*>(base)[idx] = v;
+}
+// column n >= D of c_attn's output (k: D <= n < 2 D, v above) appended at control record rec's (slot, position)
+__device__ __forceinline__ void kv_append(const GemvArgs& a, int4 rec, int n, float v) {
+  const int c = (n - D) % D, which = (n - D) / D;
+  const int head = c / HD, d = c - head * HD;
+  if (rec.x < 0) return;
+  store_kv(a, which, kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, rec.x, head, rec.y) + d, v);
 }
 
 template <typename TW> struct WReg;
@@ -472,7 +481,7 @@ __device__ __forceinline__ void gemv_stage_input(const GemvArgs& a, float* xs, f
         if (blockIdx.x == 0)
 #pragma unroll
           for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + j * 256 + lane * 4) = v[j];
-      } else {
+      } else {  // embed_row written out (its older form: the wpe row clamped, the error bit from block 0 alone)
         const int4 ri = pre ? ripre : a.st.rowinfo[b];  // {slot, pos, text id, prev}, validated by the producer
         if (ri.x < 0) {
 #pragma unroll
@@ -609,13 +618,13 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
   // control record of this lane's epilogue row in the first batch group (bb = lane % BG): the
   // KV append needs (slot, pos); loading it here keeps it off the epilogue's critical path
   int4 riep = make_int4(-1, 0, 0, 0);
-  if (OUT == GOUT_QKV && IN != GIN_EMBED_SELECT) riep = a.st.rowinfo[min(lane % BG, a.B - 1)];
-  // residual epilogue (GOUT_RESID): this lane's (row, batch row) of the first group is (row0 + lane / BG,
+  if (OUT == OUT_QKV && IN != GIN_EMBED_SELECT) riep = a.st.rowinfo[min(lane % BG, a.B - 1)];
+  // residual epilogue (OUT_RESID): this lane's (row, batch row) of the first group is (row0 + lane / BG,
   // lane % BG); its x element (and, for c_proj after a fused MLP, the pending accumulators) is
   // loaded now instead of behind the dot products
   float xep = 0.f;
   unsigned long long yep[YCOPIES];
-  if constexpr (OUT == GOUT_RESID) {
+  if constexpr (OUT == OUT_RESID) {
     const int n = row0 + lane / BG, b = lane % BG;
     if (lane < RPW * BG && n < a.N && b < a.B) {
       xep = a.st.x[(size_t)b * D + n];
@@ -741,10 +750,10 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
         if (bb >= bg || n >= a.N || lane != ((r * BG + bb) & 63)) continue;
         const float v = acc[r][bb];
         const int b = g0 + bb;
-        if (OUT == GOUT_QKV) {
+        if (OUT == OUT_QKV) {
           if (n < D) {
             a.st.q[(size_t)b * D + n] = v;
-          } else {
+          } else {  // kv_append written out (the B <= 2 cells: shared, 9 of these kernels changed their occupancy)
             const int c = (n - D) % D, which = (n - D) / D;
             const int head = c / HD, d = c - head * HD;
             const int4 ri = IN == GIN_EMBED_SELECT ? ri_s[bb] : g0 == 0 ? riep : a.st.rowinfo[b];
@@ -754,7 +763,7 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
                 kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, s, head, p) + d;
             store_kv(a, which, idx, v);
           }
-        } else if (OUT == GOUT_RESID) {
+        } else if (OUT == OUT_RESID) {
           float* xp = a.st.x + (size_t)b * D + n;
           float t = g0 == 0 ? xep : *xp;
           if (IN == GIN_MERGE && a.yfx) {  // c_proj: fold the fused MLP's accumulators into x and clear them
@@ -768,16 +777,16 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
             if (a.add_y) t += yfx_to_f(ys);
           }
           *xp = t + v;
-        } else if (OUT == GOUT_GELU) {
+        } else if (OUT == OUT_GELU) {
           a.st.h[(size_t)b * DFF + n] = gelu_tanh(v);
         } else {
           a.dst[(size_t)b * a.N + n] = v;
-          if (OUT == GOUT_LOGITS_GRAN) part[wave][r][bb] = v;
+          if (OUT == OUT_LOGITS_GRAN) part[wave][r][bb] = v;
         }
       }
     }
   }
-  if constexpr (OUT == GOUT_LOGITS_GRAN) {
+  if constexpr (OUT == OUT_LOGITS_GRAN) {
     // deferred select: this block's top1/top2 per row as one granule (plain store; the next
     // kernel boundary publishes it) and the pending flag
     __syncthreads();
@@ -799,31 +808,44 @@ __global__ __launch_bounds__(256) void ar_gemv_kernel(GemvArgs a) {
   }
 }
 
-// GEMV / batched-GEMM epilogue store of output n of batch row b
+// A wave's partial 16 x (NT * 16) MFMA tile into its LDS slab, element (row r, column c) at r * (NT * 16) + c:
+// lane holds C[4 (lane >> 4) + i][t * 16 + (lane & 15)], i = 0..3
+template <int NT>
+__device__ __forceinline__ void tile_put(float* red, const f32x4_t (&acc)[NT], int lane) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[(4 * (lane >> 4) + i) * (NT * 16) + t * 16 + (lane & 15)] = acc[t][i];
+}
+// element e of the tile: the NW waves' partials (slabs LD floats apart) summed in wave order (deterministic)
+template <int NW, int LD>
+__device__ __forceinline__ float tile_sum(const float* red, int e) {
+  float v = 0.f;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) v += red[w * LD + e];
+  return v;
+}
+
+// The step's epilogue store (OUT: ArOut) of output n of batch row b, for every batched GEMM family; ks of nks: the
+// K slice of an OUT_SPLITK block. (ar_gemv_kernel's epilogue has its operands prefetched and is its own.)
 template <int OUT>
-__device__ __forceinline__ void gemv_store(const GemvArgs& a, int n, int b, float v) {
-  if (OUT == GOUT_QKV) {
-    if (n < D) {
-      a.st.q[(size_t)b * D + n] = v;
-    } else {
-      const int c = (n - D) % D, which = (n - D) / D;
-      const int head = c / HD, d = c - head * HD;
-      const int4 ri = a.st.rowinfo[b];
-      if (ri.x < 0) return;
-      const size_t idx = kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, ri.x, head, ri.y) + d;
-      store_kv(a, which, idx, v);
-    }
-  } else if (OUT == GOUT_RESID) {
+__device__ __forceinline__ void step_store(const GemvArgs& a, int n, int b, float v, int ks = 0, int nks = YCOPIES) {
+  if (OUT == OUT_QKV) {
+    if (n < D) a.st.q[(size_t)b * D + n] = v;
+    else kv_append(a, a.st.rowinfo[b], n, v);
+  } else if (OUT == OUT_RESID) {
     float* xp = a.st.x + (size_t)b * D + n;
     float t = *xp;
     if (a.yacc && a.add_y)  // c_proj: fold the pending split-K partials of the previous mlp c_proj
 #pragma unroll
       for (int c = 0; c < YCOPIES; ++c) t += a.yacc[((size_t)b * YCOPIES + c) * D + n];
     *xp = t + v;
-  } else if (OUT == GOUT_GELU) {
+  } else if (OUT == OUT_GELU) {
     a.st.h[(size_t)b * DFF + n] = gelu_tanh(v);
-  } else if (OUT == GOUT_SPLITK) {  // split-K partial of mlp c_proj (K slice blockIdx.y) -> pending copy
-    a.yacc[((size_t)b * YCOPIES + blockIdx.y) * D + n] = v;
+  } else if (OUT == OUT_GELU_BF16) {
+    a.st.hb[a.xpk ? xfrag(b, n, DFF) : (size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
+  } else if (OUT == OUT_SPLITK) {  // split-K partial of mlp c_proj -> its pending copy
+    a.yacc[((size_t)b * nks + ks) * D + n] = v;
   } else {
     a.dst[(size_t)b * a.N + n] = v;
   }
@@ -890,6 +912,33 @@ __device__ __forceinline__ void embed_row(const GemvArgs& a, int4 ri, int lane, 
 #pragma unroll
   for (int j = 0; j < 3; ++j)
     v[j] = make_float4(v[j].x / den + pe[j].x, v[j].y / den + pe[j].y, v[j].z / den + pe[j].z, v[j].w / den + pe[j].w);
+}
+
+// One wave: row b of the step, LayerNorm'd, into row dst of a block's LDS operand tile (bf16 or fp32), lane layout
+// k = j * 256 + lane * 4. EMBED: v is the embedding of control record ri, which block 0 also stores as x[b]; else v
+// holds the x row (+ whatever is pending) on entry. live false: a tile row past B, zeros (padded columns, never stored)
+template <bool EMBED, typename T>
+__device__ __forceinline__ void ln_tile_row(const GemvArgs& a, bool live, int b, const int4& ri, float4 (&v)[3],
+                                            const float4 (&g)[3], T* dst, int lane) {
+  static_assert(sizeof(T) == 2 || sizeof(T) == 4, "bf16 or fp32 tile");
+  auto put = [&](int j, float4 x) {
+    if constexpr (sizeof(T) == 2) reinterpret_cast<uint2*>(dst)[j * 64 + lane] = pack4_bf16(x);
+    else *reinterpret_cast<float4*>(dst + j * 256 + lane * 4) = x;
+  };
+  if (live) {
+    if (EMBED) {
+      embed_row(a, ri, lane, v);
+      if (blockIdx.x == 0)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = v[j];
+    }
+    wave_ln_regs(v, g);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) put(j, v[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) put(j, make_float4(0.f, 0.f, 0.f, 0.f));
+  }
 }
 
 // One wave: {1 / den, mean, rstd} of row b's embedding row for record rn, the statistics that layer 0's
@@ -1287,8 +1336,6 @@ __device__ __forceinline__ float slot_fold_wave(float m, float& l, float (&o)[24
 // selcopy). Ordering inside the block is by LDS barriers alone.
 // LA (ArStepPlan::la_fused, layers >= 1 of such a step): the block runs its row's LayerNorm and its head's c_attn
 // rows instead of the tables; described at ar_attn_la_kernel.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // plan_tok(st, b, jn + 1) from the plan element loaded at min(jn + 1, plan_stride - 1) (384 when no plan is bound)
 __device__ __forceinline__ int l0_next_tok(const ArState& st, int jn, int loaded) {
   if (!st.text_plan) return 384;
@@ -1591,7 +1638,7 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   if constexpr (LA) {
     // the history's first tiles are in flight behind the row and the first weight tiles. ar_rows_kernel<RMODE_LN_Y>'s
     // LayerNorm of x + the pending copies by the same functions (xrow_sum, wave_ln_regs, pack4_bf16; every wave, its own LDS copy of
-    // the bf16 row), then this head's 18 column tiles of c_attn as ar_mfma2_kernel<768, 2, M2OUT_QKV> computes
+    // the bf16 row), then this head's 18 column tiles of c_attn as ar_mfma2_kernel<768, 2, OUT_QKV> computes
     // them: wave w owns k in [192 w, 192 w + 192), six k-steps in order, the batch operand the one row
     // replicated over the MFMA's 16 columns (an output element depends on its weight row and its batch column
     // alone), the four K-slice partials summed in wave order. The weights stream through a ring of RT tiles,
@@ -1794,7 +1841,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArg
 // layer-0 form. Grid (1, 8 heads, B): block (row, head) runs ar_rows_kernel<RMODE_LN_Y>'s LayerNorm of its row and
 // its head's 288 of c_attn's 2,304 output rows itself, with the history's first KV tiles in flight, so the
 // step has neither of those two launches at these layers (the pending copies are then folded into x by
-// c_proj: M2OUT_RESID_STATS with add_y). The head's 442 KB weight slice is the same for the B blocks of a
+// c_proj: OUT_RESID_STATS with add_y). The head's 442 KB weight slice is the same for the B blocks of a
 // head, which share an XCD (head = linear block id mod 8): one fetch per XCD, then L2 hits. selcopy (layer
 // 1): the records of the fused layer-0 attention are read from the shadow arrays and copied back by the
 // head-0 block, as layer 0 of the unfused deferred-select forms does.
@@ -2138,12 +2185,12 @@ static void launch_gemv(const GemvArgs& a, hipStream_t s) {
   const int rows_per_block = (4 / KW) * RPW;
   dim3 grid((a.N + rows_per_block - 1) / rows_per_block);
   constexpr int BGMAX = (K == 768) ? 16 : 4;
-  if constexpr (OUT == GOUT_LOGITS_GRAN || IN == GIN_EMBED_SELECT) {  // select variants: one batch group of <= 4 rows (SEL_GRAN: B <= 2)
+  if constexpr (OUT == OUT_LOGITS_GRAN || IN == GIN_EMBED_SELECT) {  // select variants: one batch group of <= 4 rows (SEL_GRAN: B <= 2)
     if (a.B <= 1) hipLaunchKernelGGL((ar_gemv_kernel<TW, K, KW, RPW, 1, IN, OUT>), grid, dim3(256), 0, s, a);
     else if (a.B <= 2) hipLaunchKernelGGL((ar_gemv_kernel<TW, K, KW, RPW, 2, IN, OUT>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((ar_gemv_kernel<TW, K, KW, RPW, 4, IN, OUT>), grid, dim3(256), 0, s, a);
   } else {
-    if constexpr (IN == GIN_MERGE && OUT == GOUT_RESID && K == 768 && KW == 1) {
+    if constexpr (IN == GIN_MERGE && OUT == OUT_RESID && K == 768 && KW == 1) {
       if (a.B == 1) {  // B = 1 c_proj: the split merge once per block, 16 splits
         hipLaunchKernelGGL((ar_cproj_b1_kernel<TW, RPW, NSPLIT>), grid, dim3(256), 0, s, a);
         return;
@@ -2525,21 +2572,39 @@ static void launch_merge_bf16(const ArState& st, int B, int nsm, hipStream_t s, 
   else hipLaunchKernelGGL(ar_merge_bf16_kernel<NSPLIT>, dim3(B), dim3(256), 0, s, st, nsm, xpk);
 }
 
-// OUT: M2OUT_*, XM: M2X_* (ar_plan.h). A block covers K columns starting at blockIdx.y * K of rows
-// of length KTOT (KTOT > K: split K, M2OUT_SPLITK).
+// x[b][n], with a.add_y plus the NC pending copies of the split mlp c_proj: x + c0 + c1 + ..., the order of
+// step_store<OUT_RESID> and of ar_rows_kernel<RMODE_LN_Y> (xrow_sum). The copies are loaded whether or not they are
+// folded: no load under a branch (a.yacc is set on every MFMA step; a null one reads x itself, never folded)
+template <int NC>
+__device__ __forceinline__ float x_plus_copies(const GemvArgs& a, int b, int n) {
+  float t = a.st.x[(size_t)b * D + n];
+  const float* yp = a.yacc ? a.yacc + (size_t)b * NC * D + n : a.st.x + (size_t)b * D + n;
+  const int ys = a.yacc ? D : 0;
+  float yc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) yc[c] = yp[c * ys];
+  if (a.yacc && a.add_y)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) t += yc[c];
+  return t;
+}
+
+// OUT: OUT_*, XM: M2X_* (ar_plan.h). A block covers K columns starting at blockIdx.y * K of rows
+// of length KTOT (KTOT > K: split K, OUT_SPLITK).
 // M2X_LN_AFTER (c_fc): LayerNorm applied after the GEMM. The operand is the bf16 copy of x * ln_2.weight
-// the previous c_proj (M2OUT_RESID_STATS) left, multiplied as it is; the epilogue centres and scales:
+// the previous c_proj (OUT_RESID_STATS) left, multiplied as it is; the epilogue centres and scales:
 // LN2(x) . W^T = rstd * ((x * g) . W^T - mean * G[n]), G = ArWeights::fc_gsum, with (mean, rstd)
 // from the per-row statistics c_proj left in 48 column-block partials (mean, M2 over 16 columns
 // each, combined here with Chan's formula while the operands load): no rows kernel and no
 // per-element normalisation on the operand path (round 2: 4.1 -> ~2.7 us from entry to MFMA).
-// M2OUT_RESID_STATS (c_proj): x += v, plus that bf16 copy (x * ln_2.weight) and this block's (mean, M2)
+// OUT_RESID_STATS (c_proj): x += v, plus that bf16 copy (x * ln_2.weight) and this block's (mean, M2)
 // of its 16 columns.
 template <int K, int NT, int OUT, int KTOT = K, int XM = 0>
 __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
   constexpr int NW = K / 192;  // waves per block, each a 192-wide K slice (6 MFMA k-steps)
+  static_assert(XM != M2X_LN_AFTER || OUT == OUT_GELU_BF16, "LayerNorm after the GEMM: c_fc alone");
   __shared__ float red[NW][NT * 256];
-  __shared__ float xo[OUT == M2OUT_RESID_STATS ? 16 * NT * 16 : 1];
+  __shared__ float xo[OUT == OUT_RESID_STATS ? 16 * NT * 16 : 1];
   __shared__ float2 rs[XM == M2X_LN_AFTER ? NT * 16 : 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // XCD-aligned tile order (a.xmap, 1-D grid): workgroups are dealt to the 8 XCDs round robin, so
@@ -2570,57 +2635,31 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
   const int k0 = by * K + wave * 192 + 8 * (lane >> 4);
   // epilogue operands first (a load in the epilogue is one more dependent round trip): thread tid
   // stores elements e = tid + k * NW * 64, all of batch row tid % (NT * 16) (NW * 64 is a multiple
-  // of NT * 16): its control record (M2OUT_QKV, KV append) or its x values (M2OUT_RESID_STATS, residual)
+  // of NT * 16): its control record (OUT_QKV, KV append) or its x values (OUT_RESID_STATS, residual)
   constexpr int EPT = (16 * NT * 16 + NW * 64 - 1) / (NW * 64);
   static_assert((NW * 64) % (NT * 16) == 0, "one batch row per thread in the epilogue");
   int4 ripre = make_int4(-1, 0, 0, 0);
-  float xpre[(OUT == M2OUT_RESID_STATS || OUT == M2OUT_RESID) ? EPT : 1];
-  float gpre[(OUT == M2OUT_RESID_STATS || XM == M2X_LN_AFTER) ? EPT : 1];  // M2OUT_RESID_STATS: ln_2.weight[n]; M2X_LN_AFTER: G[n]
-  if constexpr (OUT == M2OUT_QKV) ripre = a.st.rowinfo[min(r0 + tid % (NT * 16), B - 1)];
-  if constexpr (OUT == M2OUT_RESID) {
-    // (B <= 8 c_proj) x and the MLP's pending copies up front, summed in gemv_store<GOUT_RESID>'s order
-    // (x + c0 + c1 + c2 + c3, then + v): round 3, they were loaded in the epilogue, one more
-    // dependent round trip after the MFMAs. The copies are loaded whether or not they are folded
-    // (add_y: layers >= 1): no load under a branch.
+  float xpre[(OUT == OUT_RESID_STATS || OUT == OUT_RESID) ? EPT : 1];
+  float gpre[(OUT == OUT_RESID_STATS || XM == M2X_LN_AFTER) ? EPT : 1];  // OUT_RESID_STATS: ln_2.weight[n]; M2X_LN_AFTER: G[n]
+  if constexpr (OUT == OUT_QKV) ripre = a.st.rowinfo[min(r0 + tid % (NT * 16), B - 1)];
+  // x and the mlp c_proj's pending copies up front (round 3: loaded in the epilogue they were one more dependent
+  // round trip after the MFMAs). OUT_RESID (B <= 8 c_proj): the YCS copies of that path, folded at layers >= 1;
+  // OUT_RESID_STATS: folded in a step whose c_attn ran inside the attention (no rows kernel folded them).
+  // (One loop for both forms moved a VGPR count across an occupancy step whichever way its index was written.)
+  if constexpr (OUT == OUT_RESID) {
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
       const int e = min(tid + k * NW * 64, 16 * NT * 16 - 1), r = e / (NT * 16), b = min(r0 + e - r * (NT * 16), B - 1);
-      const int n = min(n0 + r, a.N - 1);
-      float t = a.st.x[(size_t)b * D + n];
-      // (a.yacc is set on every MFMA step; a null one reads x itself, never folded)
-      const float* yp = a.yacc ? a.yacc + (size_t)b * YCS * D + n : a.st.x + (size_t)b * D + n;
-      const int ys = a.yacc ? D : 0;
-      float yc[YCS];
-#pragma unroll
-      for (int c = 0; c < YCS; ++c) yc[c] = yp[c * ys];
-      if (a.yacc && a.add_y)
-#pragma unroll
-        for (int c = 0; c < YCS; ++c) t += yc[c];
-      xpre[k] = t;
+      xpre[k] = x_plus_copies<YCS>(a, b, min(n0 + r, a.N - 1));
     }
   }
-  if constexpr (OUT == M2OUT_RESID_STATS || XM == M2X_LN_AFTER) {
+  if constexpr (OUT == OUT_RESID_STATS || XM == M2X_LN_AFTER) {
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
       const int e = min(tid + k * NW * 64, 16 * NT * 16 - 1), r = e / (NT * 16), b = e - r * (NT * 16);
       const int n = min(n0 + r, a.N - 1);
-      if constexpr (OUT == M2OUT_RESID_STATS) {
-        // x, and with add_y (a step whose c_attn ran inside the attention: no rows kernel folded them) the
-        // mlp c_proj's pending copies, summed in ar_rows_kernel<RMODE_LN_Y>'s order (xrow_sum: x + c0 + c1 +
-        // c2 + c3). Loaded whether or not they are folded: no load under a branch.
-        const int br = min(r0 + b, B - 1);
-        float t = a.st.x[(size_t)br * D + n];
-        const float* yp = a.yacc ? a.yacc + (size_t)br * YCOPIES * D + n : a.st.x + (size_t)br * D + n;
-        const int ys = a.yacc ? D : 0;
-        float yc[YCOPIES];
-#pragma unroll
-        for (int c = 0; c < YCOPIES; ++c) yc[c] = yp[c * ys];
-        if (a.yacc && a.add_y)
-#pragma unroll
-          for (int c = 0; c < YCOPIES; ++c) t += yc[c];
-        xpre[k] = t;
-      }
-      gpre[k] = OUT == M2OUT_RESID_STATS ? a.ln_w[n] : a.gsum[n];
+      if constexpr (OUT == OUT_RESID_STATS) xpre[k] = x_plus_copies<YCOPIES>(a, min(r0 + b, B - 1), n);
+      gpre[k] = OUT == OUT_RESID_STATS ? a.ln_w[n] : a.gsum[n];
     }
   }
   // M2X_LN_AFTER: the row statistics partials first (vmcnt retires in issue order, so the Chan combine
@@ -2688,11 +2727,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf[kk]),
                                                        __builtin_bit_cast(bf16x8_t, xf[t][kk]), acc[t], 0, 0, 0);
   TS_MARK(1);
-  // partial 16 x (NT*16) tiles -> LDS, element (row r, col c) at r * (NT*16) + c
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][(4 * (lane >> 4) + i) * (NT * 16) + t * 16 + (lane & 15)] = acc[t][i];
+  tile_put<NT>(red[wave], acc, lane);
   __syncthreads();
 #pragma unroll
   for (int k = 0; k < EPT; ++k) {
@@ -2700,35 +2735,25 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
     if (e >= 16 * NT * 16) break;
     const int r = e / (NT * 16), b = r0 + e - r * (NT * 16), n = n0 + r;
     if (b >= B || n >= a.N) continue;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += red[w][e];
-    if (OUT == M2OUT_QKV && n >= D) {  // K / V append at the row's (slot, pos), record prefetched
-      const int c = (n - D) % D, which = (n - D) / D;
-      const int head = c / HD, d = c - head * HD;
-      if (ripre.x < 0) continue;
-      const size_t idx = kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, ripre.x, head, ripre.y) + d;
-      store_kv(a, which, idx, v);
-    } else if (OUT == M2OUT_GELU_BF16) {
-      if constexpr (XM == M2X_LN_AFTER) {  // LayerNorm after the GEMM: rstd * (v - mean * G[n])
-        const float2 st = rs[b - r0];
-        v = (v - st.x * gpre[k]) * st.y;
-      }
-      a.st.hb[a.xpk ? xfrag(b, n, DFF) : (size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
-    } else if (OUT == M2OUT_RESID_STATS) {
+    float v = tile_sum<NW, NT * 256>(red[0], e);
+    if (OUT == OUT_QKV && n >= D) {  // K / V append at the row's (slot, pos), record prefetched
+      kv_append(a, ripre, n, v);
+    } else if (OUT == OUT_RESID_STATS) {
       const float xn = xpre[k] + v;
       a.st.x[(size_t)b * D + n] = xn;
       a.st.xb[a.xpk ? xfrag(b, n, D) : (size_t)b * D + n] = f32_to_bf16(xn * gpre[k]);
       xo[e] = xn;
-    } else if (OUT == M2OUT_SPLITK) {  // split-K partial of mlp c_proj (K slice by) -> pending copy
-      a.yacc[((size_t)b * (KTOT / K) + by) * D + n] = v;
-    } else if (OUT == M2OUT_RESID) {  // x (+ the folded copies, prefetched) + v
+    } else if (OUT == OUT_RESID) {  // x (+ the folded copies, prefetched) + v
       a.st.x[(size_t)b * D + n] = xpre[k] + v;
     } else {
-      gemv_store<OUT>(a, n, b, v);
+      if constexpr (XM == M2X_LN_AFTER) {  // LayerNorm after the GEMM: rstd * (v - mean * G[n])
+        const float2 st = rs[b - r0];
+        v = (v - st.x * gpre[k]) * st.y;
+      }
+      step_store<OUT>(a, n, b, v, by, KTOT / K);
     }
   }
-  if constexpr (OUT == M2OUT_RESID_STATS) {  // (mean, M2) of this block's 16 columns for every batch row
+  if constexpr (OUT == OUT_RESID_STATS) {  // (mean, M2) of this block's 16 columns for every batch row
     __syncthreads();
     if (tid < NT * 16 && r0 + tid < B) {
       float mean = 0.f;
@@ -2744,7 +2769,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
       reinterpret_cast<float2*>(a.st.xstat)[(size_t)(r0 + tid) * (D / 16) + bx] = make_float2(mean, m2);
     }
   }
-  TS_SAVE(OUT == M2OUT_QKV ? 1 : OUT == M2OUT_RESID_STATS ? 3 : OUT == M2OUT_GELU_BF16 ? 4 : OUT == M2OUT_SPLITK ? 5 : 6, a.layer, blockIdx.x + gridDim.x * blockIdx.y);
+  TS_SAVE(OUT == OUT_QKV ? 1 : OUT == OUT_RESID_STATS ? 3 : OUT == OUT_GELU_BF16 ? 4 : OUT == OUT_SPLITK ? 5 : 6, a.layer, blockIdx.x + gridDim.x * blockIdx.y);
 }
 
 // measured alternatives to the batched v2 layout (round 1/2, us/step at B = 32, t = 256-512), removed:
@@ -2752,6 +2777,15 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
 // c_attn / lm_head from an unsplit mlp c_proj's row statistics (48 blocks of 16 waves: 178 vs 156);
 // the split mlp c_proj combined in-launch by each column tile's last arriving slice (release /
 // acquire fences: 182 vs 157; write-through slabs and sc1 loads, no fences: 171.9 vs 162-168)
+// B -> NT: 16 / 32 / 64 batch rows per block
+template <int K, int OUT, int KTOT, int XM>
+static void launch_mfma2_nt(const GemvArgs& a, dim3 grid, hipStream_t s) {
+  const dim3 block((K / 192) * 64);
+  if (a.B <= 16) hipLaunchKernelGGL((ar_mfma2_kernel<K, 1, OUT, KTOT, XM>), grid, block, 0, s, a);
+  else if (a.B <= 32) hipLaunchKernelGGL((ar_mfma2_kernel<K, 2, OUT, KTOT, XM>), grid, block, 0, s, a);
+  else hipLaunchKernelGGL((ar_mfma2_kernel<K, 4, OUT, KTOT, XM>), grid, block, 0, s, a);
+}
+
 template <int K, int OUT, int XM = 0>
 static void launch_mfma2(const GemvArgs& a, hipStream_t s, bool btile = false) {
   dim3 grid((a.N + 15) / 16), block((K / 192) * 64);
@@ -2764,9 +2798,9 @@ static void launch_mfma2(const GemvArgs& a, hipStream_t s, bool btile = false) {
       return;
     }
     hipLaunchKernelGGL((ar_mfma2_kernel<K, 1, OUT, K, XM>), grid, block, 0, s, a);
-  } else if (a.B <= 16) hipLaunchKernelGGL((ar_mfma2_kernel<K, 1, OUT, K, XM>), grid, block, 0, s, a);
-  else if (a.B <= 32) hipLaunchKernelGGL((ar_mfma2_kernel<K, 2, OUT, K, XM>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((ar_mfma2_kernel<K, 4, OUT, K, XM>), grid, block, 0, s, a);
+  } else {
+    launch_mfma2_nt<K, OUT, K, XM>(a, grid, s);
+  }
 }
 
 // (round 2-5: c_attn at 9 <= B <= 32 as four K-slice partials summed by the attention, the block's
@@ -2782,18 +2816,16 @@ static void launch_mfma2(const GemvArgs& a, hipStream_t s, bool btile = false) {
 template <int OUT>
 static void launch_mproj_split(const GemvArgs& a, hipStream_t s) {
   static_assert(DFF == YCOPIES * 768, "one pending copy per K slice");
-  dim3 grid((a.N + 15) / 16, YCOPIES), block(256);
+  dim3 grid((a.N + 15) / 16, YCOPIES);
   GemvArgs b = a;
   if (YCOPIES == 4 && grid.x % 2 == 0) {  // XCD-aligned order (xmap 1): 1-D grid
     b.xmap = 1;
     grid = dim3(grid.x * 4);
   }
-  if (a.B <= 16) hipLaunchKernelGGL((ar_mfma2_kernel<768, 1, OUT, DFF>), grid, block, 0, s, b);
-  else if (a.B <= 32) hipLaunchKernelGGL((ar_mfma2_kernel<768, 2, OUT, DFF>), grid, block, 0, s, b);
-  else hipLaunchKernelGGL((ar_mfma2_kernel<768, 4, OUT, DFF>), grid, block, 0, s, b);
+  launch_mfma2_nt<768, OUT, DFF, M2X_NONE>(b, grid, s);
 }
 
-// Batched GEMM with the per-row prologue fused (K = 768; small B; OUT: MLOUT_*, MODE: MLMODE_*,
+// Batched GEMM with the per-row prologue fused (K = 768; small B; OUT: OUT_*, MODE: MLMODE_*,
 // ar_plan.h): every block builds the LayerNorm (MLMODE_LN), LayerNorm of x + pending copies
 // (MLMODE_LN_Y) or embedding + LayerNorm (MLMODE_EMBED; block 0 also stores x) of all B rows into
 // an LDS bf16 tile, then runs the MFMA 16 x (NT*16) tile of its 16 weight rows from it. The rows
@@ -2803,17 +2835,17 @@ static void launch_mproj_split(const GemvArgs& a, hipStream_t s) {
 // after committing the previous step's greedy select from lm_head's granules (block 0 writes the state
 // and the shadow records, attention layer 0 copies them back, as the B <= 2 GEMV step's
 // GIN_EMBED_SELECT); every block builds the rows from the new records, which the KV append of the
-// epilogue uses too. MLOUT_LOGITS with SEL_LN_GRAN: the block's top-1 / top-2 per row as one granule,
+// epilogue uses too. OUT_LOGITS with SEL_LN_GRAN: the block's top-1 / top-2 per row as one granule,
 // the pending flag set by block 0.
 template <int NT, int OUT, int MODE>
 __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
   constexpr int K = 768, NW = 4, R = NT * 16, RW = R / NW;  // rows per wave
   constexpr int LDX = K + 8;                                 // bf16 row stride (16-B pad)
-  static_assert(MODE != MLMODE_EMBED_SELECT || (NT == 1 && OUT == MLOUT_QKV), "the deferred select's c_attn: B <= 8");
+  static_assert(MODE != MLMODE_EMBED_SELECT || (NT == 1 && OUT == OUT_QKV), "the deferred select's c_attn: B <= 8");
   constexpr int SR = MODE == MLMODE_EMBED_SELECT ? LM8_ROWS / NW : 1;          // rows per wave that can be live (B <= 8)
   __shared__ __attribute__((aligned(16))) bf16_t xs[R * LDX];
   __shared__ float red[NW][NT * 256];
-  __shared__ float lgs[OUT == MLOUT_LOGITS && NT == 1 ? 16 * 17 : 1];
+  __shared__ float lgs[OUT == OUT_LOGITS && NT == 1 ? 16 * 17 : 1];
   __shared__ int4 ri_s[MODE == MLMODE_EMBED_SELECT ? LM8_ROWS : 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int n0 = blockIdx.x * 16;
@@ -2887,30 +2919,18 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
 #pragma unroll
   for (int i = 0; i < RW; ++i) {
     const int b = wave + NW * i;
-    uint2* dst = reinterpret_cast<uint2*>(xs + b * LDX);
-    if (b < B && (MODE != MLMODE_EMBED_SELECT || i < SR)) {
-      if (MODE == MLMODE_EMBED || MODE == MLMODE_EMBED_SELECT) {
-        embed_row(a, ri[i], lane, xv[i]);
-        if (blockIdx.x == 0)
+    const bool live = b < B && (MODE != MLMODE_EMBED_SELECT || i < SR);
+    if (MODE == MLMODE_LN_Y && live) {  // + the pending split-K copies of the previous mlp c_proj
 #pragma unroll
-          for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = xv[i][j];
-      } else if (MODE == MLMODE_LN_Y) {  // + the pending split-K copies of the previous mlp c_proj
+      for (int c = 0; c < YCS; ++c)
 #pragma unroll
-        for (int c = 0; c < YCS; ++c)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {
-            const float4 y = i < YR ? ya[i < YR ? i : 0][c][j]
-                                    : *reinterpret_cast<const float4*>(a.yacc + ((size_t)b * YCS + c) * D + j * 256 + lane * 4);
-            xv[i][j].x += y.x; xv[i][j].y += y.y; xv[i][j].z += y.z; xv[i][j].w += y.w;
-          }
-      }
-      wave_ln_regs(xv[i], g);
-#pragma unroll
-      for (int j = 0; j < 3; ++j) dst[j * 64 + lane] = pack4_bf16(xv[i][j]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) dst[j * 64 + lane] = make_uint2(0u, 0u);
+        for (int j = 0; j < 3; ++j) {
+          const float4 y = i < YR ? ya[i < YR ? i : 0][c][j]
+                                  : *reinterpret_cast<const float4*>(a.yacc + ((size_t)b * YCS + c) * D + j * 256 + lane * 4);
+          xv[i][j].x += y.x; xv[i][j].y += y.y; xv[i][j].z += y.z; xv[i][j].w += y.w;
+        }
     }
+    ln_tile_row<MODE == MLMODE_EMBED || MODE == MLMODE_EMBED_SELECT>(a, live, b, ri[i], xv[i], g, xs + b * LDX, lane);
   }
   __syncthreads();
   // 3. MFMA 16x16x32: A = weight rows (lane & 15), B = tile rows (lane & 15) of column block t
@@ -2925,34 +2945,17 @@ __global__ __launch_bounds__(256) void ar_mfma_ln_kernel(GemvArgs a) {
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf[kk]),
                                                        __builtin_bit_cast(bf16x8_t, xf), acc[t], 0, 0, 0);
     }
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][(4 * (lane >> 4) + i) * (NT * 16) + t * 16 + (lane & 15)] = acc[t][i];
+  tile_put<NT>(red[wave], acc, lane);
   __syncthreads();
   for (int e = tid; e < 16 * NT * 16; e += NW * 64) {
     const int r = e / (NT * 16), b = e - r * (NT * 16), n = n0 + r;
     if (b >= B || n >= a.N) continue;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += red[w][e];
-    if constexpr (OUT == MLOUT_LOGITS && NT == 1) lgs[r * 17 + b] = v;
-    if constexpr (MODE == MLMODE_EMBED_SELECT) {  // c_attn's store with this step's new record (gemv_store<GOUT_QKV> reads rowinfo)
-      if (n < D) {
-        a.st.q[(size_t)b * D + n] = v;
-      } else {
-        const int c = (n - D) % D, which = (n - D) / D;
-        const int head = c / HD, d = c - head * HD;
-        const int4 rr = ri_s[b];
-        if (rr.x >= 0) store_kv(a, which, kv_at(a.layer, a.st.kv_chunks, a.st.max_streams, rr.x, head, rr.y) + d, v);
-      }
-    } else if (OUT == MLOUT_GELU_BF16) {
-      a.st.hb[(size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
-    } else {
-      gemv_store<OUT>(a, n, b, v);
-    }
+    const float v = tile_sum<NW, NT * 256>(red[0], e);
+    if constexpr (OUT == OUT_LOGITS && NT == 1) lgs[r * 17 + b] = v;
+    if (MODE == MLMODE_EMBED_SELECT && n >= D) kv_append(a, ri_s[b], n, v);  // this step's new record (rowinfo: the old one)
+    else step_store<OUT>(a, n, b, v);
   }
-  if constexpr (OUT == MLOUT_LOGITS && NT == 1) {
+  if constexpr (OUT == OUT_LOGITS && NT == 1) {
     if (a.defer_sel == SEL_LN_GRAN) {  // (kernel argument: uniform) this block's granule per row, pending flag
       // raw barrier after the LDS writes: __syncthreads() would also wait for the logits stores
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -3037,21 +3040,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int rr = wave * RPW + gi + i, b = r0 + rr;
-        uint2* dst = reinterpret_cast<uint2*>(xs + rr * LDX);
-        if (b < B) {
-          if (IN == BIN_EMBED) {
-            embed_row(a, ri[i], lane, xv[i]);
-            if (blockIdx.x == 0)
-#pragma unroll
-              for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = xv[i][j];
-          }
-          wave_ln_regs(xv[i], g);
-#pragma unroll
-          for (int j = 0; j < 3; ++j) dst[j * 64 + lane] = pack4_bf16(xv[i][j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 3; ++j) dst[j * 64 + lane] = make_uint2(0u, 0u);
-        }
+        ln_tile_row<IN == BIN_EMBED>(a, b < B, b, ri[i], xv[i], g, xs + rr * LDX, lane);
       }
     }
   } else {  // BIN_ROWS: bf16 operand rows (hb, or xn of the separate merge kernel) straight from global
@@ -3078,20 +3067,12 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf[kk]),
                                                        __builtin_bit_cast(bf16x8_t, xf[kk]), acc[t], 0, 0, 0);
   }
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][(4 * (lane >> 4) + i) * R + t * 16 + (lane & 15)] = acc[t][i];
+  tile_put<NT>(red[wave], acc, lane);
   __syncthreads();
   for (int e = tid; e < 16 * R; e += NTH) {
     const int r = e / R, c = e - r * R, n = n0 + r, b = r0 + c;
     if (b >= B || n >= a.N) continue;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v += red[w][e];
-    if (OUT == BOUT_GELU_BF16) a.st.hb[(size_t)b * DFF + n] = f32_to_bf16(gelu_tanh(v));
-    else if (OUT == BOUT_RESID) a.st.x[(size_t)b * D + n] += v;
-    else gemv_store<OUT>(a, n, b, v);
+    step_store<OUT>(a, n, b, tile_sum<NW, 16 * R>(red[0], e));  // (no pending copies on this path: a.yacc is null)
   }
 }
 
@@ -3108,7 +3089,7 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_bt_kernel(GemvArgs a) {
 // are summed through LDS in wave order: deterministic, and a row's result never depends on its batch
 // position (an MFMA column's dot product uses only that column's data).
 // ---------------------------------------------------------------------------------
-// KTOT > K (mlp c_proj, FOUT_SPLITK): the K = 3072 reduction split over blockIdx.z into KTOT / K slices of
+// KTOT > K (mlp c_proj, OUT_SPLITK): the K = 3072 reduction split over blockIdx.z into KTOT / K slices of
 // 768, each slice's partial stored to its pending copy (st.yacc), folded into x by the rows kernel
 // (ar_rows_kernel<RMODE_LN_Y_F32>) that normalises c_attn's / lm_head's operand rows (FIN_LN_ROWS): 4x the blocks, a
 // quarter of the bytes per block.
@@ -3119,7 +3100,7 @@ template <int K, int NT, int IN, int OUT, int KTOT = K, int CT = 1>
 __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) {
   constexpr int NWK = K / 192, NW = NWK * CT, R = NT * 16, NTH = NW * 64;
   constexpr bool STAGE = IN != FIN_H || CT > 1;  // K == 768: the operand tile in LDS (shared by the column tiles)
-  static_assert(KTOT == K || (IN == FIN_H && OUT == FOUT_SPLITK && KTOT == YCOPIES * K), "split K: mlp c_proj into the pending copies");
+  static_assert(KTOT == K || (IN == FIN_H && OUT == OUT_SPLITK && KTOT == YCOPIES * K), "split K: mlp c_proj into the pending copies");
   // FIN_ATTN_ROWS (c_proj after a one-split attention, ATTN_F32_ROWS): the normalised rows are split 0 of part_o
   // FIN_LN_ROWS (c_attn / lm_head after ar_rows_kernel<RMODE_LN_Y_F32>): the LayerNorm'd fp32 rows in st.h
   static_assert(!STAGE || K == 768, "the LDS operand tile holds K = 768 rows");
@@ -3167,33 +3148,21 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
 #pragma unroll
     for (int i = 0; i < RPW; ++i) {
       const int rr = wave * RPW + i, b = r0 + rr;
-      float* dst = xs + rr * LDX;
-      if (b < B) {
-        if (IN == FIN_EMBED) {
-          embed_row(a, ri[i], lane, xv[i]);
-          if (blockIdx.x == 0)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(a.st.x + (size_t)b * D + j * 256 + lane * 4) = xv[i][j];
-        }
-        wave_ln_regs(xv[i], g);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(dst + j * 256 + lane * 4) = xv[i][j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(dst + j * 256 + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
+      ln_tile_row<IN == FIN_EMBED>(a, b < B, b, ri[i], xv[i], g, xs + rr * LDX, lane);
     }
   } else if constexpr (IN == FIN_MERGE) {
     // split-KV merge (as gemv_stage_input GIN_MERGE): coefficients per (row, head, split), then every
     // element sums the partials of the nsm splits the attention ran at this B (attn_ns_max). The
     // splits past nsm have coefficient 0 (part_o is zeroed at allocation, finite): leaving them out
     // of the sum changes no bit, and at B = 32 (one split) it cuts the block's partial reads 16-fold
+    // attn_ns_max(B) (ar_plan.h) written out over the plan's ATTN_BLOCKS: the call in its place cost fp32 B = 4
+    // 3.1 us per step (profiles/r10/step_sweep_variants.txt)
     int nsm = NSPLIT;
-    while (nsm > 1 && nsm * N_HEAD * B > 256) nsm >>= 1;
+    while (nsm > 1 && nsm * N_HEAD * B > ATTN_BLOCKS) nsm >>= 1;
     for (int q = tid; q < R * N_HEAD; q += NTH) {
       const int bb = q / N_HEAD, head = q - bb * N_HEAD, b = min(r0 + bb, B - 1);
       const int4 ri = a.st.rowinfo[b];
-      float* cf = cf_s + q * NSPLIT;
+      float* cf = cf_s + q * NSPLIT;  // the coefficients as gemv_stage_input GIN_MERGE has them (two copies)
       const int t = ri.y + 1;
       const int ns = (ri.x < 0 || r0 + bb >= B) ? 0 : min(nsm, (t + 63) / 64);
       const float* ml = a.st.part_ml + ((size_t)(b * N_HEAD + head) * NSPLIT) * 2;
@@ -3299,21 +3268,13 @@ __global__ __launch_bounds__(K / 192 * 64 * CT) void ar_f32b_kernel(GemvArgs a) 
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[j].w, xf[j].w, acc[t], 0, 0, 0);
     }
   }
-  // lane: C[n0 + 4 (lane >> 4) + i][t * 16 + (lane & 15)]
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave][(4 * (lane >> 4) + i) * R + t * 16 + (lane & 15)] = acc[t][i];
+  tile_put<NT>(red[wave], acc, lane);
   __syncthreads();
   for (int e = tid; e < CT * 16 * R; e += NTH) {
     const int ct = e / (16 * R), el = e - ct * (16 * R);
     const int r = el / R, c = el - r * R, n = nb + ct * 16 + r, b = r0 + c;
     if (b >= B || n >= a.N) continue;
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWK; ++w) v += red[ct * NWK + w][el];
-    if constexpr (OUT == FOUT_SPLITK) a.yacc[((size_t)b * YCOPIES + ks) * D + n] = v;  // K slice ks -> its pending copy
-    else gemv_store<OUT>(a, n, b, v);
+    step_store<OUT>(a, n, b, tile_sum<NWK, 16 * R>(red[ct * NWK], el), ks);
   }
 }
 
@@ -3498,33 +3459,45 @@ void ar_launch_q0_tables(const ArWeights& w, int max_pos, float* text, float* co
 // The kernel choice is the plan's (ar_plan.h: ArStepPlan, the OP_ / select / mode-code names); only the
 // per-B template choice is left to the launch_* helpers.
 
+// operands of op (OP_*) at layer l: the weights row-major (W) and fragment-packed (Wf), the output width, and
+// the gamma of the LayerNorm ahead of the op. The attention has none of its own.
+static void set_op_operands(GemvArgs& a, const ArWeights& w, int op, int l) {
+  a.layer = l;
+  switch (op) {
+    case OP_QKV: a.W = w.w_attn[l]; a.Wf = w.f_attn[l]; a.N = 3 * D; a.ln_w = w.ln1[l]; break;
+    case OP_CPROJ: a.W = w.w_aproj[l]; a.Wf = w.f_aproj[l]; a.N = D; break;
+    case OP_FC: a.W = w.w_fc[l]; a.Wf = w.f_fc[l]; a.N = DFF; a.ln_w = w.ln2[l]; break;
+    case OP_MPROJ: a.W = w.w_mproj[l]; a.Wf = w.f_mproj[l]; a.N = D; break;
+    case OP_LM_HEAD: a.W = w.w_lm; a.Wf = w.f_lm; a.N = VOCAB; a.ln_w = w.lnf; break;
+  }
+}
+
 // batched path v3: one kernel per op (plus the attention), final x rows at every boundary
 static void launch_op_bt(int op, GemvArgs& a, const ArWeights& w, int l, const ArStepPlan& p, hipStream_t s) {
-  a.layer = l;
+  set_op_operands(a, w, op, l);
   a.yacc = nullptr;
   a.add_y = 0;
+  a.xpk = 0;  // (step_store<OUT_GELU_BF16> reads it: row-major hb on this path)
   switch (op) {
     case OP_QKV:
-      a.W = w.w_attn[l]; a.N = 3 * D; a.ln_w = w.ln1[l];
       if (p.sel != SEL_EMBED && p.sel != SEL_ARGMAX) ar_plan_bug(p, "v3 c_attn");
       if (l == 0 && p.sel == SEL_EMBED) {  // embedding + the previous step's select, then c_attn
         hipLaunchKernelGGL(ar_embed_select_kernel<>, dim3(p.B), dim3(256), 0, s, a);
-        launch_bt<768, BIN_ROWS, BOUT_QKV>(a, s);
+        launch_bt<768, BIN_ROWS, OUT_QKV>(a, s);
       } else if (l == 0) {
-        launch_bt<768, BIN_EMBED, BOUT_QKV>(a, s);
+        launch_bt<768, BIN_EMBED, OUT_QKV>(a, s);
       } else {
-        launch_bt<768, BIN_LN, BOUT_QKV>(a, s);
+        launch_bt<768, BIN_LN, OUT_QKV>(a, s);
       }
       break;
     case OP_ATTN: launch_attn(a.st, p.kv_dtype, p.B, l, s, p.nsplit); break;
     case OP_CPROJ:
-      a.W = w.w_aproj[l]; a.N = D;
       launch_merge_bf16(a.st, p.B, p.nsplit, s);
-      launch_bt<768, BIN_ROWS, BOUT_RESID>(a, s);
+      launch_bt<768, BIN_ROWS, OUT_RESID>(a, s);
       break;
-    case OP_FC: a.W = w.w_fc[l]; a.N = DFF; a.ln_w = w.ln2[l]; launch_bt<768, BIN_LN, BOUT_GELU_BF16>(a, s); break;
-    case OP_MPROJ: a.W = w.w_mproj[l]; a.N = D; launch_bt<3072, BIN_ROWS, BOUT_RESID>(a, s); break;
-    case OP_LM_HEAD: a.W = w.w_lm; a.N = VOCAB; a.ln_w = w.lnf; launch_bt<768, BIN_LN, BOUT_LOGITS>(a, s); break;
+    case OP_FC: launch_bt<768, BIN_LN, OUT_GELU_BF16>(a, s); break;
+    case OP_MPROJ: launch_bt<3072, BIN_ROWS, OUT_RESID>(a, s); break;
+    case OP_LM_HEAD: launch_bt<768, BIN_LN, OUT_LOGITS>(a, s); break;
   }
 }
 
@@ -3537,13 +3510,12 @@ static void launch_op_bt(int op, GemvArgs& a, const ArWeights& w, int l, const A
 // p.qsplit: c_attn split over K too (B <= 32), its partials summed by the attention; option exp bit 1024: one launch
 static void launch_op_f32b(int op, GemvArgs& a, const ArWeights& w, int l, const ArStepPlan& p, hipStream_t s) {
   const int B = p.B;
-  a.layer = l;
+  set_op_operands(a, w, op, l);
   a.yacc = p.ksplit ? a.st.yacc : nullptr;
   a.add_y = 0;
   a.xpk = 0;
   switch (op) {
     case OP_QKV:
-      a.W = w.w_attn[l]; a.Wf = w.f_attn[l]; a.N = 3 * D; a.ln_w = w.ln1[l];
       if (p.sel != SEL_ARGMAX && !(p.sel == SEL_EMBED && p.qsplit)) ar_plan_bug(p, "f32b c_attn");
       if (p.qsplit) {  // rows kernel (layer 0: embedding; else x + the MLP copies) -> fp32 rows, then the K slices
         if (l == 0 && p.sel == SEL_EMBED) hipLaunchKernelGGL(ar_embed_select_kernel<true>, dim3(B), dim3(256), 0, s, a);
@@ -3552,33 +3524,30 @@ static void launch_op_f32b(int op, GemvArgs& a, const ArWeights& w, int l, const
         if (B <= 16) hipLaunchKernelGGL((ar_qkv_ksplit_f32_kernel<1>), dim3(3 * D / 64, 4), dim3(256), 0, s, a);
         else hipLaunchKernelGGL((ar_qkv_ksplit_f32_kernel<2>), dim3(3 * D / 64, 4), dim3(256), 0, s, a);
       } else if (l == 0) {
-        launch_f32b<768, FIN_EMBED, FOUT_QKV>(a, s);
+        launch_f32b<768, FIN_EMBED, OUT_QKV>(a, s);
       } else if (p.ksplit) {
         hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y_F32>), dim3(B), dim3(64), 0, s, a);
-        launch_f32b<768, FIN_LN_ROWS, FOUT_QKV>(a, s);
+        launch_f32b<768, FIN_LN_ROWS, OUT_QKV>(a, s);
       } else {
-        launch_f32b<768, FIN_LN, FOUT_QKV>(a, s);
+        launch_f32b<768, FIN_LN, OUT_QKV>(a, s);
       }
       break;
     case OP_ATTN: launch_attn(a.st, p.kv_dtype, B, l, s, p.nsplit, p.attn_direct, 0, p.qsplit); break;
     case OP_CPROJ:
-      a.W = w.w_aproj[l]; a.Wf = w.f_aproj[l]; a.N = D;
-      if (p.attn_direct == ATTN_F32_ROWS) launch_f32b<768, FIN_ATTN_ROWS, FOUT_RESID>(a, s);
-      else launch_f32b<768, FIN_MERGE, FOUT_RESID>(a, s);
+      if (p.attn_direct == ATTN_F32_ROWS) launch_f32b<768, FIN_ATTN_ROWS, OUT_RESID>(a, s);
+      else launch_f32b<768, FIN_MERGE, OUT_RESID>(a, s);
       break;
-    case OP_FC: a.W = w.w_fc[l]; a.Wf = w.f_fc[l]; a.N = DFF; a.ln_w = w.ln2[l]; launch_f32b<768, FIN_LN, FOUT_GELU>(a, s); break;
+    case OP_FC: launch_f32b<768, FIN_LN, OUT_GELU>(a, s); break;
     case OP_MPROJ:
-      a.W = w.w_mproj[l]; a.Wf = w.f_mproj[l]; a.N = D;
-      if (p.ksplit) launch_f32b<768, FIN_H, FOUT_SPLITK, DFF>(a, s);
-      else launch_f32b<3072, FIN_H, FOUT_RESID>(a, s);
+      if (p.ksplit) launch_f32b<768, FIN_H, OUT_SPLITK, DFF>(a, s);
+      else launch_f32b<3072, FIN_H, OUT_RESID>(a, s);
       break;
     case OP_LM_HEAD:
-      a.W = w.w_lm; a.Wf = w.f_lm; a.N = VOCAB; a.ln_w = w.lnf;
       if (p.ksplit) {
         hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y_F32>), dim3(B), dim3(64), 0, s, a);
-        launch_f32b<768, FIN_LN_ROWS, FOUT_LOGITS>(a, s);
+        launch_f32b<768, FIN_LN_ROWS, OUT_LOGITS>(a, s);
       } else {
-        launch_f32b<768, FIN_LN, FOUT_LOGITS>(a, s);
+        launch_f32b<768, FIN_LN, OUT_LOGITS>(a, s);
       }
       break;
   }
@@ -3597,13 +3566,12 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
   // the MFMA GEMMs read the fragment-packed weight copies (a.Wf; round 6: the row-major reads of option
   // exp bit 2, bit-identical and slower, removed)
   a.xpk = p.xpk;
-  a.layer = l;
+  set_op_operands(a, w, op, l);
   a.yacc = mf ? a.st.yacc : nullptr;
   a.yfx = fm ? a.st.yfx : nullptr;
   a.add_y = l > 0;
   switch (op) {
     case OP_QKV:
-      a.W = w.w_attn[l]; a.Wf = w.f_attn[l]; a.N = 3 * D; a.ln_w = w.ln1[l];
       // layer 0: the embedding, after the previous step's select in the plan's form
       if (!(p.sel == SEL_ARGMAX || (mf ? p.sel == SEL_EMBED || p.sel == SEL_Q0_ROWS || (ln && p.sel == SEL_LN_GRAN)
                                        : p.sel == SEL_GRAN)))
@@ -3611,30 +3579,30 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
       if (l == 0 && p.l0_fused) {  // no launch: attention layer 0 runs the select and the q0 tables itself
       } else if (l > 0 && p.la_fused) {  // no launch: the attention runs the LayerNorm and its head's c_attn rows itself
       } else if (l == 0 && p.sel == SEL_LN_GRAN) {  // select + embedding in c_attn's prologue
-        launch_mfma_ln<MLOUT_QKV, MLMODE_EMBED_SELECT>(a, s);
+        launch_mfma_ln<OUT_QKV, MLMODE_EMBED_SELECT>(a, s);
       } else if (l == 0 && p.sel == SEL_Q0_ROWS) {  // select + c_attn from the q0 tables, 9 slices per row
         hipLaunchKernelGGL(ar_q0_rows_kernel, dim3(3 * D / 256, B), dim3(256), 0, s, a);
       } else if (l == 0 && p.sel == SEL_EMBED) {  // embedding + select, then c_attn
         hipLaunchKernelGGL(ar_embed_select_kernel<>, dim3(B), dim3(256), 0, s, a);
-        launch_mfma2<768, M2OUT_QKV>(a, s);
+        launch_mfma2<768, OUT_QKV>(a, s);
       } else if (ln) {
-        if (l == 0) launch_mfma_ln<MLOUT_QKV, MLMODE_EMBED>(a, s);
-        else launch_mfma_ln<MLOUT_QKV, MLMODE_LN_Y>(a, s);
+        if (l == 0) launch_mfma_ln<OUT_QKV, MLMODE_EMBED>(a, s);
+        else launch_mfma_ln<OUT_QKV, MLMODE_LN_Y>(a, s);
       } else if (mf) {  // rows kernel: LayerNorm (layer 0: of the embedding; else of x + the MLP copies)
         if (l == 0) hipLaunchKernelGGL((ar_rows_kernel<RMODE_EMBED>), dim3(B), dim3(64), 0, s, a);
         else if (l == 1 && p.l0_fused) hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y_COPY>), dim3(B), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y>), dim3(B), dim3(64), 0, s, a);
-        launch_mfma2<768, M2OUT_QKV>(a, s);
+        launch_mfma2<768, OUT_QKV>(a, s);
       } else if (l == 0 && p.q0_gran) {  // B <= 2: select + c_attn from the q0 tables
         hipLaunchKernelGGL(ar_q0_gran_kernel, dim3(3 * D / 256), dim3(256), 0, s, a);
       } else if (l == 0 && p.sel == SEL_GRAN) {
-        launch_gemv<TW, 768, 1, 2, GIN_EMBED_SELECT, GOUT_QKV>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_EMBED_SELECT, OUT_QKV>(a, s);
       } else if (l == 0) {
-        launch_gemv<TW, 768, 1, 2, GIN_EMBED, GOUT_QKV>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_EMBED, OUT_QKV>(a, s);
       } else if (fm) {
-        launch_gemv<TW, 768, 1, 2, GIN_LN_Y, GOUT_QKV>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN_Y, OUT_QKV>(a, s);
       } else {
-        launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_QKV>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN, OUT_QKV>(a, s);
       }
       break;
     case OP_ATTN:
@@ -3658,65 +3626,60 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
       launch_attn(a.st, p.kv_dtype, B, l, s, p.nsplit, p.attn_direct, p.selcopy && l == 0, false, p.attn8);
       break;
     case OP_CPROJ:
-      a.W = w.w_aproj[l]; a.Wf = w.f_aproj[l]; a.N = D;
       if (mf) {
         // ar_rows_kernel<RMODE_LN_Y> of this layer's c_attn folded them; la_fused has no such launch: c_proj folds
         if (!ln) a.add_y = p.la_fused && l > 0;
         if (p.nsplit > 1) launch_merge_bf16(a.st, B, p.nsplit, s, a.xpk);  // one split: the attention wrote xn itself
-        a.ln_w = w.ln2[l];  // M2OUT_RESID_STATS: the bf16 copy is x * ln_2.weight (c_fc's operand)
+        a.ln_w = w.ln2[l];  // OUT_RESID_STATS: the bf16 copy is x * ln_2.weight (c_fc's operand)
         // + bf16 x and row statistics for c_fc; 16-row batch tiles (B = 32: 96 blocks of 49 KB operands
         // instead of 48 of 74 KB: -3.4 us/step at t = 512-1,151)
-        if (!ln) launch_mfma2<768, M2OUT_RESID_STATS>(a, s, true);
-        else launch_mfma2<768, M2OUT_RESID>(a, s);
+        if (!ln) launch_mfma2<768, OUT_RESID_STATS>(a, s, true);
+        else launch_mfma2<768, OUT_RESID>(a, s);
       } else {
-        launch_gemv<TW, 768, 1, 1, GIN_MERGE, GOUT_RESID>(a, s);
+        launch_gemv<TW, 768, 1, 1, GIN_MERGE, OUT_RESID>(a, s);
       }
       break;
     case OP_FC:
-      a.W = w.w_fc[l]; a.Wf = w.f_fc[l]; a.N = DFF; a.ln_w = w.ln2[l];
       if (fm) {  // 16 h rows per block (192 blocks)
         const bf16_t* wfc = reinterpret_cast<const bf16_t*>(w.w_fc[l]);
         const bf16_t* wpk = reinterpret_cast<const bf16_t*>(w.w_mproj_pk[l]);
         if (B <= 1) hipLaunchKernelGGL((ar_mlp_fused_kernel<1, 16>), dim3(DFF / 16), dim3(256), 0, s, a, wfc, wpk);
         else hipLaunchKernelGGL((ar_mlp_fused_kernel<2, 16>), dim3(DFF / 16), dim3(256), 0, s, a, wfc, wpk);
       } else if (ln) {
-        launch_mfma_ln<MLOUT_GELU_BF16, MLMODE_LN>(a, s);
+        launch_mfma_ln<OUT_GELU_BF16, MLMODE_LN>(a, s);
       } else if (mf) {
         a.gsum = w.fc_gsum[l];
-        launch_mfma2<768, M2OUT_GELU_BF16, M2X_LN_AFTER>(a, s);  // LayerNorm from c_proj's row statistics, after the GEMM
+        launch_mfma2<768, OUT_GELU_BF16, M2X_LN_AFTER>(a, s);  // LayerNorm from c_proj's row statistics, after the GEMM
       } else {
-        launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_GELU>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN, OUT_GELU>(a, s);
       }
       break;
     case OP_MPROJ:
-      a.W = w.w_mproj[l]; a.Wf = w.f_mproj[l]; a.N = D;
       if (fm) return false;
       if (ln && YCS < YCOPIES)  // YCS K slices of DFF / YCS into the YCS copies
-        hipLaunchKernelGGL((ar_mfma2_kernel<DFF / YCS, 1, M2OUT_SPLITK, DFF>), dim3(D / 16, YCS), dim3(DFF / YCS / 192 * 64), 0, s, a);
-      else if (mf) launch_mproj_split<M2OUT_SPLITK>(a, s);
-      else launch_gemv<TW, 3072, 4, 2, GIN_H, GOUT_RESID>(a, s);
+        hipLaunchKernelGGL((ar_mfma2_kernel<DFF / YCS, 1, OUT_SPLITK, DFF>), dim3(D / 16, YCS), dim3(DFF / YCS / 192 * 64), 0, s, a);
+      else if (mf) launch_mproj_split<OUT_SPLITK>(a, s);
+      else launch_gemv<TW, 3072, 4, 2, GIN_H, OUT_RESID>(a, s);
       break;
     case OP_LM_HEAD:
-      a.W = w.w_lm; a.Wf = w.f_lm; a.N = VOCAB; a.ln_w = w.lnf;
       if (ln) {
-        launch_mfma_ln<MLOUT_LOGITS, MLMODE_LN_Y>(a, s);
+        launch_mfma_ln<OUT_LOGITS, MLMODE_LN_Y>(a, s);
       } else if (mf) {
         hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y>), dim3(B), dim3(64), 0, s, a);
-        launch_mfma2<768, M2OUT_LOGITS>(a, s);
+        launch_mfma2<768, OUT_LOGITS>(a, s);
       } else if (p.sel == SEL_GRAN) {
-        if (fm) launch_gemv<TW, 768, 1, 2, GIN_LN_Y, GOUT_LOGITS_GRAN>(a, s);
-        else launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_LOGITS_GRAN>(a, s);
+        if (fm) launch_gemv<TW, 768, 1, 2, GIN_LN_Y, OUT_LOGITS_GRAN>(a, s);
+        else launch_gemv<TW, 768, 1, 2, GIN_LN, OUT_LOGITS_GRAN>(a, s);
       } else if (fm) {
-        launch_gemv<TW, 768, 1, 2, GIN_LN_Y, GOUT_LOGITS>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN_Y, OUT_LOGITS>(a, s);
       } else {
-        launch_gemv<TW, 768, 1, 2, GIN_LN, GOUT_LOGITS>(a, s);
+        launch_gemv<TW, 768, 1, 2, GIN_LN, OUT_LOGITS>(a, s);
       }
       break;
   }
   return true;
 }
 
-template <typename TW>
 static GemvArgs make_args(const ArWeights& w, const ArState& st, int kvdtype, int B, const float* emb_row) {
   GemvArgs a{};
   a.st = st;
@@ -3741,7 +3704,7 @@ static void ar_layers(const ArWeights& w, const ArState& st, const ArStepPlan& p
   // SEL_SAMPLE: the layers and lm_head run as under SEL_ARGMAX (ar_launch_step swaps the kernel after lm_head)
   ArStepPlan p = plan;
   if (p.sel == SEL_SAMPLE) p.sel = SEL_ARGMAX;
-  GemvArgs a = make_args<TW>(w, st, p.kv_dtype, p.B, emb_row);
+  GemvArgs a = make_args(w, st, p.kv_dtype, p.B, emb_row);
   a.defer_sel = p.sel;
   if (emb_row) hipLaunchKernelGGL(ar_row_state_kernel, dim3(1), dim3(1), 0, s, st, slot, pos);
   for (int l = 0; l < N_LAYER; ++l)
@@ -3759,7 +3722,7 @@ int ar_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int
   if (which < OP_QKV || which > OP_LM_HEAD) return -1;
   if (which == OP_MPROJ && p.fused_mlp) return 1;  // no kernel of its own at this B
   if (iters == 0) return 0;                        // validation only
-  GemvArgs a = make_args<float>(w, st, kvdtype, B, nullptr);
+  GemvArgs a = make_args(w, st, kvdtype, B, nullptr);
   a.dst = st.logits;
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
   const int l = which == OP_LM_HEAD ? N_LAYER - 1 : 1;
@@ -3809,14 +3772,14 @@ __global__ __launch_bounds__(64) void ar_select_final_kernel(ArState st) {
 }
 
 // Test hook (lvx_select_probe): the greedy select of each production path over given logits
-// (st.logits). path 0: ar_argmax_kernel; 1: per-block lm_head granules formed as GOUT_LOGITS_GRAN forms them
+// (st.logits). path 0: ar_argmax_kernel; 1: per-block lm_head granules formed as OUT_LOGITS_GRAN forms them
 // (8 consecutive vocabulary rows per block), reduced by ar_select_final_kernel (lmg_reduce +
 // softmax_ties, the functions the deferred select in c_attn layer 0, GIN_EMBED_SELECT, calls); 2: the batched
 // deferred select, ar_embed_select_kernel; 4: the sampled select, ar_sample_kernel.
 __global__ void ar_select_probe_prep_kernel(ArState st, int B, int path) {
   const int blk = blockIdx.x, b = threadIdx.x;
   if (b >= B) return;
-  if (path == 3 && blk < LM8_BLOCKS) {  // as ar_mfma_ln_kernel MLOUT_LOGITS forms them: 16 vocabulary rows per block
+  if (path == 3 && blk < LM8_BLOCKS) {  // as ar_mfma_ln_kernel OUT_LOGITS forms them: 16 vocabulary rows per block
     Best r{-INFINITY, -INFINITY, 0x7fffffff};
     for (int n = blk * 16; n < blk * 16 + 16; ++n) r = best_merge(r, Best{st.logits[(size_t)b * VOCAB + n], -INFINITY, n});
     reinterpret_cast<u64x2_t*>(st.lmbest)[(size_t)blk * LM8_ROWS + b] = lm_granule(r);
@@ -3848,7 +3811,7 @@ int ar_select_probe(const ArWeights& w, const ArState& st, int B, int path, hipS
   } else if (path == 4) {  // the sampled select, with the slots' current parameters and positions
     hipLaunchKernelGGL(ar_sample_kernel, dim3(B), dim3(256), 0, s, st);
   } else {
-    GemvArgs a = make_args<float>(w, st, LVX_DTYPE_F32, B, nullptr);
+    GemvArgs a = make_args(w, st, LVX_DTYPE_F32, B, nullptr);
     a.ln_w = w.ln1[0];
     hipLaunchKernelGGL(ar_embed_select_kernel<>, dim3(B), dim3(256), 0, s, a);
   }
@@ -3949,7 +3912,7 @@ int ar_attn_probe(const ArWeights& w, const ArState& st, int wdtype, int kvdtype
   if (p.qsplit) return 1;
   p.sel = SEL_ARGMAX;
   p.selcopy = false;
-  GemvArgs a = make_args<float>(w, st, kvdtype, B, nullptr);
+  GemvArgs a = make_args(w, st, kvdtype, B, nullptr);
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);
   if (p.bf16) launch_op<bf16_t>(OP_ATTN, a, w, layer, p, s);
   else launch_op<float>(OP_ATTN, a, w, layer, p, s);
@@ -4023,7 +3986,7 @@ int ar_ops(const ArWeights& w, const ArState& st, int wdtype, int kvdtype, int B
   info[11] = op_last == OP_MPROJ ? nc : 0;  // copies still pending at the exit (c_proj has folded them)
   if (first % 5 == OP_ATTN && p.qsplit) return 1;
   if (op_last == OP_FC && p.fused_mlp) return 2;
-  GemvArgs a = make_args<float>(w, st, kvdtype, B, nullptr);
+  GemvArgs a = make_args(w, st, kvdtype, B, nullptr);
   a.defer_sel = p.sel;
   a.dst = st.logits;
   hipLaunchKernelGGL(ar_rowinfo_init_kernel, dim3((B + 63) / 64), dim3(64), 0, s, st, B);

@@ -11,38 +11,43 @@
 namespace lvx {
 
 // ---------------------------------------------------------------------------------
-// Mode codes of the kernel families (template parameters stay int; the same number means different
-// things in different families, hence one prefix per family).
-// The step's op (launch_op*, ar_probe's `which`): c_attn (layer 0: + embedding), attention, c_proj
+// Mode codes of the kernel families (template parameters stay int). The epilogue (OUT) has one numbering
+// for every family: ArOut. The prologue codes (IN / MODE / XM) keep one enum and one prefix per family,
+// because there the same number does mean different things (4: GIN_LN_Y, RMODE_LN_Y, FIN_ATTN_ROWS).
+// The step's op (launch_op, ar_probe's `which`): c_attn (layer 0: + embedding), attention, c_proj
 // (+ split merge), c_fc, mlp c_proj, lm_head.
 enum { OP_QKV = 0, OP_ATTN = 1, OP_CPROJ = 2, OP_FC = 3, OP_MPROJ = 4, OP_LM_HEAD = 5 };
+// OUT, the epilogue of every GEMM family (step_store): q + KV append | x += out | h = gelu(out) (fp32) |
+// logits | hb (bf16) = gelu(out) | split-K partial into a pending copy | x += out with the bf16 copy
+// x * ln_2.weight and the row statistics (c_fc's operand) | logits + per-block top-1 / top-2 granules.
+// What each family is instantiated with:
+//   ar_gemv_kernel     QKV RESID GELU LOGITS LOGITS_GRAN (its own epilogue: prefetched operands)
+//   ar_mfma2_kernel    QKV RESID LOGITS GELU_BF16 SPLITK RESID_STATS
+//   ar_mfma_ln_kernel  QKV LOGITS GELU_BF16
+//   ar_bt_kernel       QKV RESID LOGITS GELU_BF16
+//   ar_f32b_kernel     QKV RESID GELU LOGITS SPLITK
+enum ArOut {
+  OUT_QKV = 0, OUT_RESID = 1, OUT_GELU = 2, OUT_LOGITS = 3, OUT_GELU_BF16 = 5, OUT_SPLITK = 6, OUT_RESID_STATS = 7,
+  OUT_LOGITS_GRAN = 9
+};
 // ar_gemv_kernel IN (operand prologue): LayerNorm(x) | h (fp32, K = 3072) | merge of the split-KV
 // partials | layer-0 embedding (stores x) then LayerNorm | LayerNorm(x + the fused MLP's pending
 // copies) | EMBED after committing the previous step's select from lm_head's granules (B <= 2)
 enum { GIN_LN = 0, GIN_H = 1, GIN_MERGE = 2, GIN_EMBED = 3, GIN_LN_Y = 4, GIN_EMBED_SELECT = 5 };
-// ar_gemv_kernel OUT (epilogue, gemv_store): q + KV append | x += out | h = gelu(out) (fp32) | logits
-// | split-K partial into a pending copy (ar_f32b_kernel) | logits + per-block top-1 / top-2 granules
-enum { GOUT_QKV = 0, GOUT_RESID = 1, GOUT_GELU = 2, GOUT_LOGITS = 3, GOUT_SPLITK = 6, GOUT_LOGITS_GRAN = 9 };
 // ar_rows_kernel MODE (-> bf16 operand rows xn): LayerNorm(x) | embedding (stores x) then LayerNorm |
 // LayerNorm(x + pending copies), x made final | as LN_Y / EMBED with fp32 output rows in st.h | LN_Y that
 // also copies the fused layer-0 attention's shadow control records back (layer 1 of an l0_fused step)
 enum { RMODE_LN = 0, RMODE_EMBED = 3, RMODE_LN_Y = 4, RMODE_LN_Y_F32 = 5, RMODE_EMBED_F32 = 6, RMODE_LN_Y_COPY = 7 };
-// ar_mfma2_kernel OUT: as GOUT, plus h (bf16) = gelu(out) | split-K partial into a pending copy |
-// x += out with the bf16 copy x * ln_2.weight and the row statistics (c_fc's operand). XM: LayerNorm
-// applied after the GEMM from those statistics (c_fc)
-enum { M2OUT_QKV = 0, M2OUT_RESID = 1, M2OUT_LOGITS = 3, M2OUT_GELU_BF16 = 5, M2OUT_SPLITK = 6, M2OUT_RESID_STATS = 7 };
+// ar_mfma2_kernel XM: LayerNorm applied after the GEMM from OUT_RESID_STATS's statistics (c_fc)
 enum { M2X_NONE = 0, M2X_LN_AFTER = 1 };
-// ar_mfma_ln_kernel OUT (a subset of M2OUT) and MODE (the prologue every block runs for all B rows):
-// as RMODE, plus EMBED after committing the previous step's select from lm_head's granules (SEL_LN_GRAN)
-enum { MLOUT_QKV = 0, MLOUT_LOGITS = 3, MLOUT_GELU_BF16 = 5 };
+// ar_mfma_ln_kernel MODE (the prologue every block runs for all B rows): as RMODE, plus EMBED after
+// committing the previous step's select from lm_head's granules (SEL_LN_GRAN)
 enum { MLMODE_LN = 0, MLMODE_EMBED = 3, MLMODE_LN_Y = 4, MLMODE_EMBED_SELECT = 7 };
 // ar_bt_kernel IN: LayerNorm(x) | bf16 operand rows as they are (xn / hb) | embedding then LayerNorm
 enum { BIN_LN = 0, BIN_ROWS = 1, BIN_EMBED = 3 };
-enum { BOUT_QKV = 0, BOUT_RESID = 1, BOUT_LOGITS = 3, BOUT_GELU_BF16 = 5 };
 // ar_f32b_kernel IN: LayerNorm(x) | h (fp32) | split-KV merge | embedding then LayerNorm | the
 // one-split attention's normalised rows (ATTN_F32_ROWS) | ar_rows_kernel's fp32 rows in st.h
 enum { FIN_LN = 0, FIN_H = 1, FIN_MERGE = 2, FIN_EMBED = 3, FIN_ATTN_ROWS = 4, FIN_LN_ROWS = 6 };
-enum { FOUT_QKV = 0, FOUT_RESID = 1, FOUT_GELU = 2, FOUT_LOGITS = 3, FOUT_SPLITK = 6 };
 // launch_attn's `direct` (where a one-split attention writes the head output; 0: split partials for
 // a merge): bf16 operand row xn | xn fragment-packed (xfrag) | fp32 rows in split 0 of part_o
 enum { ATTN_PARTIALS = 0, ATTN_XN = 1, ATTN_XN_PACKED = 2, ATTN_F32_ROWS = 3 };

@@ -230,7 +230,7 @@ class Model:
         w = self.layer(l)
         g2 = w["ln1"] if "ln1_for_ln2" in self.mut else self.L[(l + 1) % NL]["ln2"] if "ln2_other_layer" in self.mut else w["ln2"]
         if self.mode == "rows":
-            # ar_mfma2_kernel M2OUT_RESID_STATS: ``xb = f32_to_bf16(xn * gpre[k])`` (x * ln_2.weight), (mean, M2) of x;
+            # ar_mfma2_kernel OUT_RESID_STATS: ``xb = f32_to_bf16(xn * gpre[k])`` (x * ln_2.weight), (mean, M2) of x;
             # M2X_LN_AFTER: ``v = (v - st.x * gpre[k]) * st.y`` = rstd * (W . xb - mean * G)
             xb = self.operand(x * g2)
             mean, rstd = self.ln_stats(x)

@@ -3,7 +3,7 @@ causal forward over the device's own tokens (oracle.reference_cpu.gpt_forward, t
 smallest B of every append site:
 
   bf16 B = 1            ar_q0_gran_kernel (layer 0), ar_gemv_kernel's epilogue (layers 1-3)
-  bf16 B = 3            ar_mfma_ln_kernel through gemv_store, every layer
+  bf16 B = 3            ar_mfma_ln_kernel through step_store, every layer
   bf16 B = 4            ar_q0_rows_kernel (layer 0), ar_mfma_ln_kernel (layers 1-3)
   bf16 B = 4, l0q 0     ar_mfma_ln_kernel's select prologue form (layer 0)
   bf16 B = 9            ar_q0_rows_kernel (layer 0), ar_mfma2_kernel (layers 1-3)
