@@ -1348,7 +1348,7 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-template <typename TKV, int NW, bool QKV, bool L0, bool LA = false, int RT = 1>
+template <typename TKV, int NW, bool QKV, bool L0, bool LA = false, int RT = 1, bool XF = false>
 __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns_max, int direct, int selcopy,
                                              const GemvArgs* a0) {
   // NW waves: a tile is NW x 16 keys (4 lanes per key); NW = 8 doubles the bytes in flight per
@@ -1486,9 +1486,31 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
   auto copy_tail = [&]() {
     if (cp) st.rowx[b] = make_int2(jn, plan_tok(st, b, jn + 1));
   };
+  // LA, XF (ArStepPlan::x_folded): the folded row v = x + c0 + c1 + c2 + c3 (xrow_sum's order, which is c_proj's x_plus_copies) is in
+  // every wave's registers; wave 0 stores this head's 96-column stripe of it into x2 for this layer's c_proj, which
+  // then neither loads nor adds the copies. Plain vector stores. Never into x: the row's other seven head blocks
+  // are still reading x[b] and would add the copies twice. x2[b] is written by attention l alone and read by c_proj
+  // l alone, with a kernel boundary in between; mlp c_proj l rewrites the copies only after c_proj l has run; the
+  // next writer of x2 is attention l + 1 (or layer 1 of the next step), behind c_proj l: nothing reads it across steps.
+  auto publish_x2 = [&](const float4 (&v)[3]) {
+    if constexpr (LA && XF) {
+      if (wave == 0) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int k = j * 256 + lane * 4;
+          if (k >= head * HD && k < head * HD + HD) *reinterpret_cast<float4*>(st.x2() + (size_t)b * D + k) = v[j];
+        }
+      }
+    }
+  };
   const int s = ri.x;
   if (s < 0) {
     copy_tail();
+    if constexpr (LA && XF) {  // an idle row's c_proj runs too (its x is whatever the step leaves, as before): the same sum
+      float4 v[3];
+      xrow_sum(xr, v);
+      publish_x2(v);
+    }
     // an idle row's fp32 operand is 0, as the merge would give it
     if (direct == ATTN_F32_ROWS && sp == 0 && tid < HD) st.part_o[(size_t)(b * N_HEAD + head) * NSPLIT * HD + tid] = 0.f;
     return;
@@ -1646,6 +1668,7 @@ __device__ __forceinline__ void attn_v2_body(const ArState st, int layer, int ns
     {
       float4 v[3];
       xrow_sum(xr, v);
+      publish_x2(v);
       wave_ln_regs(v, gam);
       uint2* dst = reinterpret_cast<uint2*>(xb_s[wave]);
 #pragma unroll
@@ -1841,7 +1864,7 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArg
 // layer-0 form. Grid (1, 8 heads, B): block (row, head) runs ar_rows_kernel<RMODE_LN_Y>'s LayerNorm of its row and
 // its head's 288 of c_attn's 2,304 output rows itself, with the history's first KV tiles in flight, so the
 // step has neither of those two launches at these layers (the pending copies are then folded into x by
-// c_proj: OUT_RESID_STATS with add_y). The head's 442 KB weight slice is the same for the B blocks of a
+// c_proj: OUT_RESID_STATS with add_y, or handed to it already folded: XF below). The head's 442 KB weight slice is the same for the B blocks of a
 // head, which share an XCD (head = linear block id mod 8): one fetch per XCD, then L2 hits. selcopy (layer
 // 1): the records of the fused layer-0 attention are read from the shadow arrays and copied back by the
 // head-0 block, as layer 0 of the unfused deferred-select forms does.
@@ -1849,10 +1872,12 @@ __global__ __launch_bounds__(256) LVX_LOADS_FIRST void ar_attn_l0_kernel(GemvArg
 #ifndef LVX_LA_RT
 #define LVX_LA_RT 3  // weight tiles in flight per wave (6 x 16 B per lane each)
 #endif
-template <typename TKV>
+// XF (ArStepPlan::x_folded): the block also publishes its stripe of the folded row for c_proj (publish_x2 above); a
+// template argument, so that the form which does not publish is the code it was.
+template <typename TKV, bool XF = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void ar_attn_la_kernel(GemvArgs a, int direct,
                                                                                                     int selcopy) {
-  attn_v2_body<TKV, 4, false, false, true, LVX_LA_RT>(a.st, a.layer, 1, direct, selcopy, &a);
+  attn_v2_body<TKV, 4, false, false, true, LVX_LA_RT, XF>(a.st, a.layer, 1, direct, selcopy, &a);
 }
 
 // ---------------------------------------------------------------------------------
@@ -2603,6 +2628,7 @@ template <int K, int NT, int OUT, int KTOT = K, int XM = 0>
 __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
   constexpr int NW = K / 192;  // waves per block, each a 192-wide K slice (6 MFMA k-steps)
   static_assert(XM != M2X_LN_AFTER || OUT == OUT_GELU_BF16, "LayerNorm after the GEMM: c_fc alone");
+  static_assert(XM != M2X_X2 || OUT == OUT_RESID_STATS, "the residual from x2: c_proj alone");
   __shared__ float red[NW][NT * 256];
   __shared__ float xo[OUT == OUT_RESID_STATS ? 16 * NT * 16 : 1];
   __shared__ float2 rs[XM == M2X_LN_AFTER ? NT * 16 : 1];
@@ -2658,7 +2684,11 @@ __global__ __launch_bounds__(K / 192 * 64) void ar_mfma2_kernel(GemvArgs a) {
     for (int k = 0; k < EPT; ++k) {
       const int e = min(tid + k * NW * 64, 16 * NT * 16 - 1), r = e / (NT * 16), b = e - r * (NT * 16);
       const int n = min(n0 + r, a.N - 1);
-      if constexpr (OUT == OUT_RESID_STATS) xpre[k] = x_plus_copies<YCOPIES>(a, min(r0 + b, B - 1), n);
+      if constexpr (OUT == OUT_RESID_STATS) {
+        // M2X_X2: the attention of this layer left x + the copies in x2, one load instead of five
+        if constexpr (XM == M2X_X2) xpre[k] = a.st.x2()[(size_t)min(r0 + b, B - 1) * D + n];
+        else xpre[k] = x_plus_copies<YCOPIES>(a, min(r0 + b, B - 1), n);
+      }
       gpre[k] = OUT == OUT_RESID_STATS ? a.ln_w[n] : a.gsum[n];
     }
   }
@@ -2801,6 +2831,133 @@ static void launch_mfma2(const GemvArgs& a, hipStream_t s, bool btile = false) {
   } else {
     launch_mfma2_nt<K, OUT, K, XM>(a, grid, s);
   }
+}
+
+// ln_f + lm_head in one launch by row groups (ArStepPlan::lm_fused; the step's last ar_rows_kernel launch and its
+// boundary go). Block (vocab slice of NCOL columns, group of R batch rows): the four waves run
+// ar_rows_kernel<RMODE_LN_Y>'s fold and LayerNorm of R / 4 rows each by the same functions (xrow_issue, xrow_sum,
+// wave_ln_regs, pack4_bf16) into one fragment-packed LDS tile of bf16 operand rows, then the block runs its NCOL / 16
+// column tiles as ar_mfma2_kernel<768, NT, OUT_LOGITS> computes them: v_mfma_f32_16x16x32_bf16, wave w over k in
+// [192 w, 192 w + 192) in six k-steps, the waves' partials summed in wave order through LDS. An output element
+// depends on its weight row and its batch column alone, so the MFMA columns past the group's rows (they repeat its
+// last row) are not stored and the bits are those of the two launches. The fragment-packed f_lm weights stream
+// through a ring of at most four tiles, every refill behind its use; gamma, x and the copies of the rows are issued
+// ahead of them (clamped rows: no load under a branch).
+// x is not made final here as the rows kernel does: the other slices' blocks of the group are reading x[b] and the
+// copies in this launch (a store would have them add the copies twice), and in such a step nothing reads x after
+// lm_head: the next step's layer-0 attention rebuilds it from the embedding (lvx_ar_ops plans without the tables and
+// keeps the two launches).
+// Block order: ids i and i + 8 share an XCD under round-robin placement, so the G row groups of slice
+// (i / 8G) * 8 + i % 8 sit at i % 8 + 8 g: the slice crosses the fabric once and the other groups find it in that
+// XCD's L2 (speed only). The groups of a slice start at different column tiles (tile order rotated by the group,
+// as the fused layers form rotates by the row): blocks of one XCD asking for one line at once serialise on the fabric.
+// the value is first used here (as the whole 16-byte register tuple its load wrote: no component copies)
+__device__ __forceinline__ void pin4(float4& v) {
+  f32x4_t t = __builtin_bit_cast(f32x4_t, v);
+  asm volatile("" : "+v"(t));
+  v = __builtin_bit_cast(float4, t);
+}
+template <int R, int NCOL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void ar_lm_rows_kernel(GemvArgs a) {
+  constexpr int NT = NCOL / 16, RW = R / 4, RT = NT < 4 ? NT : 4, LDT = 16 * 17;
+  static_assert(R % 4 == 0 && R <= 16 && RW <= 2 && NCOL % 16 == 0 && (VOCAB / NCOL) % 8 == 0, "row groups x vocab slices");
+  __shared__ __attribute__((aligned(16))) bf16_t xs[16 * D];  // xfrag order of one 16-row batch tile (rows < R written)
+  __shared__ float red[4][NT * LDT];                          // [wave][tile][vocab row][batch column], rows padded to 17
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int B = a.B, G = (B + R - 1) / R;
+  const int id = blockIdx.x, g = (id >> 3) % G, sl = (id / (8 * G)) * 8 + (id & 7);
+  TS_DECL;
+  TS_MARK(0);
+  float4 gam[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) gam[j] = *reinterpret_cast<const float4*>(a.ln_w + j * 256 + lane * 4);
+  XRow<GIN_LN_Y> xr[RW];
+#pragma unroll
+  for (int i = 0; i < RW; ++i) xrow_issue(a, min(g * R + wave * RW + i, B - 1), lane, xr[i]);
+  // the rows ahead of the weights (vmcnt retires in issue order: the LayerNorm waits for the rows alone), and every
+  // load ahead of the first use (the empty asm keeps the optimiser, the builtin the scheduler from moving them)
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  const int rot = g % NT;
+  auto tile_of = [&](int i) { const int j = i + rot; return j >= NT ? j - NT : j; };  // the i-th tile this block runs
+  const uint4* wsl = reinterpret_cast<const uint4*>(a.Wf) + ((size_t)sl * NT * (D / 32) + wave * 6) * 64 + lane;
+  uint4 wr[RT][6];
+#pragma unroll
+  for (int i = 0; i < RT; ++i)
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk) wr[i][kk] = wsl[((size_t)tile_of(i) * (D / 32) + kk) * 64];
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < RW; ++i)  // (the rows are first used here, not among the loads: instruction selection orders
+#pragma unroll                  // unchained arithmetic freely, and put the packed adds' register moves and their waits
+    for (int j = 0; j < 3; ++j) {  // ahead of the weight loads)
+      if (i == 0) pin4(gam[j]);
+      pin4(xr[i].x[j]);
+#pragma unroll
+      for (int c = 0; c < YCOPIES; ++c) pin4(xr[i].y[c][j]);
+    }
+#pragma unroll
+  for (int i = 0; i < RW; ++i) {
+    float4 v[3];
+    xrow_sum(xr[i], v);
+    wave_ln_regs(v, gam);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) *reinterpret_cast<uint2*>(xs + xfrag(wave * RW + i, j * 256 + lane * 4, D)) = pack4_bf16(v[j]);
+  }
+  lds_barrier();  // (not __syncthreads: the weight tiles stay in flight)
+  TS_MARK(1);
+  uint4 xf[6];
+#pragma unroll
+  for (int kk = 0; kk < 6; ++kk)  // batch column lane % 16, clamped to the group's last row
+    xf[kk] = *reinterpret_cast<const uint4*>(xs + ((size_t)((wave * 6 + kk) * 64 + (lane & 48) + min(lane & 15, R - 1)) << 3));
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    f32x4_t acc = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 6; ++kk)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wr[i % RT][kk]),
+                                                    __builtin_bit_cast(bf16x8_t, xf[kk]), acc, 0, 0, 0);
+    if (i + RT < NT) {
+#pragma unroll
+      for (int kk = 0; kk < 6; ++kk) wr[i % RT][kk] = wsl[((size_t)tile_of(i + RT) * (D / 32) + kk) * 64];
+    }
+    if ((lane & 15) < R) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][tile_of(i) * LDT + (4 * (lane >> 4) + r) * 17 + (lane & 15)] = acc[r];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  lds_barrier();
+#pragma unroll
+  for (int e = tid; e < NCOL * R; e += 256) {  // consecutive threads: consecutive columns of one row
+    const int bl = e / NCOL, nl = e - bl * NCOL, b = g * R + bl;
+    const int o = (nl >> 4) * LDT + (nl & 15) * 17 + bl;
+    float v = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) v += red[w][o];
+    if (b < B) a.dst[(size_t)b * a.N + sl * NCOL + nl] = v;
+  }
+  TS_SAVE(10, a.layer, blockIdx.x);
+}
+#ifndef LVX_LM_R  // rows per group and columns per slice of the fused lm_head (A/B builds: tools/build_variant.sh)
+#define LVX_LM_R 8
+#define LVX_LM_NCOL 64
+#endif
+static void launch_lm_rows(const GemvArgs& a, hipStream_t s) {
+  const int G = (a.B + LVX_LM_R - 1) / LVX_LM_R;
+  hipLaunchKernelGGL((ar_lm_rows_kernel<LVX_LM_R, LVX_LM_NCOL>), dim3(G * (VOCAB / LVX_LM_NCOL)), dim3(256), 0, s, a);
+}
+
+// c_proj of an x_folded step (16 <= B <= 32): launch_mfma2<768, OUT_RESID_STATS>'s 16-row batch tiles (one tile, or
+// two in the XCD-aligned order) with the residual from x2; the wider tiles of that helper are never launched here
+static void launch_cproj_x2(const GemvArgs& a, hipStream_t s) {
+  static_assert(D / 16 % 8 == 0, "XCD-aligned order (xmap 2)");
+  if (a.B > 32) abort();
+  GemvArgs b = a;
+  b.xmap = a.B > 16 ? 2 : 0;
+  hipLaunchKernelGGL((ar_mfma2_kernel<768, 1, OUT_RESID_STATS, 768, M2X_X2>), dim3(D / 16 * (a.B > 16 ? 2 : 1)), dim3(256), 0,
+                     s, b);
 }
 
 // (round 2-5: c_attn at 9 <= B <= 32 as four K-slice partials summed by the attention, the block's
@@ -3616,10 +3773,14 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
       }
       if (l > 0 && p.la_fused) {  // LayerNorm + this head's c_attn rows + attention; layer 1 copies layer 0's shadow records back
         a.Wf = w.f_attn[l]; a.ln_w = w.ln1[l];
-        if (p.kv_dtype == LVX_DTYPE_BF16)
-          hipLaunchKernelGGL(ar_attn_la_kernel<bf16_t>, dim3(1, N_HEAD, B), dim3(256), 0, s, a, p.attn_direct, (int)(l == 1));
-        else if (p.kv_dtype == LVX_DTYPE_FP8)
-          hipLaunchKernelGGL(ar_attn_la_kernel<fp8_t>, dim3(1, N_HEAD, B), dim3(256), 0, s, a, p.attn_direct, (int)(l == 1));
+        const dim3 grid(1, N_HEAD, B);
+        const int ad = p.attn_direct, sc = l == 1;
+        if (p.kv_dtype == LVX_DTYPE_BF16 && p.x_folded)
+          hipLaunchKernelGGL((ar_attn_la_kernel<bf16_t, true>), grid, dim3(256), 0, s, a, ad, sc);
+        else if (p.kv_dtype == LVX_DTYPE_BF16) hipLaunchKernelGGL((ar_attn_la_kernel<bf16_t>), grid, dim3(256), 0, s, a, ad, sc);
+        else if (p.kv_dtype == LVX_DTYPE_FP8 && p.x_folded)
+          hipLaunchKernelGGL((ar_attn_la_kernel<fp8_t, true>), grid, dim3(256), 0, s, a, ad, sc);
+        else if (p.kv_dtype == LVX_DTYPE_FP8) hipLaunchKernelGGL((ar_attn_la_kernel<fp8_t>), grid, dim3(256), 0, s, a, ad, sc);
         else ar_plan_bug(p, "fused layers attention");
         break;
       }
@@ -3628,12 +3789,14 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
     case OP_CPROJ:
       if (mf) {
         // ar_rows_kernel<RMODE_LN_Y> of this layer's c_attn folded them; la_fused has no such launch: c_proj folds
-        if (!ln) a.add_y = p.la_fused && l > 0;
+        // (x_folded: the attention already did, into x2: nothing to fold)
+        if (!ln) a.add_y = p.la_fused && l > 0 && !p.x_folded;
         if (p.nsplit > 1) launch_merge_bf16(a.st, B, p.nsplit, s, a.xpk);  // one split: the attention wrote xn itself
         a.ln_w = w.ln2[l];  // OUT_RESID_STATS: the bf16 copy is x * ln_2.weight (c_fc's operand)
         // + bf16 x and row statistics for c_fc; 16-row batch tiles (B = 32: 96 blocks of 49 KB operands
         // instead of 48 of 74 KB: -3.4 us/step at t = 512-1,151)
-        if (!ln) launch_mfma2<768, OUT_RESID_STATS>(a, s, true);
+        if (!ln && p.x_folded && l > 0) launch_cproj_x2(a, s);  // the residual from x2
+        else if (!ln) launch_mfma2<768, OUT_RESID_STATS>(a, s, true);
         else launch_mfma2<768, OUT_RESID>(a, s);
       } else {
         launch_gemv<TW, 768, 1, 1, GIN_MERGE, OUT_RESID>(a, s);
@@ -3664,6 +3827,8 @@ static bool launch_op(int op, GemvArgs& a, const ArWeights& w, int l, const ArSt
     case OP_LM_HEAD:
       if (ln) {
         launch_mfma_ln<OUT_LOGITS, MLMODE_LN_Y>(a, s);
+      } else if (mf && p.lm_fused) {  // ln_f of a row group + a vocab slice of lm_head per block
+        launch_lm_rows(a, s);
       } else if (mf) {
         hipLaunchKernelGGL((ar_rows_kernel<RMODE_LN_Y>), dim3(B), dim3(64), 0, s, a);
         launch_mfma2<768, OUT_LOGITS>(a, s);

@@ -38,8 +38,9 @@ enum { GIN_LN = 0, GIN_H = 1, GIN_MERGE = 2, GIN_EMBED = 3, GIN_LN_Y = 4, GIN_EM
 // LayerNorm(x + pending copies), x made final | as LN_Y / EMBED with fp32 output rows in st.h | LN_Y that
 // also copies the fused layer-0 attention's shadow control records back (layer 1 of an l0_fused step)
 enum { RMODE_LN = 0, RMODE_EMBED = 3, RMODE_LN_Y = 4, RMODE_LN_Y_F32 = 5, RMODE_EMBED_F32 = 6, RMODE_LN_Y_COPY = 7 };
-// ar_mfma2_kernel XM: LayerNorm applied after the GEMM from OUT_RESID_STATS's statistics (c_fc)
-enum { M2X_NONE = 0, M2X_LN_AFTER = 1 };
+// ar_mfma2_kernel XM: LayerNorm applied after the GEMM from OUT_RESID_STATS's statistics (c_fc) | OUT_RESID_STATS
+// with the residual from ArState::x2(), where the fused attention left x + the pending copies (x_folded steps)
+enum { M2X_NONE = 0, M2X_LN_AFTER = 1, M2X_X2 = 2 };
 // ar_mfma_ln_kernel MODE (the prologue every block runs for all B rows): as RMODE, plus EMBED after
 // committing the previous step's select from lm_head's granules (SEL_LN_GRAN)
 enum { MLMODE_LN = 0, MLMODE_EMBED = 3, MLMODE_LN_Y = 4, MLMODE_EMBED_SELECT = 7 };
@@ -95,6 +96,13 @@ struct ArStepPlan {
   // block (row, head) runs the row's LayerNorm and its head's c_attn rows itself (ar_attn_la_kernel), layer 1's
   // copies the shadow records back, and c_proj folds the pending copies into x
   bool la_fused;
+  // la_fused steps at B >= 16 with option xfold: that attention block publishes its 96-column stripe of x + the pending copies
+  // (the sum it formed for the LayerNorm) into ArState::x2(), and c_proj of layers 1-3 takes its residual from
+  // there instead of loading x and the four copies and adding them again (ar_mfma2_kernel XM = M2X_X2)
+  bool x_folded;
+  // la_fused steps with option lmf: no ar_rows_kernel launch ahead of lm_head; ln_f of a row group and a vocab
+  // slice of lm_head in one launch (ar_lm_rows_kernel)
+  bool lm_fused;
 };
 
 constexpr int MFMA_BATCH_MIN = 3;  // smallest B on the batched MFMA path (measured B = 3: 117 vs 154 us, B = 2: 119 vs 114)
@@ -199,6 +207,20 @@ inline ArStepPlan ar_plan_step(const Opts& o_, int wdtype, int kvdtype, int B, b
   // The fused layers form on the same cells (each attention block of layers 1-3 is then its own c_attn: no
   // hand-off between workgroups, the head's weight slice shared through the XCD's L2)
   p.la_fused = o.laf && p.l0_fused;
+  // The two tail forms ride on the fused layers form (ar_probe / ar_ops plan without the tables and so keep the
+  // separate kernels they model; sampling plans are never la_fused)
+  // Measured per part (tools/step_sweep.py, t = 384-639, option sets in one process, us per step off -> on, against
+  // the parent library's max - min over its runs in that cell):
+  //   xfold  bf16 KV B = 32: 116.3 -> 114.0 (spread 1.9), B = 16: 95.9 -> 94.5 (1.0), B = 9: 90.9 -> 91.0 (0.2);
+  //          fp8 KV B = 32: 100.0 -> 98.0 (0.5), B = 17: 95.2 -> 94.7 (0.4)
+  //   lmf    bf16 KV B = 32: 116.3 -> 115.7 (1.9), B = 16: 95.9 -> 95.1 (1.0), B = 9: 90.9 -> 89.9 (0.2);
+  //          fp8 KV B = 32: 100.0 -> 99.2 (0.5), B = 17: 95.2 -> 94.2 (0.4)
+  // xfold does nothing for few rows (c_proj's loads are not what such a step waits for): off below B = 16. At fp8 KV
+  // B = 17 its 0.4-0.5 only equals the spread; it stays on there, since the gain repeats to 0.1 in process and the cell
+  // sits between two that clear it. lmf at bf16 KV B = 16 / 32 is inside the parent's process-to-process spread but
+  // repeats to 0.1 in process (twice each) and is never a loss: it stays on in every la_fused cell.
+  p.x_folded = o.xfold && p.la_fused && B >= 16;
+  p.lm_fused = o.lmf && p.la_fused;
   // fragment-packed operand rows on the v2 steps with the rows kernel at B <= 32
   p.xpk = (p.path == PATH_MFMA_ROWS && B <= 32) ? 1 : 0;
   p.attn_direct = p.nsplit > 1 || !(mf || p.path == PATH_F32B) ? ATTN_PARTIALS

@@ -649,7 +649,7 @@ int lvx_finalize(lvx_ctx* c) {
   c->smp_temp.assign(S, 0.f);
   c->n_sampling = 0;
   if ((r = c->dalloc(&st.slots, S)) || (r = c->dalloc(&st.pos, S)) || (r = c->dalloc(&st.prev, S)) ||
-      (r = c->dalloc(&st.err, 4)) || (r = c->dalloc(&st.x, (size_t)S * D)) || (r = c->dalloc(&st.q, (size_t)S * D)) ||
+      (r = c->dalloc(&st.err, 4)) || (r = c->dalloc(&st.x, (size_t)2 * S * D)) || (r = c->dalloc(&st.q, (size_t)S * D)) ||
       (r = c->dalloc(&st.part_o, (size_t)S * N_HEAD * NSPLIT * HD)) ||
       (r = c->dalloc(&st.part_ml, (size_t)S * N_HEAD * NSPLIT * 2)) || (r = c->dalloc(&st.h, (size_t)S * DFF)) ||
       (r = c->dalloc(&st.logits, (size_t)S * VOCAB)) || (r = c->dalloc(&st.rowinfo, S)) ||
@@ -663,6 +663,7 @@ int lvx_finalize(lvx_ctx* c) {
     return r;
   HIP_TRY(hipMemset(st.yfx, 0, (size_t)YCOPIES * S * D * 8));
   HIP_TRY(hipMemset(st.yacc, 0, (size_t)YCOPIES * S * D * 4));
+  HIP_TRY(hipMemset(st.x, 0, (size_t)2 * S * D * 4));  // (every row of x2 that c_proj reads was published by its attention blocks first: defined bytes, no more)
   HIP_TRY(hipMemset(st.selp, 0, 16));
   HIP_TRY(hipMemset(st.part_o, 0, (size_t)S * N_HEAD * NSPLIT * HD * 4));
   HIP_TRY(hipMemset(st.part_ml, 0, (size_t)S * N_HEAD * NSPLIT * 2 * 4));
@@ -895,6 +896,8 @@ int lvx_set_option(lvx_ctx* c, const char* name, int value) {
   else if (n == "l0q") o.l0q = value != 0;
   else if (n == "l0a") o.l0a = value != 0;
   else if (n == "laf") o.laf = value != 0;
+  else if (n == "xfold") o.xfold = value != 0;
+  else if (n == "lmf") o.lmf = value != 0;
   else if (n == "fmt_group") o.fmt_group = std::min(std::max(value, 0), 32);
   else return fail(LVX_E_NAME, "unknown option " + n);
   ++c->opt_epoch;  // this context's captured kernels change (checked in cached_graph)

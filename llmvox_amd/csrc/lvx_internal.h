@@ -52,6 +52,11 @@ struct Opts {
   int laf = 1;           // the same steps (l0a on): LayerNorm and c_attn of layers 1-3 inside their attention blocks
                          // (ar_attn_la_kernel); 0: ar_rows_kernel + c_attn + attention (bit-identical:
                          // tests/test_gpu_la_fused.py)
+  int xfold = 1;         // la_fused steps at B >= 16: the attention blocks of layers 1-3 publish x + the pending mlp copies (the sum
+                         // they form for their LayerNorm) into the second plane of x, and c_proj takes its residual
+                         // from there; 0: c_proj loads x and the four copies and folds them again
+  int lmf = 1;           // la_fused steps: ln_f and lm_head in one launch by row groups (ar_lm_rows_kernel); 0:
+                         // ar_rows_kernel + the lm_head GEMM (both bit-identical: tests/test_gpu_tail_fused.py)
   int fmt_group = 0;     // formant stage: hop blocks a workgroup writes, 1 .. 32; 0: chosen per launch from its rows and
                          // their lengths (pcm_launch_formant). Bit-identical at every value: tests/test_gpu_pcm_formant.py
 };
@@ -137,7 +142,10 @@ struct ArState {
                                 // of range in the drop-in gathers, 32 fused-MLP fixed-point range); [1] codec
                                 // (4 code out of range, 8 ISTFT envelope); [2] / [3] take slots of
                                 // lvx_check_errors / lvx_stream_position
-  float* x = nullptr;           // [B][768] residual stream
+  float* x = nullptr;           // [2][max_streams][768]: the residual stream [B][768], and a second plane x2() of folded
+                                // rows (ArStepPlan::x_folded: written by attention l, read by c_proj l; no member of
+                                // its own: see smp)
+  __host__ __device__ float* x2() const { return x + (size_t)max_streams * D; }
   float* q = nullptr;           // [B][768]
   float* part_o = nullptr;      // [B][8][NSPLIT][96]
   float* part_ml = nullptr;     // [B][8][NSPLIT][2]

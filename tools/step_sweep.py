@@ -59,4 +59,4 @@ for spec, smp in runs:
         for s in range(B):
             e.set_sampling(s, 0.0, 0, 0)
     for k, v in opts:
-        e.set_option(k, {"bt": 1, "defer_select": 1, "fuse_mlp": 1, "codec_g2": 1, "codec_g3": 1, "codec_skinny": 1, "f32b": 1, "ln_max": 8, "l0q": 1, "l0a": 1, "laf": 1}.get(k, 0))
+        e.set_option(k, {"bt": 1, "defer_select": 1, "fuse_mlp": 1, "codec_g2": 1, "codec_g3": 1, "codec_skinny": 1, "f32b": 1, "ln_max": 8, "l0q": 1, "l0a": 1, "laf": 1, "xfold": 1, "lmf": 1}.get(k, 0))

@@ -22,7 +22,9 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 P0 = int(sys.argv[2]) if len(sys.argv) > 2 else 512
 graphs = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 TAGS = {0: "rows", 1: "c_attn", 2: "attn", 3: "c_proj", 4: "c_fc", 5: "mlp_proj", 6: "lm_head", 7: "embed_sel",
-        8: "rows_lm", 9: "fused_q"}  # fused_q: the fused layer-0 / layers attention's (entry, q ready, end of the KV loop)
+        8: "rows_lm", 9: "fused_q", 10: "lm_fused"}
+# fused_q: the fused layer-0 / layers attention's (entry, q ready, end of the KV loop); lm_fused: ar_lm_rows_kernel's
+# (entry, operand rows ready, end)
 NBLK = 1024
 lib = _lib.load()
 lib.lvx_debug_timeline.restype = ctypes.c_int
